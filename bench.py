@@ -1,7 +1,13 @@
 """Benchmark: op-log compose+conflict throughput on device-resident synthetic logs.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--n-ops N]
-                    [--weak | --independent] [--no-pmc] [--no-cpu-baseline] [--no-e2e] [--no-async] [--no-breakdown]
+                    [--weak | --independent] [--dump-outputs DIR]
+                    [--full [--no-pmc] [--no-cpu-baseline] [--no-e2e] [--no-async] [--no-breakdown]]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given, and prints the result line.  Every other leg below (the
+per-stage breakdown, the async / timers-off legs, the PMC traffic passes, the CPU
+baselines, the drop-in legs) runs only with --full; their keys are null without it.
 
 One step = one composition (semmerge/compose.py:11-114 restated on the GPU) of
 SURVEY §8(d) config 3: 100M lift-shaped ops (50M per branch), 1M symbols, seed 11.
@@ -19,7 +25,7 @@ The time is the max over ranks; rank 0 prints one JSON line.
 
 roofline is SURVEY §8(d)'s figure for the whole merge: 53 B/op over the smx_compose
 wall time (ms_per_step); kernel_roofline is the plan's dominant kernel alone.
-Rank 0 at N = 1 also reports, after the timed steps (never inside them):
+With --full, rank 0 at N = 1 also reports, after the timed steps (never inside them):
   roofline.traffic / kernel_roofline.traffic  HBM bytes per merge from rocprofv3 --pmc
         FETCH_SIZE and WRITE_SIZE passes over this same workload (child processes,
         one counter per pass; FETCH_SIZE x2 for gfx950's streaming reads, WRITE_SIZE
@@ -32,6 +38,14 @@ Rank 0 at N = 1 also reports, after the timed steps (never inside them):
         native marshal, device compose, native materialise
   small_merge    a 1k-op merge (the CLI's size): device latency on resident buffers (the
         one-workgroup plan) and the drop-in on Op objects
+
+--dump-outputs DIR writes what the last timed step left in the caller's output buffers
+(order, addr, file, ctx, the conflict pairs and the two counts) as DIR/<name>.npy in
+float64 (every value is an int32 or a count, exact in float64).  Above DUMP_SAMPLE
+composed ops the four per-op arrays are sampled at fixed seeded positions
+(DIR/sample_index.npy), -1 where the position is past the composed count.  The inputs
+come from the config's seed, so two builds run with the same arguments are comparable
+file by file.  N > 1: each rank writes its shard's buffers as <name>_rank<r>.npy.
 """
 from __future__ import annotations
 
@@ -70,6 +84,8 @@ WINDOW_BYTES_PER_OP = ROOF_STAGES["window"][1]
 ROOF_STEPS = 3  # timed steps whose roofline-kernel launches carry HIP events
 REF_PY_OPS_S = 47_600          # SURVEY §3.4 / BASELINE.md: reference compose_oplogs, 1 core, 1M ops
 FETCH_FACTOR, WRITE_FACTOR = 2.0, 1.0   # gfx950 FETCH_SIZE reads 1/2 of streamed bytes (guide)
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: positions kept of each per-op output (all ranks together)
+DUMP_SEED = 20240611
 
 
 def log(*a):
@@ -131,6 +147,33 @@ def pmc_traffic(args) -> dict:
                               "and x1 the lower bound"}
     out["status"] = "ok"
     return out
+
+
+def dump_outputs(path: str, bufs, rank: int, world: int) -> None:
+    """The caller's output buffers after the last timed step -> path/<name>.npy (float64)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    k, nc = (int(x) for x in bufs.counts.cpu().tolist())
+    n = bufs.order.numel()
+    keep = max(DUMP_SAMPLE // world, 1)
+    if n <= keep:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, keep, dtype=np.int64))
+    didx = torch.from_numpy(idx).to(bufs.order.device)
+    valid = idx < max(k, 0)
+
+    def save(name, a):
+        np.save(os.path.join(path, name + sfx + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    save("counts", np.array([k, nc]))
+    save("sample_index", idx)
+    for name in ("order", "addr", "file", "ctx"):
+        v = getattr(bufs, name)[didx].cpu().numpy().astype(np.float64)
+        save(name, np.where(valid, v, -1.0))
+    ncw = max(min(nc, bufs.conf.numel() // 2, DUMP_SAMPLE), 0)   # (counts holds nc itself)
+    save("conflicts", bufs.conf[: 2 * ncw].cpu().numpy().reshape(ncw, 2))
 
 
 def cpu_baseline(soa, args) -> dict:
@@ -271,6 +314,11 @@ def main() -> None:
     ap.add_argument("--n-sym", type=int, default=0, help="override the config's symbol count")
     ap.add_argument("--cpu-sample", type=int, default=40_000_000,
                     help="ops in the 1-thread CPU-baseline sample (rank 0, N=1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: per-stage breakdown, async / timers-off "
+                         "legs, PMC traffic, CPU baselines, drop-in legs (each can be skipped with --no-*)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 traffic passes")
     ap.add_argument("--no-e2e", action="store_true", help="skip the drop-in end-to-end leg")
@@ -283,6 +331,8 @@ def main() -> None:
     ap.add_argument("--independent", action="store_true",
                     help="N > 1: independent merges per rank instead of one sharded merge")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu_baseline = args.no_pmc = args.no_e2e = args.no_async = args.no_breakdown = True
 
     import torch
     from semantic_merge_amd import _lib, synth
@@ -371,6 +421,8 @@ def main() -> None:
     lib.smx_set_profiling(0)
     plan = _lib.DeviceCompose.last_plan()
     stages = _lib.stage_times()
+    if args.dump_outputs:  # what the last timed step left, before any other leg runs
+        dump_outputs(args.dump_outputs, sc if sharded else dc, rank, world)
     # per-stage breakdown (every stage timed), outside the timed region
     lib.smx_set_profiling_stages(0xFFFFFFFF)
     stages_all, n_breakdown = stages, args.steps
@@ -542,8 +594,10 @@ def main() -> None:
         "pmc": pmc,
         # per merge: each stage's summed time over its launches in one merge, and how many
         # times the merge entered it (breakdown leg: every stage timed, n_breakdown merges)
-        "stages_ms_per_step": {k2: round(v[0] / n_breakdown, 4) for k2, v in stages_all.items() if v[1]},
-        "stage_calls_per_step": {k2: round(v[1] / n_breakdown, 2) for k2, v in stages_all.items() if v[1]},
+        "stages_ms_per_step": {k2: round(v[0] / n_breakdown, 4) for k2, v in stages_all.items() if v[1]}
+        if args.full else None,
+        "stage_calls_per_step": {k2: round(v[1] / n_breakdown, 2) for k2, v in stages_all.items() if v[1]}
+        if args.full else None,
         "cpu_baseline": cpu,
         "end_to_end": e2e,
         "small_merge": small,

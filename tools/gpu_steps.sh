@@ -6,7 +6,7 @@
 #        smallph (phase stamps, tools/_build/var_stamps), gtests (the whole -m gpu suite),
 #        ab / ab5 (tools/ab_libs.py, current vs tools/_build/var_old, configs 3 / 5),
 #        rgabench (tools/bench_rga.py), rgaprof (its kernel trace and timeline), bench (bench.py,
-#        no PMC / CPU legs), benchfull (bench.py default), c5, c2 (bench.py configs), c2prof
+#        --full without the PMC / CPU legs), benchfull (bench.py --full), c5, c2 (bench.py configs), c2prof
 #        (config-2 kernel timeline), shard (sharded GPU tests + tools/shard_probe.py), prof
 #        (config-3 kernel stats), sq (tools/pmc_sq.sh)
 set -o pipefail
@@ -49,15 +49,15 @@ for s in "$@"; do
         tail -12 "$O/ab_c5.txt";;
     rgabench) run 300 bench_rga.json python -u tools/bench_rga.py
         tail -1 "$O/bench_rga.json";;
-    bench) run 300 bench.json python -u bench.py --no-cpu-baseline --no-pmc --no-e2e
+    bench) run 300 bench.json python -u bench.py --full --no-cpu-baseline --no-pmc --no-e2e
         tail -1 "$O/bench.json" | cut -c1-600;;
-    benchfull) run 600 bench_full.json python -u bench.py
+    benchfull) run 600 bench_full.json python -u bench.py --full
         tail -1 "$O/bench_full.json" | cut -c1-600;;
-    c5) run 300 bench_c5.json python -u bench.py --config c5 --steps 10 --no-cpu-baseline --no-e2e
+    c5) run 300 bench_c5.json python -u bench.py --full --config c5 --steps 10 --no-cpu-baseline --no-e2e
         tail -1 "$O/bench_c5.json" | cut -c1-600;;
-    c2) run 300 bench_c2.json python -u bench.py --config c2 --steps 50 --no-pmc --no-e2e
+    c2) run 300 bench_c2.json python -u bench.py --full --config c2 --steps 50 --no-pmc --no-e2e
         tail -1 "$O/bench_c2.json" | cut -c1-400;;
-    prof) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof" -o p -- python3 "$R/bench.py" --steps 8 --warmup 2 --no-cpu-baseline --no-pmc --no-e2e > "$O/prof.log" 2>&1) || { echo "prof failed"; tail -20 "$O/prof.log"; exit 1; }
+    prof) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof" -o p -- python3 "$R/bench.py" --full --steps 8 --warmup 2 --no-cpu-baseline --no-pmc --no-e2e > "$O/prof.log" 2>&1) || { echo "prof failed"; tail -20 "$O/prof.log"; exit 1; }
           python3 tools/prof_export.py "$O/prof" "$O/kernel_stats.csv" && head -8 "$O/kernel_stats.csv";;
     c3tl) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace -d "$O/c3tl" -o p -- python3 "$R/bench.py" --steps 4 --warmup 2 --no-cpu-baseline --no-pmc --no-e2e --no-breakdown --no-async > "$O/c3tl.log" 2>&1) || { echo "c3tl failed"; tail -20 "$O/c3tl.log"; exit 1; }
           python3 tools/prof_timeline.py "$O/c3tl" 60 > "$O/c3_timeline.txt" && tail -62 "$O/c3_timeline.txt";;
