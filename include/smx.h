@@ -38,7 +38,11 @@ extern "C" {
 
 #define SMX_OK 0
 #define SMX_E_ARG (-1)      /* bad argument / shape */
-#define SMX_E_CAPACITY (-2) /* an output buffer is too small; required size reported */
+/* More conflicts than smx_compose_out.conflict_cap.  No entry point of the library returns
+ * it: a merge is enqueued, not waited for, so the overflow shows in counts[1] (see
+ * smx_compose_out), and the code is kept for callers that turn that into an error (the
+ * Python wrapper's SmxError). */
+#define SMX_E_CAPACITY (-2)
 #define SMX_E_HIP (-3)      /* a HIP runtime call failed */
 #define SMX_E_WORKSPACE (-4) /* workspace too small */
 
@@ -73,9 +77,12 @@ typedef struct smx_ops {
   const int32_t* v0;
   const int32_t* v1;
   /* B op j (j >= n_a) is stored at index j + b_gap of every field array (0: right
-   * after A).  A sharded merge keeps headroom between its A and B ranges so its
-   * exchange moves only the ops that change shard; smx_compose's generic plan
-   * (logs not timestamp-ordered) needs b_gap = 0. */
+   * after A); the b_gap entries between the branches are not part of the merge.  A sharded merge
+   * keeps headroom between its A and B ranges so its exchange moves only the ops that
+   * change shard.  The presorted, presorted-wide and small plans take any b_gap >= 0;
+   * the sorting plans (segmented, radix) need b_gap = 0: with b_gap > 0, smx_compose
+   * returns SMX_E_ARG for branch logs that are not timestamp-ordered and for ordered
+   * logs whose equal-timestamp groups no presorted window holds. */
   int64_t b_gap;
 } smx_ops;
 
@@ -86,8 +93,13 @@ typedef struct smx_ops {
  *   file[k]       string id of the move-chain newFile it sees, or SMX_NONE
  *   ctx[k]        string id of its renameContext (non-renames), or SMX_NONE
  *   conflicts     (a_idx, b_idx) pairs in the reference's discovery order;
- *                 capacity conflict_cap pairs (min(n_a, n_b) always suffices)
+ *                 capacity conflict_cap pairs, >= 0 (min(n_a, n_b) always suffices)
  *   counts[0]     number of composed ops, counts[1] number of conflicts
+ * A conflict_cap smaller than the number of conflicts is not an error of the call (it
+ * returns SMX_OK): counts[1] is the full number of conflicts, the first conflict_cap pairs
+ * are written, nothing is written at or after conflicts[2 * conflict_cap], and the
+ * composed ops (order, addr, file, ctx, counts[0]) are complete.  The caller compares
+ * counts[1] with conflict_cap after synchronising the stream.
  */
 typedef struct smx_compose_out {
   int32_t* order;

@@ -89,41 +89,68 @@ def _hip_check(rc: int, what: str) -> None:
 
 
 class DeviceCompose:
-    """Device-resident inputs, outputs and workspace for repeated smx_compose calls."""
+    """Device-resident inputs, outputs and workspace for repeated smx_compose calls.
 
-    def __init__(self, soa: SoA, device: str = "cuda") -> None:
+    The optional arguments reach the corners of the C ABI (include/smx.h):
+    b_gap        branch B's columns start b_gap entries after branch A's (smx_ops.b_gap);
+                 the gap holds an invalid kind (0xFF) and symbol (0xFFFFFFFF), so a kernel
+                 that read it would report invalid input;
+    conflict_cap the capacity passed for the conflict pairs (default min(n_a, n_b), which
+                 always suffices); CONF_GUARD guard words follow the 2 * conflict_cap
+                 words (guard_intact());
+    ws_bytes     the workspace size passed (default: what smx_compose_workspace_bytes
+                 asks for; the buffer itself always has that size)."""
+
+    CONF_GUARD = 64
+    _GUARD_WORD = 0x5A5A5A5A
+
+    def __init__(self, soa: SoA, device: str = "cuda", b_gap: int = 0, conflict_cap: Optional[int] = None,
+                 ws_bytes: Optional[int] = None) -> None:
         torch = _torch()
         self.torch = torch
         self.soa = soa
         self.n = soa.n
         dev = torch.device(device)
         self.device = dev
+        na = soa.n_a
+        if b_gap < 0:
+            raise ValueError("b_gap must be >= 0")
 
-        def up(a, dt):
-            return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev, non_blocking=False)
+        def up(a, dt, fill=0):
+            a = np.ascontiguousarray(a)
+            if b_gap:
+                a = np.concatenate([a[:na], np.full(b_gap, fill, a.dtype), a[na:]])
+            return torch.from_numpy(a.view(dt)).to(dev, non_blocking=False)
 
-        self.kind = up(soa.kind, np.uint8)
+        self.kind = up(soa.kind, np.uint8, 0xFF)
         self.ts = up(soa.ts, np.int64)      # bit-identical u64 payload
         self.hi = up(soa.oid_hi, np.int64)
         self.lo = up(soa.oid_lo, np.int64)
-        self.sym = up(soa.sym, np.int32)
-        self.v0 = up(soa.v0, np.int32)
-        self.v1 = up(soa.v1, np.int32)
+        self.sym = up(soa.sym, np.int32, 0xFFFFFFFF)
+        self.v0 = up(soa.v0, np.int32, -1)
+        self.v1 = up(soa.v1, np.int32, -1)
         n = max(self.n, 1)
         self.order = torch.empty(n, dtype=torch.int32, device=dev)
         self.addr = torch.empty(n, dtype=torch.int32, device=dev)
         self.file = torch.empty(n, dtype=torch.int32, device=dev)
         self.ctx = torch.empty(n, dtype=torch.int32, device=dev)
-        self.cap = max(min(soa.n_a, soa.n_b), 1)
-        self.conf = torch.empty(2 * self.cap, dtype=torch.int32, device=dev)
+        if conflict_cap is None:
+            self.cap = max(min(soa.n_a, soa.n_b), 1)
+            self.conf = torch.empty(2 * self.cap, dtype=torch.int32, device=dev)
+        else:
+            self.cap = conflict_cap
+            self.conf = torch.full((2 * max(self.cap, 0) + self.CONF_GUARD,), self._GUARD_WORD,
+                                   dtype=torch.int32, device=dev)
+        self._guarded = conflict_cap is not None
         self.counts = torch.zeros(2, dtype=torch.int64, device=dev)
         ws = C.c_size_t(0)
         check(lib().smx_compose_workspace_bytes(soa.n_a, soa.n_b, soa.n_sym, C.byref(ws)))
-        self.ws_bytes = ws.value
+        self.ws_needed = ws.value
+        self.ws_bytes = ws.value if ws_bytes is None else ws_bytes
         self.ws = torch.empty(max(ws.value, 1), dtype=torch.uint8, device=dev)
         self._ops = _abi.SmxOps(soa.n_a, soa.n_b, soa.n_sym, _ptr(self.kind), _ptr(self.ts),
                                 _ptr(self.hi), _ptr(self.lo), _ptr(self.sym), _ptr(self.v0),
-                                _ptr(self.v1))
+                                _ptr(self.v1), b_gap)
         self._out = _abi.SmxComposeOut(_ptr(self.order), _ptr(self.addr), _ptr(self.file),
                                        _ptr(self.ctx), _ptr(self.conf), self.cap,
                                        _ptr(self.counts))
@@ -148,13 +175,26 @@ class DeviceCompose:
     def last_plan() -> str:
         return _abi.PLAN_NAMES[lib().smx_last_plan()]
 
-    def results(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    def guard_intact(self) -> bool:
+        """The CONF_GUARD words after the conflict pairs' capacity are as they were set
+        (a DeviceCompose built with conflict_cap)."""
+        if not self._guarded:
+            raise ValueError("no guard words: built without conflict_cap")
+        self.torch.cuda.synchronize(self.device)
+        return bool((self.conf[2 * max(self.cap, 0):] == self._GUARD_WORD).all().item())
+
+    def results(self, truncated: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The composed arrays and the conflict pairs.  More conflicts than conflict_cap
+        (include/smx.h: counts[1] > conflict_cap, only the first conflict_cap pairs
+        written) raise SmxError -2, or with truncated=True give those first pairs."""
         self.torch.cuda.synchronize(self.device)
         k, nc = (int(x) for x in self.counts.cpu().tolist())
         if k < 0:
             raise SmxError(-1, "invalid input: sym >= n_sym or kind >= 18")
         if nc > self.cap:
-            raise SmxError(-2, f"{nc} conflicts exceed capacity {self.cap}")
+            if not truncated:
+                raise SmxError(-2, f"{nc} conflicts exceed capacity {self.cap}")
+            nc = self.cap
         return (self.order[:k].cpu().numpy(), self.addr[:k].cpu().numpy(),
                 self.file[:k].cpu().numpy(), self.ctx[:k].cpu().numpy(),
                 self.conf[: 2 * nc].cpu().numpy().reshape(nc, 2))

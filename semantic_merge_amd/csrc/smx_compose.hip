@@ -2547,6 +2547,7 @@ static int check_args(const smx_ops* ops, const smx_compose_out* out, void* ws, 
     return set_err(SMX_E_ARG, "null input/output pointer");
   if (n_sym < 1) return set_err(SMX_E_ARG, "n_sym must be >= 1");
   if (ops->b_gap < 0) return set_err(SMX_E_ARG, "b_gap must be >= 0");
+  if (out->conflict_cap < 0) return set_err(SMX_E_ARG, "conflict_cap must be >= 0");
   *L = layout(na, nb, n_sym);
   if (!ws || ws_bytes < L->total)
     return set_err(SMX_E_WORKSPACE, "workspace too small: need " + std::to_string(L->total));
@@ -2608,7 +2609,10 @@ static int order_fallbacks(const Ctx& C, bool allow_generic, bool tail, ComposeM
   }
   if (hm->f_fail && !hm->bad_sym && allow_generic) {
     if (C.ops->b_gap != 0)
-      return set_err(SMX_E_ARG, "branch logs not timestamp-ordered: the generic plan needs b_gap = 0");
+      return set_err(SMX_E_ARG, hm->f_fail & 1
+                                    ? "branch logs not timestamp-ordered: the generic plan needs b_gap = 0"
+                                    : "timestamp groups too long for the presorted windows: the generic plan needs "
+                                      "b_gap = 0");
     if (require_ordered && (hm->f_fail & 1)) return unordered();
     if (!(hm->f_fail & 1)) {  // ordered, long groups: the segmented sort, tail behind it
       g_plan = SMX_PLAN_SEGMENTED;

@@ -39,3 +39,13 @@ def assert_case(backend, case, label=""):
     out, conf = run_backend(backend, case["A"], case["B"])
     assert jline(out) == jline(case["out"]), f"{label}: composed ops differ"
     assert jline(conf) == jline(case["conflicts"]), f"{label}: conflicts differ"
+
+
+def _eq_soa(gpu, ref, label):
+    """Both (order, addr, file, ctx, conflict pairs) tuples are equal, array by array."""
+    names = ("order", "addr", "file", "ctx", "conflicts")
+    for name, g, r in zip(names, gpu, ref):
+        assert g.shape == r.shape, f"{label}: {name} shape {g.shape} vs {r.shape}"
+        if not np.array_equal(g, r):
+            bad = np.flatnonzero(g.reshape(-1) != r.reshape(-1))[:5]
+            raise AssertionError(f"{label}: {name} differs at {bad.tolist()}")

@@ -10,18 +10,10 @@ from semantic_merge_amd._lib import DeviceCompose, compose_soa
 from semantic_merge_amd.compose import compose_oplogs
 from semantic_merge_amd.marshal import marshal
 
-from _util import assert_case, jline, load, to_ops
+from _shapes import alternating_groups as _alternating_groups
+from _util import _eq_soa, assert_case, jline, load, to_ops
 
 pytestmark = pytest.mark.gpu
-
-
-def _eq_soa(gpu, ref, label):
-    names = ("order", "addr", "file", "ctx", "conflicts")
-    for name, g, r in zip(names, gpu, ref):
-        assert g.shape == r.shape, f"{label}: {name} shape {g.shape} vs {r.shape}"
-        if not np.array_equal(g, r):
-            bad = np.flatnonzero(g.reshape(-1) != r.reshape(-1))[:5]
-            raise AssertionError(f"{label}: {name} differs at {bad.tolist()}")
 
 
 def test_library_runs_on_gpu():
@@ -167,18 +159,6 @@ def test_gpu_wide_plan_config5_shape():
     dc.run()
     _eq_soa(dc.results(), oracle.compose(soa), "config 5 shape, wide windows")
     assert dc.last_plan() == "presorted-wide"
-
-
-def _alternating_groups(spec, big, small):
-    """spec's logs with timestamp groups of alternately `big` and `small` ops per branch
-    (the same on both branches)."""
-    soa = synth.lift_soa(synth.lift_logs(spec))
-    for lo, m in ((0, soa.n_a), (soa.n_a, soa.n_b)):
-        period = big + small
-        k = np.arange(m)
-        grp = 2 * (k // period) + ((k % period) >= big)
-        soa.ts[lo:lo + m] = soa.ts[0] + grp.astype(np.uint64) * np.uint64(2)
-    return soa
 
 
 def test_gpu_segmented_plan_when_wide_windows_overflow():

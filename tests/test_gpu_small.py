@@ -8,7 +8,7 @@ from oracle import oracle
 from semantic_merge_amd import synth
 from semantic_merge_amd._lib import DeviceCompose, compose_soa, set_small_limit
 
-from _util import assert_case, load
+from _util import _eq_soa as _eq, assert_case, load
 
 pytestmark = pytest.mark.gpu
 
@@ -18,14 +18,6 @@ def plan(request):
     old = set_small_limit(2048 if request.param == "small" else 0)
     yield request.param
     set_small_limit(old)
-
-
-def _eq(gpu, ref, label):
-    for name, g, r in zip(("order", "addr", "file", "ctx", "conflicts"), gpu, ref):
-        assert g.shape == r.shape, f"{label}: {name} shape {g.shape} vs {r.shape}"
-        if not np.array_equal(g, r):
-            bad = np.flatnonzero(g.reshape(-1) != r.reshape(-1))[:5]
-            raise AssertionError(f"{label}: {name} differs at {bad.tolist()}")
 
 
 def test_golden_both_plans(plan):
