@@ -6,6 +6,8 @@
  *                    (sort_key/_precedence :16-21,130-149; merge loop :51-112;
  *                     DivergentRename check :60-70,88-98 with conflict.py:34-49;
  *                     rename/move chains :27-28,71-82,99-110; materialize :30-49)
+ *   smx_compose_batch <- the same loop for many independent merges of at most 2048 ops
+ *                    each, in one call (a merge queue, a rebase, a monorepo)
  *   smx_rga_replay <- semmerge/crdt.py:23-57  RGA.insert/move/delete/materialize,
  *                    batched over many independent lists
  *
@@ -14,7 +16,8 @@
  * caller-provided workspace sized by the *_workspace_bytes queries.  Calls are
  * stream-ordered on `stream` (a hipStream_t passed as void*; NULL = the null
  * stream).  smx_compose performs one stream synchronisation (in smx_compose_finish)
- * to check its plan; read device-side counts only after synchronising the stream.
+ * to check its plan; smx_compose_batch performs none; read device-side counts only after
+ * synchronising the stream.
  *
  * Reentrant: host threads may compose concurrently, each on its own stream and
  * workspace (the library's side stream and fork/join events are kept per caller
@@ -148,6 +151,51 @@ int smx_last_plan(void);
  * workgroup and one launch; 0 sends every merge through the window plans.  Process-wide;
  * returns the previous limit. */
 int64_t smx_set_small_limit(int64_t n);
+
+/*
+ * Batched compose: n_merges independent merges of at most 2048 ops each in one call (a
+ * merge queue, a rebase, a monorepo merged package by package).  The merges' columns lie
+ * one after another in shared arrays; a device pre-pass sorts the merges into size classes
+ * (256, 1024, 2048 ops) and one launch per class spreads them over the chip, several
+ * workgroups per CU for the small classes.  The call only enqueues on `stream`: no host
+ * synchronisation, no allocation, no read-back (read counts after synchronising).
+ *
+ * Per merge m the results equal smx_compose on that merge alone: counts[2m] composed ops
+ * in order/addr/file/ctx at off[m].., order[] local to the merge (0 .. len-1, A first);
+ * counts[2m+1] the full number of conflicts, of which the first
+ * conf_off[m+1] - conf_off[m] pairs are written at conflicts[2 * conf_off[m]] and nothing at
+ * or past the merge's conflict region.  String and symbol ids are opaque and local to a
+ * merge (every merge's symbols are < n_sym <= 2^32 - 1).
+ *
+ * Checked on the device, per merge, before any of its columns is read:
+ *   counts[2m] = counts[2m+1] = -1  off[m] < 0, off[m+1] < off[m] or > n_total, n_a[m]
+ *                                   outside [0, len], conf_off decreasing or negative; or
+ *                                   an op with kind >= 18 or sym >= n_sym
+ *   counts[2m] = counts[2m+1] = -2  len > 2048: send that merge through smx_compose
+ * A failed merge writes nothing else and does not affect its neighbours.
+ */
+typedef struct smx_batch {
+  int64_t n_merges, n_total, n_sym;      /* n_sym: bound for every merge's symbol ids */
+  const int64_t* off;                    /* device [n_merges+1]: merge m's ops are
+                                            [off[m], off[m+1]) of the columns, A first */
+  const int64_t* n_a;                    /* device [n_merges] */
+  const uint8_t* kind; const uint64_t* ts, *oid_hi, *oid_lo;
+  const uint32_t* sym; const int32_t* v0, *v1;     /* as smx_ops, n_total entries */
+  int32_t* order, *addr, *file, *ctx;    /* n_total entries; merge m's results at off[m]..,
+                                            order[] local to the merge (0 .. len-1) */
+  int32_t* conflicts; const int64_t* conf_off;  /* device [n_merges+1], in pairs: merge m's
+                                            capacity is conf_off[m+1]-conf_off[m] */
+  int64_t* counts;                       /* [2*n_merges]: composed ops, conflicts */
+  int32_t grid_cap;                      /* 0: library's choice; >0: at most this many
+                                            workgroups per class (tuning, tests) */
+} smx_batch;
+/* Workspace for a batch of n_merges (0 .. 2^31 - 1) merges. */
+int smx_compose_batch_workspace_bytes(int64_t n_merges, size_t* bytes);
+/* SMX_E_ARG (negative sizes, grid_cap < 0, n_sym > 2^32 - 1, a null pointer with
+ * n_merges > 0 -- the column and result arrays may be null only when n_total = 0) and
+ * SMX_E_WORKSPACE are reported before any HIP call; n_merges = 0 returns SMX_OK and
+ * launches nothing. */
+int smx_compose_batch(const smx_batch* b, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Sharded single merge: one process per GPU, shard r of G.

@@ -2,7 +2,7 @@
 from .ops import Op, Target  # noqa: F401
 from .conflict import Conflict  # noqa: F401
 
-__all__ = ["Op", "Target", "Conflict", "compose_oplogs"]
+__all__ = ["Op", "Target", "Conflict", "compose_oplogs", "compose_many"]
 
 
 def __getattr__(name):
@@ -10,4 +10,7 @@ def __getattr__(name):
     if name == "compose_oplogs":
         from .compose import compose_oplogs
         return compose_oplogs
+    if name == "compose_many":
+        from .compose import compose_many
+        return compose_many
     raise AttributeError(name)

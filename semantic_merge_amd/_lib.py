@@ -200,6 +200,89 @@ class DeviceCompose:
                 self.conf[: 2 * nc].cpu().numpy().reshape(nc, 2))
 
 
+class DeviceBatch:
+    """Device-resident inputs, outputs and workspace for repeated smx_compose_batch calls
+    on a list of merges (tests, tools/batch_probe.py).  The optional arguments reach the
+    corners of the C ABI (include/smx.h smx_batch):
+    conflict_caps per-merge capacities of the conflict pairs (default min(n_a, n_b));
+    grid_cap      smx_batch.grid_cap;
+    n_a           per-merge n_a passed instead of the SoAs' own;
+    n_sym         the batch's symbol bound (default: the largest of the merges');
+    n_total       smx_batch.n_total passed instead of the columns' real length;
+    fill          every output word (results, conflict pairs, counts) starts as this value,
+                  and CONF_GUARD such words follow the last merge's conflict region."""
+
+    CONF_GUARD = 64
+
+    def __init__(self, soas, device: str = "cuda", conflict_caps=None, grid_cap: int = 0, n_a=None,
+                 n_sym: Optional[int] = None, fill: Optional[int] = None, n_total: Optional[int] = None) -> None:
+        torch = _torch()
+        self.torch = torch
+        dev = self.device = torch.device(device)
+        soas = self.soas = list(soas)
+        M = self.n_merges = len(soas)
+        self.off = np.zeros(M + 1, np.int64)
+        np.cumsum([s.n for s in soas], out=self.off[1:])
+        tot = self.n_total = int(self.off[-1])
+        self.n_a = np.asarray([s.n_a for s in soas] if n_a is None else n_a, np.int64).reshape(M)
+        caps = [min(s.n_a, s.n_b) for s in soas] if conflict_caps is None else conflict_caps
+        self.conf_off = np.zeros(M + 1, np.int64)
+        np.cumsum(caps, out=self.conf_off[1:])
+        self.n_sym = max([int(s.n_sym) for s in soas] + [1]) if n_sym is None else n_sym
+
+        def up(a, dt=None):
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(a.view(dt) if dt is not None else a).to(dev)
+
+        def col(name, dt, view):
+            parts = [np.ascontiguousarray(getattr(s, name)).astype(dt, copy=False) for s in soas]
+            return up(np.concatenate(parts) if parts else np.zeros(0, dt), view)
+
+        self._in = [col("kind", np.uint8, None), col("ts", np.uint64, np.int64), col("oid_hi", np.uint64, np.int64),
+                    col("oid_lo", np.uint64, np.int64), col("sym", np.uint32, np.int32), col("v0", np.int32, None),
+                    col("v1", np.int32, None)]
+        self._idx = [up(self.off), up(self.n_a), up(self.conf_off)]
+        f = 0 if fill is None else fill
+        self.order, self.addr, self.file, self.ctx = (
+            torch.full((max(tot, 1),), f, dtype=torch.int32, device=dev) for _ in range(4))
+        self.conf = torch.full((2 * int(self.conf_off[-1]) + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        self.counts = torch.full((2 * max(M, 1),), f, dtype=torch.int64, device=dev)
+        ws = C.c_size_t(0)
+        check(lib().smx_compose_batch_workspace_bytes(M, C.byref(ws)))
+        self.ws_bytes = ws.value
+        self.ws = torch.empty(max(ws.value, 1), dtype=torch.uint8, device=dev)
+        self._b = _abi.SmxBatch(M, tot if n_total is None else n_total, self.n_sym, self._idx[0].data_ptr(), self._idx[1].data_ptr(),
+                                *[t.data_ptr() for t in self._in], self.order.data_ptr(), self.addr.data_ptr(),
+                                self.file.data_ptr(), self.ctx.data_ptr(), self.conf.data_ptr(),
+                                self._idx[2].data_ptr(), self.counts.data_ptr(), grid_cap)
+
+    def run(self, stream=None) -> None:
+        """Enqueue one smx_compose_batch on `stream` (default: torch's current stream)."""
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().smx_compose_batch(C.byref(self._b), self.ws.data_ptr(), self.ws_bytes, s.cuda_stream))
+
+    def raw(self) -> dict:
+        """Every output array as the device holds it (after a device sync), on the host."""
+        self.torch.cuda.synchronize(self.device)
+        return {k: getattr(self, k).cpu().numpy() for k in ("order", "addr", "file", "ctx", "conf", "counts")}
+
+    def results(self, raw: Optional[dict] = None):
+        """Per merge (order, addr, file, ctx, pairs) trimmed to its counts and its conflict
+        capacity, or its negative counts[2m] for a merge that failed."""
+        r = self.raw() if raw is None else raw
+        out = []
+        for m in range(self.n_merges):
+            k, nc = int(r["counts"][2 * m]), int(r["counts"][2 * m + 1])
+            if k < 0:
+                out.append(k)
+                continue
+            o, c = int(self.off[m]), int(self.conf_off[m])
+            nc = min(nc, int(self.conf_off[m + 1]) - c)
+            out.append(tuple(r[x][o: o + k] for x in ("order", "addr", "file", "ctx"))
+                       + (r["conf"][2 * c: 2 * (c + nc)].reshape(nc, 2),))
+        return out
+
+
 def _al(x: int) -> int:
     return (x + 255) & ~255
 
@@ -321,6 +404,117 @@ class ComposeSession:
         return res + (pairs,)
 
 
+    # -- batched compose (smx_compose_batch): many small merges, one launch sequence --------
+
+    def _batch_layout(self, ns):
+        """Byte offsets of a batch of merges of ns ops in the staging areas: the input
+        columns for sum(ns) ops, then off / n_a / conf_off; the four outputs, the conflict
+        pairs (at most sum(ns) / 2) and the counts."""
+        m, tot = len(ns), int(sum(ns))
+        lay, o = {"n_total": tot}, 0
+        for name, w in self._IN:
+            lay[name] = o
+            o += _al(tot * w)
+        for name, cnt in (("off", m + 1), ("n_a", m), ("conf_off", m + 1)):
+            lay[name] = o
+            o += _al(cnt * 8)
+        lay["in_bytes"] = o
+        q = _al(tot * 4)
+        lay["q"], lay["conf"], lay["counts"] = q, 4 * q, 4 * q + _al(4 * tot + 8)
+        lay["out_bytes"] = lay["counts"] + 16 * m
+        return lay
+
+    def _ensure_batch(self, lay, ws_bytes: int) -> None:
+        # (_ensure sizes the areas per op: 37 input bytes and 20 output bytes each at least)
+        self._ensure(max(-(-lay["in_bytes"] // 37), -(-lay["out_bytes"] // 20)), ws_bytes)
+
+    def staging_many(self, ns):
+        """The input columns of a batch of merges of ns ops (each at most BATCH_MAX_OPS) as
+        views of the pinned staging area, one dict per merge, laid out as compose_many()
+        copies them: SoAs marshalled into them are not packed again."""
+        lay = self._batch_layout(ns)
+        self._ensure_batch(lay, 0)
+        hin = self.h_in.numpy()
+        offs = np.concatenate([[0], np.cumsum(ns, dtype=np.int64)]) if len(ns) else np.zeros(1, np.int64)
+        return [{name: hin[lay[name] + int(offs[m]) * w: lay[name] + int(offs[m + 1]) * w].view(self._DT[name])
+                 for name, w in self._IN} for m in range(len(ns))]
+
+    def compose_many(self, soas, copy: bool = True):
+        """[(order, addr, file, ctx, conflict_pairs)] of independent merges, in input order.
+        The merges of at most BATCH_MAX_OPS ops are packed at consecutive offsets of the
+        staging area and run as one batch: one host-to-device copy, one smx_compose_batch,
+        one copy back, one stream sync.  Larger merges (and any the library sends back,
+        counts -2) go through compose() afterwards.  An invalid merge raises SmxError naming
+        its index.  copy=False: views of the staging area, valid until the session's next
+        merge (taken only when no merge is routed through compose())."""
+        soas = list(soas)
+        small = [i for i, s in enumerate(soas) if s.n <= _abi.BATCH_MAX_OPS]
+        routed = [i for i, s in enumerate(soas) if s.n > _abi.BATCH_MAX_OPS]
+        res = [None] * len(soas)
+        if small:
+            M = len(small)
+            ns = [soas[i].n for i in small]
+            lay = self._batch_layout(ns)
+            ws = C.c_size_t(0)
+            check(lib().smx_compose_batch_workspace_bytes(M, C.byref(ws)))
+            self._ensure_batch(lay, ws.value)
+            hin, hout = self.h_in.numpy(), self.h_out.numpy()
+            h0 = hin.ctypes.data
+            off = np.zeros(M + 1, np.int64)
+            np.cumsum(ns, out=off[1:])
+            n_a = np.fromiter((soas[i].n_a for i in small), np.int64, M)
+            conf_off = np.zeros(M + 1, np.int64)
+            np.cumsum(np.minimum(n_a, off[1:] - off[:-1] - n_a), out=conf_off[1:])  # min(n_a, n_b): never truncates
+            n_sym = 1
+            for m, i in enumerate(small):
+                soa, n = soas[i], ns[m]
+                n_sym = max(n_sym, int(soa.n_sym))
+                if n and int(np.max(soa.sym)) >= soa.n_sym:  # (the batch has one bound for all its merges)
+                    raise SmxError(-1, f"merge {i}: invalid input: sym >= n_sym")
+                for name, w in self._IN:
+                    col, at = getattr(soa, name), lay[name] + int(off[m]) * w
+                    if not (isinstance(col, np.ndarray) and col.ctypes.data == h0 + at and col.nbytes == n * w):
+                        hin[at: at + n * w] = np.ascontiguousarray(col).view(np.uint8).reshape(-1)
+            for name, arr in (("off", off), ("n_a", n_a), ("conf_off", conf_off)):
+                hin[lay[name]: lay[name] + arr.nbytes] = arr.view(np.uint8)
+            hip = _hiprt()
+            st = self.stream.cuda_stream
+            d0, o0 = self.d_in.data_ptr(), self.d_out.data_ptr()
+            _hip_check(hip.hipMemcpyAsync(d0, self.h_in.data_ptr(), lay["in_bytes"], 1, st), "hipMemcpyAsync (inputs)")
+            q = lay["q"]
+            b = _abi.SmxBatch(M, lay["n_total"], n_sym, d0 + lay["off"], d0 + lay["n_a"],
+                              *[d0 + lay[name] for name, _ in self._IN],
+                              o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"], d0 + lay["conf_off"],
+                              o0 + lay["counts"], 0)
+            check(lib().smx_compose_batch(C.byref(b), self.ws.data_ptr(), ws.value, st))
+            _hip_check(hip.hipMemcpyAsync(self.h_out.data_ptr(), o0, lay["out_bytes"], 2, st), "hipMemcpyAsync (outputs)")
+            _hip_check(hip.hipStreamSynchronize(st), "hipStreamSynchronize")
+            counts = hout[lay["counts"]: lay["counts"] + 16 * M].view(np.int64)
+            keep = copy or bool(routed)
+            for m, i in enumerate(small):
+                k, nc = int(counts[2 * m]), int(counts[2 * m + 1])
+                if k == -2:
+                    routed.append(i)
+                    keep = True
+                    continue
+                if k < 0:
+                    raise SmxError(-1, f"merge {i}: invalid input: sym >= n_sym or kind >= 18")
+                if nc > conf_off[m + 1] - conf_off[m]:
+                    raise SmxError(-2, f"merge {i}: {nc} conflicts exceed capacity {conf_off[m + 1] - conf_off[m]}")
+                o = 4 * int(off[m])
+                c = lay["conf"] + 8 * int(conf_off[m])
+                res[i] = tuple(hout[j * q + o: j * q + o + 4 * k].view(np.int32) for j in range(4)) + (
+                    hout[c: c + 8 * nc].view(np.int32).reshape(nc, 2),)
+            if keep:  # (compose() below reuses the staging area)
+                res = [r if r is None else tuple(x.copy() for x in r) for r in res]
+        for i in sorted(routed):
+            try:
+                res[i] = self.compose(soas[i])
+            except SmxError as e:
+                raise SmxError(e.code, f"merge {i}: {e}") from None
+        return res
+
+
 _sessions = {}
 
 
@@ -359,6 +553,14 @@ def compose_soa(soa: SoA, device: str = "cuda"):
     merge of this thread holds that session)."""
     s = session(device)
     return (s if not s.busy else ComposeSession(device)).compose(soa)
+
+
+def compose_soa_many(soas, device: str = "cuda"):
+    """[(order, addr, file, ctx, conflict_pairs)] of independent merges in one batch
+    (ComposeSession.compose_many on the thread's session, or on buffers of its own while a
+    drop-in merge of this thread holds that session)."""
+    s = session(device)
+    return (s if not s.busy else ComposeSession(device)).compose_many(soas)
 
 
 def set_small_limit(n: int) -> int:

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 from typing import Any, List, Sequence, Tuple
 
+from ._abi import BATCH_MAX_OPS
 from ._lib import dropin_session
 from .marshal import marshal_native
 from .materialize import materialize_conflicts, materialize_ops_native
@@ -33,3 +34,26 @@ def compose_oplogs(delta_a: Sequence[Any], delta_b: Sequence[Any]) -> Tuple[List
         out = materialize_ops_native(ops, soa.kind, soa.strings, order, addr, file, ctx)
         conflicts = materialize_conflicts(ops, pairs)
     return out, conflicts
+
+
+def compose_many(pairs: Sequence[Tuple[Sequence[Any], Sequence[Any]]]) -> List[Tuple[List[Any], List[Any]]]:
+    """``[compose_oplogs(a, b) for a, b in pairs]`` with the merges of at most 2048 ops run
+    as one GPU batch (one copy in, one smx_compose_batch, one copy back, one sync); larger
+    merges take ``compose_oplogs`` one by one.  Inputs are never mutated."""
+    logs = [(list(a), list(b)) for a, b in pairs]
+    res: List[Any] = [None] * len(logs)
+    small = [i for i, (a, b) in enumerate(logs) if len(a) + len(b) <= BATCH_MAX_OPS]
+    if small:
+        with dropin_session() as sess:
+            # each merge marshalled straight into its slice of the pinned staging columns;
+            # the results are views of the staging area, materialised while the session is held
+            cols = sess.staging_many([len(logs[i][0]) + len(logs[i][1]) for i in small])
+            soas = [marshal_native(logs[i][0], logs[i][1], c) for i, c in zip(small, cols)]
+            for i, soa, (order, addr, file, ctx, cpairs) in zip(small, soas, sess.compose_many(soas, copy=False)):
+                ops = logs[i][0] + logs[i][1]
+                res[i] = (materialize_ops_native(ops, soa.kind, soa.strings, order, addr, file, ctx),
+                          materialize_conflicts(ops, cpairs))
+    for i, (a, b) in enumerate(logs):
+        if res[i] is None:
+            res[i] = compose_oplogs(a, b)
+    return res

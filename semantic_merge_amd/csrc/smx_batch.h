@@ -1,0 +1,67 @@
+// smx_batch.h — many independent small merges in one call (smx_compose_batch).
+//
+// A merge of at most SMALL_N ops is one workgroup's work (smx_small.h), so a caller with
+// many of them -- a merge queue, a rebase, a monorepo merged package by package -- wants
+// them spread over the chip, not one launch, two copies and a sync each to keep one CU
+// busy.  Here a pre-pass sorts the merges into size classes and one launch per class
+// runs them: compose_small<N> at N = 256, 1024 and 2048 ops, N / 2 threads and ~64 N
+// bytes of LDS per workgroup, so that a batch of 100-op merges puts several workgroups on
+// each CU where the 2048-op instance alone fills it (DESIGN.md §11 has the resource table).
+//
+//   k_batch_classify  one workgroup reads every merge's bounds, checks them before any
+//                     column is touched, and appends the merge to its class's list in
+//                     the workspace (or fails it: counts -1 for bad bounds, -2 for a merge
+//                     over SMALL_N ops, which the caller sends through smx_compose)
+//   k_compose_batch<N> a grid capped by the class's residency; workgroup b runs the merges
+//                     b, b + grid, ... of the class list one after another, a barrier
+//                     between two (compose_small sets up all its LDS state per merge)
+// Nothing here waits, allocates or reads back: three or four launches on the caller's stream.
+#pragma once
+
+#include "smx_small.h"
+
+#define BATCH_CLASSES 3
+#define BATCH_HDR 256  // workspace: class counts (u32), then the class lists [BATCH_CLASSES][n_merges] (u32)
+__host__ __device__ constexpr int batch_class_cap(int c) { return c == 0 ? 256 : c == 1 ? 1024 : SMALL_N; }
+static_assert(batch_class_cap(BATCH_CLASSES - 1) == SMALL_N, "the last class holds every small merge");
+
+static inline size_t batch_list_bytes(int64_t n_merges) { return ((size_t)n_merges * 4 + 255) & ~(size_t)255; }
+
+__global__ void __launch_bounds__(256) k_batch_classify(smx_batch b, u32* cnt, u32* lists, size_t list_stride) {
+  __shared__ u32 c[BATCH_CLASSES];
+  const int t = threadIdx.x;
+  if (t < BATCH_CLASSES) c[t] = 0;
+  __syncthreads();
+  for (i64 m = t; m < b.n_merges; m += 256) {
+    const i64 o0 = b.off[m], o1 = b.off[m + 1], na = b.n_a[m], c0 = b.conf_off[m], c1 = b.conf_off[m + 1];
+    const i64 len = o1 - o0;
+    i64 fail = 0;
+    if (o0 < 0 || o1 < o0 || o1 > b.n_total || na < 0 || na > len || c0 < 0 || c1 < c0) fail = -1;
+    else if (len > SMALL_N) fail = -2;
+    if (fail) {
+      b.counts[2 * m] = fail;
+      b.counts[2 * m + 1] = fail;
+      continue;
+    }
+    int k = 0;
+    while (len > batch_class_cap(k)) ++k;
+    lists[(size_t)k * list_stride + atomicAdd(&c[k], 1u)] = (u32)m;
+  }
+  __syncthreads();
+  if (t < BATCH_CLASSES) cnt[t] = c[t];
+}
+
+template <int N>
+__global__ void __launch_bounds__(N / 2) k_compose_batch(smx_batch b, const u32* cnt, const u32* list) {
+  const u32 c = *cnt;
+  for (u32 i = blockIdx.x; i < c; i += gridDim.x) {
+    const i64 m = (i64)list[i];
+    const i64 o = b.off[m], len = b.off[m + 1] - o, na = b.n_a[m], co = b.conf_off[m];
+    const smx_ops ops{na, len - na, b.n_sym, b.kind + o, b.ts + o, b.oid_hi + o, b.oid_lo + o, b.sym + o, b.v0 + o,
+                      b.v1 + o, 0};
+    const smx_compose_out out{b.order + o, b.addr + o, b.file + o, b.ctx + o, b.conflicts + 2 * co,
+                              b.conf_off[m + 1] - co, b.counts + 2 * m};
+    compose_small<N, false>(ops, out, nullptr, nullptr, 0);
+    __syncthreads();  // the next merge's load overwrites what this one's last phase reads
+  }
+}

@@ -29,9 +29,8 @@
 
 #include "smx_common.h"
 
-#define SMALL_N 2048  // ops per merge
-#define SMALL_NT 1024
-#define SMALL_HT 4096  // hash slots (symbols), a power of two >= 2 * SMALL_N
+#define SMALL_N 2048  // ops per merge (the largest instance: smx_compose's, and a batch's last class)
+#define SMALL_NT (SMALL_N / 2)
 #define SMALL_EMPTY 0xffffffffu
 #define SMALL_BKT 32  // largest interpolation bucket ranked by counting (larger: bitonic sort)
 
@@ -47,47 +46,63 @@ __device__ u64 g_small_stamp[16];
   } while (0)
 #endif
 
-__global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_compose_out out, ComposeMeta* meta,
-                                                                u64* hrec, u64 hseq) {
-  constexpr int IT = SMALL_N / SMALL_NT;
-  constexpr int NW = SMALL_NT / WAVE;
+constexpr int small_log2(int x) { return x <= 1 ? 0 : 1 + small_log2(x >> 1); }
+
+// One merge of at most N ops (a power of two, 128..SMALL_N) by the N / 2 threads of the
+// calling workgroup: two ops per thread, which the stable split by kind (1d) assumes.
+// SINGLE: smx_compose's call, which also fills the meta block and the verdict word; a
+// batch (smx_batch.h) calls it merge after merge with a barrier between two merges: every
+// piece of LDS state is set up again inside the call.  Invalid input writes counts -1 and
+// nothing else.
+template <int N, bool SINGLE>
+__device__ __forceinline__ void compose_small(const smx_ops& ops, const smx_compose_out& out, ComposeMeta* meta,
+                                              u64* hrec, u64 hseq) {
+  constexpr int NT = N / 2;
+  constexpr int HT = 2 * N;               // hash slots (symbols), a power of two >= 2 * N
+  constexpr int HT_BITS = small_log2(HT);
+  constexpr int IT = N / NT;
+  constexpr int NW = NT / WAVE;
+  static_assert(N >= 2 * WAVE && N <= SMALL_N && (N & (N - 1)) == 0, "merge capacity");
+  static_assert((1 << HT_BITS) == HT && N <= 0x10000 / 2, "T + 1 and the slots' writers in 16 bits");
   // keys of the sort (dead after it: the hash table takes their place)
-  __shared__ __attribute__((aligned(16))) u64 keys[3][SMALL_N];
+  __shared__ __attribute__((aligned(16))) u64 keys[3][N];
   u64* kts = keys[0];
   u64* khi = keys[1];
   u64* klo = keys[2];
-  __shared__ u8 skd[SMALL_N];     // kind by element
-  __shared__ u16 ord[SMALL_N];    // T -> element
-  __shared__ u16 mrg[SMALL_N];    // ordered logs: (ts, id, index) order -> element
-  __shared__ u32 ssym[SMALL_N];   // by element
-  __shared__ i32 sv0[SMALL_N], sv1[SMALL_N];
-  __shared__ u8 skip[SMALL_N];    // by T: a rename the walk skipped
-  __shared__ u16 rat[SMALL_N + 1];  // rename block: A's renames before T (1a, 1b: run ends)
-  __shared__ u16 posA[SMALL_N], posB[SMALL_N];  // the i-th rename of a side: its T
-  __shared__ u64 sn[SMALL_N];                   // rename block, by T: symbol << 32 | newName
+  __shared__ u8 skd[N];     // kind by element
+  __shared__ u16 ord[N];    // T -> element
+  __shared__ u16 mrg[N];    // ordered logs: (ts, id, index) order -> element
+  __shared__ u32 ssym[N];   // by element
+  __shared__ i32 sv0[N], sv1[N];
+  __shared__ u8 skip[N];    // by T: a rename the walk skipped
+  __shared__ u16 rat[N + 1];  // rename block: A's renames before T (1a, 1b: run ends)
+  __shared__ u16 posA[N], posB[N];  // the i-th rename of a side: its T
+  __shared__ u64 sn[N];                   // rename block, by T: symbol << 32 | newName
                                                 // (1b: bucket counts and fill)
-  __shared__ u32 nxtA[SMALL_N + 1], nxtB[SMALL_N + 1];  // next rename of a side at or after T
+  __shared__ u32 nxtA[N + 1], nxtB[N + 1];  // next rename of a side at or after T
   __shared__ u32 wcnt[SMX_N_KINDS * NW];          // per (kind, wave): ops, then their start
   __shared__ u32 sscan[NW + 1];
   __shared__ u32 sinfo[8];  // [2] nmv, [3] rend
-  u32* hkey = reinterpret_cast<u32*>(keys[0]);              // [SMALL_HT] symbol of the slot
-  u16* hw = reinterpret_cast<u16*>(keys[1]);                 // [3][SMALL_HT]: T + 1 of the last
+  u32* hkey = reinterpret_cast<u32*>(keys[0]);              // [HT] symbol of the slot
+  u16* hw = reinterpret_cast<u16*>(keys[1]);                 // [3][HT]: T + 1 of the last
                                                              // addr / file writer and of the
                                                              // last kept rename (0: none)
-  static_assert(SMALL_HT * 4 <= SMALL_N * 8 && 3 * SMALL_HT * 2 <= 2 * SMALL_N * 8, "hash table in the keys");
+  static_assert(HT * 4 <= N * 8 && 3 * HT * 2 <= 2 * N * 8, "hash table in the keys");
   static_assert(SMX_N_KINDS * NW <= 5 * WAVE, "kind scan: 5 counters per lane");
-  static_assert(sizeof(ComposeMeta) % 4 == 0 && sizeof(ComposeMeta) / 4 <= SMALL_NT, "meta zeroed one word per thread");
+  static_assert(!SINGLE || (sizeof(ComposeMeta) % 4 == 0 && sizeof(ComposeMeta) / 4 <= NT),
+                "meta zeroed one word per thread");
   const int t = threadIdx.x, lane = t & (WAVE - 1), w = t / WAVE;
   const i64 na = ops.n_a, nb = ops.n_b;
   const int n = (int)(na + nb);
   if (t < 8) sinfo[t] = 0;
-  if (t < (int)(sizeof(ComposeMeta) / 4)) reinterpret_cast<u32*>(meta)[t] = 0u;
+  if constexpr (SINGLE)
+    if (t < (int)(sizeof(ComposeMeta) / 4)) reinterpret_cast<u32*>(meta)[t] = 0u;
   SMALL_STAMP(0);
   // 1. load (B op j is stored at j + b_gap)
   u32 bad = 0;
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
-    const int e = t + SMALL_NT * i;
+    const int e = t + NT * i;
     if (e < n) {
       const i64 j = e < na ? (i64)e : (i64)e + ops.b_gap;
       const u32 k = ops.kind[j], s = ops.sym[j];
@@ -102,11 +117,11 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
     }
     skip[e] = 0;
     reinterpret_cast<u32*>(sn)[e] = 0u;  // (1b's bucket counts and fill)
-    reinterpret_cast<u32*>(sn)[SMALL_N + e] = 0u;
+    reinterpret_cast<u32*>(sn)[N + e] = 0u;
   }
   if (__syncthreads_or(bad)) {  // invalid input: the call fails (as the large path: counts -1)
     if (t == 0) {
-      meta->bad_sym = 1;
+      if constexpr (SINGLE) meta->bad_sym = 1;
       out.counts[0] = -1;
       out.counts[1] = -1;
       if (hrec) *hrec = hseq << 1 | 1u;  // the verdict word (smx_compose's synchronous call)
@@ -152,8 +167,8 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
     //     binary search); inside it, interpolation buckets on the top 32 id bits (one op per
     //     bucket on random ids; counts in LDS, one scan), then each op ranks itself on
     //     (id, index) among its bucket's ops.  Ties: A before B = the lower index.
-    u32* bcnt = reinterpret_cast<u32*>(sn);  // [SMALL_N] bucket counts, then starts
-    u32* bfill = bcnt + SMALL_N;             // [SMALL_N] bucket fill
+    u32* bcnt = reinterpret_cast<u32*>(sn);  // [N] bucket counts, then starts
+    u32* bfill = bcnt + N;             // [N] bucket fill
     u32 bk[IT];
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
@@ -197,7 +212,7 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
     for (int i = 0; i < IT; ++i) {
       const int e = t * IT + i;
       if (e >= n) continue;
-      const u32 b = bk[i], b0 = bcnt[b], b1 = b + 1 < (u32)SMALL_N ? bcnt[b + 1] : (u32)n;
+      const u32 b = bk[i], b0 = bcnt[b], b1 = b + 1 < (u32)N ? bcnt[b + 1] : (u32)n;
       ord[b0 + atomicAdd(&bfill[b], 1u)] = (u16)e;
       big |= b1 - b0 > SMALL_BKT;
     }
@@ -207,7 +222,7 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
       for (int i = 0; i < IT; ++i) {
         const int e = t * IT + i;
         if (e >= n) continue;
-        const u32 b = bk[i], b0 = bcnt[b], b1 = b + 1 < (u32)SMALL_N ? bcnt[b + 1] : (u32)n;
+        const u32 b = bk[i], b0 = bcnt[b], b1 = b + 1 < (u32)N ? bcnt[b + 1] : (u32)n;
         const u64 h = khi[e], l = klo[e];
         u32 r = 0;
         for (u32 q = b0; q < b1; ++q) {
@@ -270,7 +285,7 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
       return x < y;  // (side, index): A before B, then the branch index
     };
 #pragma unroll
-    for (int i = 0; i < IT; ++i) ord[t + SMALL_NT * i] = (u16)(t + SMALL_NT * i);
+    for (int i = 0; i < IT; ++i) ord[t + NT * i] = (u16)(t + NT * i);
     __syncthreads();
     int P = 1;
     while (P < n) P <<= 1;
@@ -278,7 +293,7 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
       for (int jj = k >> 1; jj > 0; jj >>= 1) {
 #pragma unroll
         for (int i = 0; i < IT; ++i) {
-          const int a = t + SMALL_NT * i;
+          const int a = t + NT * i;
           const int b = a ^ jj;
           if (a < P && b > a) {
             const u32 x = ord[a], y = ord[b];
@@ -422,23 +437,25 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
     if (lane == 0) {
       out.counts[0] = (i64)(n - 2 * (int)nc);
       out.counts[1] = (i64)nc;
-      meta->n_conf = nc;
-      meta->n_skip = 2 * nc;
+      if constexpr (SINGLE) {
+        meta->n_conf = nc;
+        meta->n_skip = 2 * nc;
+      }
       if (hrec) *hrec = hseq << 1;  // read after the stream wait: the kernel's end publishes it
     }
     SMALL_STAMP(6);
   }
   // the keys are dead: the hash table takes their LDS
-  for (int i = t; i < SMALL_HT; i += SMALL_NT) {
+  for (int i = t; i < HT; i += NT) {
     hkey[i] = SMALL_EMPTY;
-    hw[i] = hw[SMALL_HT + i] = hw[2 * SMALL_HT + i] = 0;
+    hw[i] = hw[HT + i] = hw[2 * HT + i] = 0;
   }
   __syncthreads();
   SMALL_STAMP(7);
   // 3. the chains: every op's symbol slot (moves and renames insert, the rest look up)
   auto slot_of = [&](u32 s, bool ins) -> int {
-    u32 h = (s * 2654435761u) >> (32 - 12);
-    for (int probe = 0; probe < SMALL_HT; ++probe, h = (h + 1) & (SMALL_HT - 1)) {
+    u32 h = (s * 2654435761u) >> (32 - HT_BITS);
+    for (int probe = 0; probe < HT; ++probe, h = (h + 1) & (HT - 1)) {
       const u32 cur = hkey[h];
       if (cur == s) return (int)h;
       if (cur == SMALL_EMPTY) {
@@ -447,19 +464,19 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
         if (old == SMALL_EMPTY || old == s) return (int)h;
       }
     }
-    return -1;  // (unreachable: at most SMALL_N symbols in SMALL_HT slots)
+    return -1;  // (unreachable: at most N symbols in HT slots)
   };
   int slot_r[IT];
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
-    const int T = t + SMALL_NT * i;
+    const int T = t + NT * i;
     slot_r[i] = -1;
     if (T >= rend) continue;
     slot_r[i] = slot_of(ssym[ord[T]], true);
   }
   __syncthreads();
   SMALL_STAMP(8);
-  // last writers: T + 1 packed in u16 (T < SMALL_N); an atomic max on a u16 is emulated
+  // last writers: T + 1 packed in u16 (T < N); an atomic max on a u16 is emulated
   // with a CAS loop on its 32-bit word
   auto max16 = [&](u16* base, int h, u32 v) {
     u32* wd = reinterpret_cast<u32*>(base) + (h >> 1);
@@ -474,14 +491,14 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
   };
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
-    const int T = t + SMALL_NT * i;
+    const int T = t + NT * i;
     if (slot_r[i] < 0) continue;
     const u32 e = ord[T];
     if (T < nmv) {
       if (sv0[e] >= 0) max16(hw, slot_r[i], (u32)T + 1u);
-      if (sv1[e] >= 0) max16(hw + SMALL_HT, slot_r[i], (u32)T + 1u);
+      if (sv1[e] >= 0) max16(hw + HT, slot_r[i], (u32)T + 1u);
     } else if (!skip[T]) {  // a kept rename (compose.py:71-72)
-      max16(hw + 2 * SMALL_HT, slot_r[i], (u32)T + 1u);
+      max16(hw + 2 * HT, slot_r[i], (u32)T + 1u);
     }
   }
   // The moves' inclusive prefixes (compose.py:73-82), only when a move has a None value:
@@ -492,17 +509,17 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
   u16* pwa = posA;  // by T: T' + 1 of the move's prefix addr / file writer (0: none);
   u16* pwf = posB;  // (posA / posB are dead after the walk)
   u16* la = reinterpret_cast<u16*>(sn);  // by slot: the running writers (sn is dead after
-  u16* lf = la + SMALL_HT;               // the walk; klo is not: hw's third table lies in it)
-  static_assert(2 * SMALL_HT * 2 <= SMALL_N * 8, "running writers in sn");
+  u16* lf = la + HT;               // the walk; klo is not: hw's third table lies in it)
+  static_assert(2 * HT * 2 <= N * 8, "running writers in sn");
   bool none_here = false;
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
-    const int T = t + SMALL_NT * i;
+    const int T = t + NT * i;
     if (T < nmv) none_here |= (sv0[ord[T]] < 0) | (sv1[ord[T]] < 0);
   }
   const bool any_none = __syncthreads_or(none_here);  // (also orders the last-writer maxes)
   if (any_none) {
-    for (int i = t; i < SMALL_HT; i += SMALL_NT) la[i] = lf[i] = 0;
+    for (int i = t; i < HT; i += NT) la[i] = lf[i] = 0;
     __syncthreads();
     if (w == 0) {
       const u64 lt = lanemask_lt();
@@ -512,7 +529,7 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
         const u32 e = v ? ord[T] : 0u;
         const int h = v ? slot_of(ssym[e], false) : 0;  // (every move inserted its slot)
         const bool ha = v && sv0[e] >= 0, hf = v && sv1[e] >= 0;
-        const u64 peers = wave_peers_n((u32)h, v, 12);
+        const u64 peers = wave_peers_n((u32)h, v, HT_BITS);
         const u64 pa = __ballot(ha) & peers, pf = __ballot(hf) & peers;
         const u32 ra = v ? la[h] : 0u, rf = v ? lf[h] : 0u;  // (read before the step's updates)
         if (v) {
@@ -559,7 +576,7 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
     } else {
       const int h = slot_of(s, false);
       if (h >= 0) {
-        const u32 wa = hw[h], wf = hw[SMALL_HT + h], wr = hw[2 * SMALL_HT + h];
+        const u32 wa = hw[h], wf = hw[HT + h], wr = hw[2 * HT + h];
         if (wa) a = sv0[ord[wa - 1]];
         if (wf) f = sv1[ord[wf - 1]];
         if (k != SMX_KIND_RENAME && wr) c = sv1[ord[wr - 1]];  // renameContext: non-renames only
@@ -575,4 +592,10 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
   __syncthreads();
   SMALL_STAMP(10);
 #endif
+}
+
+// smx_compose's one-workgroup plan: the SMALL_N instance
+__global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_compose_out out, ComposeMeta* meta,
+                                                                u64* hrec, u64 hseq) {
+  compose_small<SMALL_N, true>(ops, out, meta, hrec, hseq);
 }
