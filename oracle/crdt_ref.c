@@ -6,6 +6,7 @@
  *   move              crdt.py:33-38  (pop the first live element with the value, then insert)
  *   delete            crdt.py:40-43  (tombstone every element with the value)
  *   materialize       crdt.py:45-46
+ *   list              crdt.py:26-27  (out_tomb non-NULL: every element, tombstoned ones flagged)
  *   _find_insert_index crdt.py:48-57 (tuple compare of (anchor, t, author, opid))
  * on the SoA of include/smx.h (host pointers).  O(n^2) per list, like the reference.
  */
@@ -85,9 +86,10 @@ int smx_oracle_rga(const smx_rga_ops* o, const smx_rga_out* out) {
       }
     }
     for (int64_t q = 0; q < m; ++q) {
-      if (buf[q].tomb) continue;
+      if (buf[q].tomb && !out->out_tomb) continue;
       out->out_value[k] = buf[q].value;
       out->out_src[k] = buf[q].src;
+      if (out->out_tomb) out->out_tomb[k] = (uint8_t)buf[q].tomb;
       ++k;
     }
   }

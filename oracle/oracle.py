@@ -65,8 +65,10 @@ def compose(soa: SoA) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, n
     return order[:k], addr[:k], file[:k], ctx[:k], conf[: 2 * nc].reshape(nc, 2)
 
 
-def rga(n_lists: int, list_id, op, value, anchor, t, author, opid_hi, opid_lo):
-    """Sequential RGA replay; returns (values, src, offsets)."""
+def rga(n_lists: int, list_id, op, value, anchor, t, author, opid_hi, opid_lo, tombstones: bool = False):
+    """Sequential RGA replay; returns (values, src, offsets) of materialize().  With
+    tombstones=True the whole list state (crdt.py RGA.list: live and tombstoned elements
+    in list order) and a fourth array, the tombstone flags."""
     arrs = [np.ascontiguousarray(a, dtype=d) for a, d in (
         (list_id, np.uint32), (op, np.uint8), (value, np.uint32), (anchor, np.uint32),
         (t, np.int64), (author, np.uint32), (opid_hi, np.uint64), (opid_lo, np.uint64))]
@@ -76,9 +78,12 @@ def rga(n_lists: int, list_id, op, value, anchor, t, author, opid_hi, opid_lo):
     src = np.empty(max(n, 1), np.int32)
     offs = np.empty(n_lists + 1, np.int64)
     counts = np.zeros(1, np.int64)
-    out = SmxRgaOut(_p(vals), _p(src), _p(offs), _p(counts))
+    tomb = np.zeros(max(n, 1), np.uint8) if tombstones else None
+    out = SmxRgaOut(_p(vals), _p(src), _p(offs), _p(counts), _p(tomb) if tombstones else None)
     rc = lib().smx_oracle_rga(C.byref(ops), C.byref(out))
     if rc != 0:
         raise RuntimeError(f"oracle rga failed: {rc}")
     k = int(counts[0])
+    if tombstones:
+        return vals[:k], src[:k], offs, tomb[:k].astype(np.bool_)
     return vals[:k], src[:k], offs

@@ -197,18 +197,33 @@ def test_rga_list_out_of_key_order_matches_reference_semantics():
 
 @pytest.mark.parametrize("n_ops,n_lists,seed", [(1_000_000, 5_000, 14), (300_000, 30, 15)])
 def test_rga_list_mode_live_elements_match(n_ops, n_lists, seed):
-    """At scale (the oracle has no list mode): the list state's live elements are exactly
-    materialize()'s output, list by list, and its tombstoned ones are extra elements."""
+    """At scale: the list state equals the oracle's list mode (every element, tombstoned
+    ones in their places and flagged); its live elements are exactly materialize()'s
+    output, list by list, and its tombstoned ones are extra elements."""
     batch = synth.rga_batch(n_ops, n_lists, seed)
     lv, ls, lo = rga_replay_device(batch)
     tv, ts, to, tomb = rga_replay_device(batch, tombstones=True)
     assert tomb.any()
+    _check_list_mode(batch, (tv, ts, to, tomb))
     for i in range(batch.n_lists):
         a, b = to[i], to[i + 1]
         live = ~tomb[a:b]
         assert np.array_equal(ts[a:b][live], ls[lo[i]:lo[i + 1]]), f"list {i}"
         assert np.array_equal(tv[a:b][live], lv[lo[i]:lo[i + 1]])
     assert np.all(batch.op[ts[tomb]] != 2)  # tombstoned elements were created by inserts / moves
+
+
+def _check_list_mode(batch, got=None, grouped=False):
+    """The library's list mode (smx_rga_out.out_tomb) against the oracle's: values, src,
+    offsets and tombstone flags of every element."""
+    gv, gs, go, gt = got if got is not None else rga_replay_device(batch, tombstones=True, grouped=grouped)
+    ov, os_, oo, ot = oracle.rga(batch.n_lists, batch.list_id, batch.op, batch.value, batch.anchor,
+                                 batch.t, batch.author, batch.opid_hi, batch.opid_lo, tombstones=True)
+    assert ot.any() and not ot.all()
+    assert np.array_equal(go, oo)
+    assert np.array_equal(gs, os_)
+    assert np.array_equal(gv, ov)
+    assert np.array_equal(gt, ot)
 
 
 def _check(batch, grouped=False):
@@ -296,6 +311,7 @@ def test_rga_mixed_list_sizes():
     counts = np.bincount(lid, minlength=2000)
     assert (counts > 2048).any() and ((counts > 512) & (counts <= 2048)).any() and (counts == 0).any()
     _check(b)
+    _check_list_mode(b)
 
 
 def test_rga_hot_list_and_invalid_input():

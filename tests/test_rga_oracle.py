@@ -1,4 +1,7 @@
 """The CPU RGA oracle (oracle/crdt_ref.c) reproduces the reference RGA's outputs."""
+import numpy as np
+import pytest
+
 from oracle import oracle
 from semantic_merge_amd.crdt import DELETE, INSERT, MOVE, Key, marshal_streams
 
@@ -94,3 +97,72 @@ def test_effective_keys_give_the_scan_slot():
             k = (rnd.choice("abcd"), rnd.randrange(4), "u", "o")
             scan = next((i for i, x in enumerate(ks) if k < x), len(ks))
             assert scan == bisect.bisect_right([tup(x) for x in eff], k)
+
+
+def test_rga_oracle_list_mode_matches_reference():
+    """The oracle's list mode (out_tomb given) is the reference's own RGA.list after each
+    golden stream: keys, values and tombstones of every element, in list order."""
+    cases = load("rga_cases.json")
+    want = load("rga_list_cases.json")
+    streams = to_streams(cases)
+    b = marshal_streams(streams)
+    vals, src, offs, tomb = oracle.rga(b.n_lists, b.list_id, b.op, b.value, b.anchor, b.t,
+                                       b.author, b.opid_hi, b.opid_lo, tombstones=True)
+    assert len(vals) == len(src) == len(tomb) == offs[-1]
+    assert tomb.sum() > 100 and (~tomb).sum() > 100
+    events = [ev for s in streams for ev in s]
+    srcl, tl, offl = src.tolist(), tomb.tolist(), offs.tolist()
+    for i, w in enumerate(want):
+        got = []
+        for s, tb in zip(srcl[offl[i]:offl[i + 1]], tl[offl[i]:offl[i + 1]]):
+            _, k, v = events[s]
+            got.append([[k.anchor, k.t, k.author, k.opid], v, tb])
+        assert got == w, f"rga list case {i}"
+    # materialize mode is the same state without the tombstoned elements
+    mv, ms, mo = oracle.rga(b.n_lists, b.list_id, b.op, b.value, b.anchor, b.t, b.author, b.opid_hi, b.opid_lo)
+    assert ms.tolist() == [s for s, tb in zip(srcl, tl) if not tb]
+    assert mv.tolist() == [v for v, tb in zip(vals.tolist(), tl) if not tb]
+    assert mo.tolist() == [0] + np.cumsum([sum(1 for tb in tl[offl[i]:offl[i + 1]] if not tb)
+                                           for i in range(b.n_lists)]).tolist()
+
+
+class _Val:
+    """A value that compares by its id and remembers the event that carried it."""
+    __slots__ = ("v", "i")
+
+    def __init__(self, v, i):
+        self.v, self.i = v, i
+
+    def __eq__(self, other):
+        return self.v == other.v
+
+    __hash__ = None
+
+
+@pytest.mark.parametrize("regime", ["narrow", "wide"])
+def test_rga_oracle_list_mode_matches_list_ref_on_ties(regime):
+    """Past the golden streams' 40 events: the oracle's list state equals the pure-Python
+    restatement oracle/rga_list_ref.py on the tie-heavy batch (lists of 0 to 5000 events,
+    keys tied at every level), list by list: creating events, values and tombstones."""
+    from oracle.rga_list_ref import ListRga
+    import _rga_shapes as shapes
+    b = shapes.tie_batch(regime=regime)
+    vals, src, offs, tomb = oracle.rga(*shapes.args(b), tombstones=True)
+    shapes.assert_ties(b, src, offs)
+    refs = [ListRga() for _ in range(b.n_lists)]
+    cols = [c.tolist() for c in (b.list_id, b.op, b.value, b.anchor, b.t, b.author, b.opid_hi, b.opid_lo)]
+    for i, (l, op, v, an, t, au, hi, lo) in enumerate(zip(*cols)):
+        if op == INSERT:
+            refs[l].insert((an, t, au, (hi, lo)), _Val(v, i))
+        elif op == MOVE:
+            refs[l].move(_Val(v, i), (an, t, au, (hi, lo)))
+        else:
+            refs[l].delete(_Val(v, i))
+    assert tomb.any() and not tomb.all()
+    for l, ref in enumerate(refs):
+        a, e = int(offs[l]), int(offs[l + 1])
+        st = ref.state()
+        assert src[a:e].tolist() == [v.i for _, v, _ in st], f"list {l}"
+        assert vals[a:e].tolist() == [v.v for _, v, _ in st], f"list {l}"
+        assert tomb[a:e].tolist() == [tb for _, _, tb in st], f"list {l}"
+    assert offs[-1] == len(src)
