@@ -8,6 +8,8 @@
  *                     rename/move chains :27-28,71-82,99-110; materialize :30-49)
  *   smx_compose_batch <- the same loop for many independent merges of at most 2048 ops
  *                    each, in one call (a merge queue, a rebase, a monorepo)
+ *   smx_compose_batch_shared <- the same, for merges that all have one log on one side,
+ *                    stored once
  *   smx_rga_replay <- semmerge/crdt.py:23-57  RGA.insert/move/delete/materialize,
  *                    batched over many independent lists
  *
@@ -196,6 +198,56 @@ int smx_compose_batch_workspace_bytes(int64_t n_merges, size_t* bytes);
  * SMX_E_WORKSPACE are reported before any HIP call; n_merges = 0 returns SMX_OK and
  * launches nothing. */
 int smx_compose_batch(const smx_batch* b, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Batched compose against one shared log: n_merges merges that all have the same log on one
+ * side (a merge queue composing every pull request's delta against the target branch's, a
+ * rebase composing every commit of a stack against the upstream delta).  The shared log is
+ * stored once, as ops [0, n_shared) of the columns; merge m's own ops are [off[m], off[m+1]).
+ * Merge m composes (shared, own_m) when shared_is_b = 0 and (own_m, shared) when it is 1, and
+ * its results are exactly those of smx_compose on that pair alone:
+ *   order[]    local to the merge: A's ops are 0 .. n_a-1 and B's follow (with shared_is_b = 0
+ *              the shared ops are 0 .. n_shared-1, with 1 they are len_m .. len_m+n_shared-1)
+ *   results    counts[2m] entries of order/addr/file/ctx starting at
+ *              r(m) = off[m] + (m - 1) * n_shared: every merge has room for n_shared + len_m
+ *              entries, in input order; the result arrays hold
+ *              n_out = n_total - n_shared + n_merges * n_shared entries
+ *   conflicts  conf_off, counts[2m+1] and truncation exactly as in smx_batch; pairs are
+ *              (A index, B index), local to the merge
+ * String and symbol ids form one domain for the whole batch (the shared log is stored once):
+ * n_sym bounds all of them.  The size classes, the launches and the stream-ordered contract
+ * (no host synchronisation, no allocation, no read-back) are those of smx_compose_batch.
+ *
+ * Checked on the device, per merge, before any of its own columns is read:
+ *   counts[2m] = counts[2m+1] = -1  off[m] < n_shared, off[m+1] < off[m] or > n_total,
+ *                                   conf_off decreasing or negative; or an op of the merge
+ *                                   with kind >= 18 or sym >= n_sym -- an op of the shared
+ *                                   log included: every merge then reports -1
+ *   counts[2m] = counts[2m+1] = -2  n_shared + len_m > 2048: send that merge through
+ *                                   smx_compose
+ * A failed merge writes nothing else and does not affect its neighbours.
+ */
+typedef struct smx_batch_shared {
+  int64_t n_merges, n_total, n_sym;
+  int64_t n_shared;                      /* ops [0, n_shared) of every column: the shared log */
+  const int64_t* off;                    /* device [n_merges+1], off[0] >= n_shared: merge m's
+                                            own ops are [off[m], off[m+1]) of the columns */
+  const uint8_t* kind; const uint64_t* ts, *oid_hi, *oid_lo;
+  const uint32_t* sym; const int32_t* v0, *v1;     /* as smx_ops, n_total entries */
+  int32_t* order, *addr, *file, *ctx;    /* n_out entries; merge m's results at r(m).. */
+  int32_t* conflicts; const int64_t* conf_off;  /* as smx_batch */
+  int64_t* counts;                       /* [2*n_merges]: composed ops, conflicts */
+  int32_t grid_cap;                      /* as smx_batch */
+  int32_t shared_is_b;                   /* 0: the shared log is branch A of every merge;
+                                            1: branch B */
+} smx_batch_shared;
+/* Workspace for a batch of n_merges (0 .. 2^31 - 1) merges. */
+int smx_compose_batch_shared_workspace_bytes(int64_t n_merges, size_t* bytes);
+/* SMX_E_ARG (negative sizes, n_shared > n_total, grid_cap < 0, shared_is_b not 0 or 1,
+ * n_sym > 2^32 - 1, a null pointer with n_merges > 0 -- the column and result arrays may be
+ * null only when n_total = 0) and SMX_E_WORKSPACE are reported before any HIP call;
+ * n_merges = 0 returns SMX_OK and launches nothing. */
+int smx_compose_batch_shared(const smx_batch_shared* b, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Sharded single merge: one process per GPU, shard r of G.

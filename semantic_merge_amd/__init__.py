@@ -2,7 +2,7 @@
 from .ops import Op, Target  # noqa: F401
 from .conflict import Conflict  # noqa: F401
 
-__all__ = ["Op", "Target", "Conflict", "compose_oplogs", "compose_many"]
+__all__ = ["Op", "Target", "Conflict", "compose_oplogs", "compose_many", "compose_against"]
 
 
 def __getattr__(name):
@@ -13,4 +13,7 @@ def __getattr__(name):
     if name == "compose_many":
         from .compose import compose_many
         return compose_many
+    if name == "compose_against":
+        from .compose import compose_against
+        return compose_against
     raise AttributeError(name)

@@ -63,6 +63,32 @@ class SmxBatch(C.Structure):
     ]
 
 
+class SmxBatchShared(C.Structure):
+    _fields_ = [
+        ("n_merges", C.c_int64),
+        ("n_total", C.c_int64),
+        ("n_sym", C.c_int64),
+        ("n_shared", C.c_int64),
+        ("off", C.c_void_p),
+        ("kind", C.c_void_p),
+        ("ts", C.c_void_p),
+        ("oid_hi", C.c_void_p),
+        ("oid_lo", C.c_void_p),
+        ("sym", C.c_void_p),
+        ("v0", C.c_void_p),
+        ("v1", C.c_void_p),
+        ("order", C.c_void_p),
+        ("addr", C.c_void_p),
+        ("file", C.c_void_p),
+        ("ctx", C.c_void_p),
+        ("conflicts", C.c_void_p),
+        ("conf_off", C.c_void_p),
+        ("counts", C.c_void_p),
+        ("grid_cap", C.c_int32),
+        ("shared_is_b", C.c_int32),
+    ]
+
+
 BATCH_MAX_OPS = 2048          # ops per merge of smx_compose_batch (larger: counts -2)
 BATCH_CLASSES = (256, 1024, 2048)  # its size classes (csrc/smx_batch.h)
 
@@ -143,6 +169,8 @@ EXPORTS = (
     "smx_set_small_limit",
     "smx_compose_batch_workspace_bytes",
     "smx_compose_batch",
+    "smx_compose_batch_shared_workspace_bytes",
+    "smx_compose_batch_shared",
     "smx_shard_step",
     "smx_shard_range_info",
     "smx_set_profiling",
@@ -180,6 +208,11 @@ def declare(lib: C.CDLL) -> C.CDLL:
         lib.smx_compose_batch_workspace_bytes.restype = C.c_int
         lib.smx_compose_batch.argtypes = [C.POINTER(SmxBatch), C.c_void_p, C.c_size_t, C.c_void_p]
         lib.smx_compose_batch.restype = C.c_int
+    if hasattr(lib, "smx_compose_batch_shared"):  # (older builds, e.g. A/B baselines, lack it)
+        lib.smx_compose_batch_shared_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_size_t)]
+        lib.smx_compose_batch_shared_workspace_bytes.restype = C.c_int
+        lib.smx_compose_batch_shared.argtypes = [C.POINTER(SmxBatchShared), C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.smx_compose_batch_shared.restype = C.c_int
     lib.smx_shard_step.argtypes = [C.POINTER(SmxOps), C.POINTER(SmxShard), C.POINTER(SmxComposeOut),
                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
     lib.smx_shard_step.restype = C.c_int

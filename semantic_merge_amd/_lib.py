@@ -283,6 +283,95 @@ class DeviceBatch:
         return out
 
 
+class DeviceBatchShared:
+    """Device-resident inputs, outputs and workspace for repeated smx_compose_batch_shared
+    calls on a SharedSoA (tests, tools/shared_probe.py).  The optional arguments reach the
+    corners of the C ABI (include/smx.h smx_batch_shared):
+    shared_is_b   smx_batch_shared.shared_is_b;
+    conflict_caps per-merge capacities of the conflict pairs (default min(n_shared, len_m));
+    grid_cap      smx_batch_shared.grid_cap;
+    off           the offsets passed instead of the SharedSoA's own;
+    n_sym         the symbol bound passed instead of the SharedSoA's;
+    n_total       smx_batch_shared.n_total passed instead of the columns' real length;
+    fill          every output word (results, conflict pairs, counts) starts as this value,
+                  and CONF_GUARD such words follow the last merge's conflict region."""
+
+    CONF_GUARD = 64
+
+    def __init__(self, ssoa, device: str = "cuda", shared_is_b: bool = False, conflict_caps=None, grid_cap: int = 0,
+                 off=None, n_sym: Optional[int] = None, fill: Optional[int] = None,
+                 n_total: Optional[int] = None) -> None:
+        torch = _torch()
+        self.torch = torch
+        dev = self.device = torch.device(device)
+        self.ssoa = ssoa
+        M = self.n_merges = ssoa.n_merges
+        S = self.n_shared = int(ssoa.n_shared)
+        self.off = np.asarray(ssoa.off if off is None else off, np.int64).reshape(M + 1)
+        tot = self.n_total = int(ssoa.n_total)
+        lens = np.diff(np.asarray(ssoa.off, np.int64))
+        caps = np.minimum(lens, S) if conflict_caps is None else conflict_caps
+        self.conf_off = np.zeros(M + 1, np.int64)
+        np.cumsum(caps, out=self.conf_off[1:])
+        self.n_sym = int(ssoa.n_sym) if n_sym is None else n_sym
+        self.n_out = tot - S + M * S
+
+        def up(a, dt=None):
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(a.view(dt) if dt is not None else a).to(dev)
+
+        def col(name, dt, view):
+            return up(np.ascontiguousarray(getattr(ssoa, name)).astype(dt, copy=False), view)
+
+        self._in = [col("kind", np.uint8, None), col("ts", np.uint64, np.int64), col("oid_hi", np.uint64, np.int64),
+                    col("oid_lo", np.uint64, np.int64), col("sym", np.uint32, np.int32), col("v0", np.int32, None),
+                    col("v1", np.int32, None)]
+        self._idx = [up(self.off), up(self.conf_off)]
+        f = 0 if fill is None else fill
+        self.order, self.addr, self.file, self.ctx = (
+            torch.full((max(self.n_out, 1),), f, dtype=torch.int32, device=dev) for _ in range(4))
+        self.conf = torch.full((2 * int(self.conf_off[-1]) + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        self.counts = torch.full((2 * max(M, 1),), f, dtype=torch.int64, device=dev)
+        ws = C.c_size_t(0)
+        check(lib().smx_compose_batch_shared_workspace_bytes(M, C.byref(ws)))
+        self.ws_bytes = ws.value
+        self.ws = torch.empty(max(ws.value, 1), dtype=torch.uint8, device=dev)
+        self._b = _abi.SmxBatchShared(M, tot if n_total is None else n_total, self.n_sym, S, self._idx[0].data_ptr(),
+                                      *[t.data_ptr() for t in self._in], self.order.data_ptr(), self.addr.data_ptr(),
+                                      self.file.data_ptr(), self.ctx.data_ptr(), self.conf.data_ptr(),
+                                      self._idx[1].data_ptr(), self.counts.data_ptr(), grid_cap, int(shared_is_b))
+
+    def slot(self, m: int) -> int:
+        """r(m): where merge m's results start in order / addr / file / ctx."""
+        return int(self.off[m]) + (m - 1) * self.n_shared
+
+    def run(self, stream=None) -> None:
+        """Enqueue one smx_compose_batch_shared on `stream` (default: torch's current stream)."""
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().smx_compose_batch_shared(C.byref(self._b), self.ws.data_ptr(), self.ws_bytes, s.cuda_stream))
+
+    def raw(self) -> dict:
+        """Every output array as the device holds it (after a device sync), on the host."""
+        self.torch.cuda.synchronize(self.device)
+        return {k: getattr(self, k).cpu().numpy() for k in ("order", "addr", "file", "ctx", "conf", "counts")}
+
+    def results(self, raw: Optional[dict] = None):
+        """Per merge (order, addr, file, ctx, pairs) trimmed to its counts and its conflict
+        capacity, or its negative counts[2m] for a merge that failed."""
+        r = self.raw() if raw is None else raw
+        out = []
+        for m in range(self.n_merges):
+            k, nc = int(r["counts"][2 * m]), int(r["counts"][2 * m + 1])
+            if k < 0:
+                out.append(k)
+                continue
+            o, c = self.slot(m), int(self.conf_off[m])
+            nc = min(nc, int(self.conf_off[m + 1]) - c)
+            out.append(tuple(r[x][o: o + k] for x in ("order", "addr", "file", "ctx"))
+                       + (r["conf"][2 * c: 2 * (c + nc)].reshape(nc, 2),))
+        return out
+
+
 def _al(x: int) -> int:
     return (x + 255) & ~255
 
@@ -514,6 +603,123 @@ class ComposeSession:
                 raise SmxError(e.code, f"merge {i}: {e}") from None
         return res
 
+    # -- batched compose against one shared log (smx_compose_batch_shared) -------------------
+
+    def _shared_layout(self, n_total: int, n_shared: int, m: int):
+        """Byte offsets of a shared-log batch in the staging areas: the input columns for
+        n_total ops (the shared log once), then off / conf_off; the four outputs of
+        n_total - n_shared + m * n_shared entries, the conflict pairs (at most
+        n_total - n_shared) and the counts."""
+        lay, o = {"n_total": n_total}, 0
+        for name, w in self._IN:
+            lay[name] = o
+            o += _al(n_total * w)
+        for name in ("off", "conf_off"):
+            lay[name] = o
+            o += _al((m + 1) * 8)
+        lay["in_bytes"] = o
+        q = _al((n_total - n_shared + m * n_shared) * 4)
+        lay["q"], lay["conf"], lay["counts"] = q, 4 * q, 4 * q + _al(8 * (n_total - n_shared) + 8)
+        lay["out_bytes"] = lay["counts"] + 16 * m
+        return lay
+
+    def staging_shared(self, n_total: int, n_shared: int, n_merges: int) -> dict:
+        """The input columns of a shared-log batch of n_total ops as views of the pinned
+        staging area, laid out as compose_shared() copies them: a SharedSoA marshalled into
+        them is not packed again."""
+        lay = self._shared_layout(n_total, n_shared, n_merges)
+        self._ensure_batch(lay, 0)
+        hin = self.h_in.numpy()
+        return {name: hin[lay[name]: lay[name] + n_total * w].view(self._DT[name]) for name, w in self._IN}
+
+    def compose_shared(self, ssoa, shared_is_b: bool = False, copy: bool = True):
+        """[(order, addr, file, ctx, conflict_pairs)] of the merges (shared, branch m) -- or
+        (branch m, shared) with shared_is_b -- of a SharedSoA, in branch order.  The columns,
+        the shared log once, are staged as they are: one host-to-device copy, one
+        smx_compose_batch_shared, one copy back, one stream sync.  Merges over BATCH_MAX_OPS
+        ops (the library sends them back, counts -2) go through compose(ssoa.merge(m))
+        afterwards.  Invalid input raises SmxError naming the merge.  copy=False: views of
+        the staging area, valid until the session's next merge (taken only when no merge is
+        routed through compose())."""
+        import time
+        t0 = time.perf_counter()
+        M, S, tot = ssoa.n_merges, int(ssoa.n_shared), int(ssoa.n_total)
+        off = np.ascontiguousarray(ssoa.off, dtype=np.int64)
+        lens = off[1:] - off[:-1]
+        if M and (int(off[0]) < S or (lens < 0).any() or int(off[-1]) > tot):
+            raise SmxError(-1, "invalid input: the branch offsets leave the columns or decrease")
+        if M:  # (the batch has one bound for all its symbols; entries before off[0] are no merge's)
+            sym = np.asarray(ssoa.sym)
+            if S and int(np.max(sym[:S])) >= ssoa.n_sym:
+                raise SmxError(-1, "the shared log: invalid input: sym >= n_sym")
+            o0, o1 = int(off[0]), int(off[-1])
+            if o1 > o0 and int(np.max(sym[o0:o1])) >= ssoa.n_sym:
+                at = o0 + int(np.argmax(sym[o0:o1] >= ssoa.n_sym))
+                raise SmxError(-1, f"merge {int(np.searchsorted(off, at, 'right')) - 1}: invalid input: sym >= n_sym")
+        res = [None] * M
+        routed = []
+        self.last = {"pack_s": 0.0, "device_s": 0.0, "unpack_s": 0.0, "in_bytes": 0}
+        if M and (S + lens <= _abi.BATCH_MAX_OPS).any():
+            lay = self._shared_layout(tot, S, M)
+            ws = C.c_size_t(0)
+            check(lib().smx_compose_batch_shared_workspace_bytes(M, C.byref(ws)))
+            self._ensure_batch(lay, ws.value)
+            hin, hout = self.h_in.numpy(), self.h_out.numpy()
+            h0 = hin.ctypes.data
+            conf_off = np.zeros(M + 1, np.int64)
+            np.cumsum(np.minimum(lens, S), out=conf_off[1:])  # min(n_a, n_b): never truncates
+            for name, w in self._IN:
+                col, at = getattr(ssoa, name), lay[name]
+                if not (isinstance(col, np.ndarray) and col.ctypes.data == h0 + at and col.nbytes == tot * w):
+                    hin[at: at + tot * w] = np.ascontiguousarray(col).view(np.uint8).reshape(-1)
+            for name, arr in (("off", off), ("conf_off", conf_off)):
+                hin[lay[name]: lay[name] + arr.nbytes] = arr.view(np.uint8)
+            t1 = time.perf_counter()
+            hip = _hiprt()
+            st = self.stream.cuda_stream
+            d0, o0 = self.d_in.data_ptr(), self.d_out.data_ptr()
+            _hip_check(hip.hipMemcpyAsync(d0, self.h_in.data_ptr(), lay["in_bytes"], 1, st), "hipMemcpyAsync (inputs)")
+            q = lay["q"]
+            b = _abi.SmxBatchShared(M, tot, int(ssoa.n_sym), S, d0 + lay["off"],
+                                    *[d0 + lay[name] for name, _ in self._IN],
+                                    o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"], d0 + lay["conf_off"],
+                                    o0 + lay["counts"], 0, int(bool(shared_is_b)))
+            check(lib().smx_compose_batch_shared(C.byref(b), self.ws.data_ptr(), ws.value, st))
+            _hip_check(hip.hipMemcpyAsync(self.h_out.data_ptr(), o0, lay["out_bytes"], 2, st), "hipMemcpyAsync (outputs)")
+            _hip_check(hip.hipStreamSynchronize(st), "hipStreamSynchronize")
+            t2 = time.perf_counter()
+            counts = hout[lay["counts"]: lay["counts"] + 16 * M].view(np.int64)
+            for m in range(M):
+                k, nc = int(counts[2 * m]), int(counts[2 * m + 1])
+                if k == -2:
+                    routed.append(m)
+                    continue
+                if k < 0:
+                    raise SmxError(-1, f"merge {m}: invalid input: sym >= n_sym or kind >= 18")
+                if nc > conf_off[m + 1] - conf_off[m]:
+                    raise SmxError(-2, f"merge {m}: {nc} conflicts exceed capacity {conf_off[m + 1] - conf_off[m]}")
+                o = 4 * (int(off[m]) + (m - 1) * S)
+                c = lay["conf"] + 8 * int(conf_off[m])
+                res[m] = tuple(hout[j * q + o: j * q + o + 4 * k].view(np.int32) for j in range(4)) + (
+                    hout[c: c + 8 * nc].view(np.int32).reshape(nc, 2),)
+            if copy or routed:  # (compose() below reuses the staging area)
+                res = [r if r is None else tuple(x.copy() for x in r) for r in res]
+            self.last = {"pack_s": t1 - t0, "device_s": t2 - t1, "unpack_s": time.perf_counter() - t2,
+                         "in_bytes": lay["in_bytes"]}
+        else:
+            routed = list(range(M))
+        if routed:
+            # (copies: the columns may be views of the staging area that compose() packs into)
+            merges = [ssoa.merge(m, shared_is_b) for m in routed]
+            last = self.last
+            for m, soa in zip(routed, merges):
+                try:
+                    res[m] = self.compose(soa)
+                except SmxError as e:
+                    raise SmxError(e.code, f"merge {m}: {e}") from None
+            self.last = last  # (the batch's legs; the routed merges are compose()'s)
+        return res
+
 
 _sessions = {}
 
@@ -561,6 +767,14 @@ def compose_soa_many(soas, device: str = "cuda"):
     drop-in merge of this thread holds that session)."""
     s = session(device)
     return (s if not s.busy else ComposeSession(device)).compose_many(soas)
+
+
+def compose_soa_shared(ssoa, shared_is_b: bool = False, device: str = "cuda"):
+    """[(order, addr, file, ctx, conflict_pairs)] of a SharedSoA's merges in one batch
+    (ComposeSession.compose_shared on the thread's session, or on buffers of its own while a
+    drop-in merge of this thread holds that session)."""
+    s = session(device)
+    return (s if not s.busy else ComposeSession(device)).compose_shared(ssoa, shared_is_b)
 
 
 def set_small_limit(n: int) -> int:

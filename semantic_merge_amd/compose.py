@@ -15,9 +15,11 @@ from __future__ import annotations
 
 from typing import Any, List, Sequence, Tuple
 
+import numpy as np
+
 from ._abi import BATCH_MAX_OPS
 from ._lib import dropin_session
-from .marshal import marshal_native
+from .marshal import marshal_native, marshal_shared
 from .materialize import materialize_conflicts, materialize_ops_native
 
 
@@ -56,4 +58,37 @@ def compose_many(pairs: Sequence[Tuple[Sequence[Any], Sequence[Any]]]) -> List[T
     for i, (a, b) in enumerate(logs):
         if res[i] is None:
             res[i] = compose_oplogs(a, b)
+    return res
+
+
+def compose_against(shared: Sequence[Any], branches: Sequence[Sequence[Any]],
+                    shared_side: str = "a") -> List[Tuple[List[Any], List[Any]]]:
+    """``[compose_oplogs(shared, b) for b in branches]`` -- or ``compose_oplogs(b, shared)``
+    with ``shared_side="b"`` -- for merges that all have one log on one side: a merge queue
+    composing every pull request's delta against the target branch's, a rebase composing
+    every commit of a stack against the upstream delta.  The shared log is marshalled and
+    copied to the GPU once, and the merges of at most 2048 ops run as one batch (one copy in,
+    one smx_compose_batch_shared, one copy back, one sync); larger merges follow one by one.
+    Inputs are never mutated."""
+    if shared_side not in ("a", "b"):
+        raise ValueError("shared_side must be 'a' or 'b'")
+    is_b = shared_side == "b"
+    sh = list(shared)
+    logs = [list(b) for b in branches]
+    if not logs:
+        return []
+    res: List[Tuple[List[Any], List[Any]]] = []
+    with dropin_session() as sess:
+        # marshalled straight into the session's pinned staging columns; the results are
+        # views of its staging area too, materialised while the session is held
+        n_total = len(sh) + sum(len(b) for b in logs)
+        ssoa = marshal_shared(sh, logs, sess.staging_shared(n_total, len(sh), len(logs)))
+        kind = ssoa.kind.copy()  # (a merge routed through compose() reuses the staging columns)
+        k_sh = kind[: len(sh)]
+        for m, (order, addr, file, ctx, cpairs) in enumerate(sess.compose_shared(ssoa, is_b, copy=False)):
+            k_own = kind[int(ssoa.off[m]): int(ssoa.off[m + 1])]
+            ops = logs[m] + sh if is_b else sh + logs[m]
+            k = np.concatenate([k_own, k_sh] if is_b else [k_sh, k_own])
+            res.append((materialize_ops_native(ops, k, ssoa.strings, order, addr, file, ctx),
+                        materialize_conflicts(ops, cpairs)))
     return res

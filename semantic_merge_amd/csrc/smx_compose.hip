@@ -3302,25 +3302,32 @@ struct BatchGrid {
   int dev = -1;
   int wg[BATCH_CLASSES] = {};
 };
-static int batch_grid_of(const BatchGrid** out) {
-  static thread_local BatchGrid g[4];
+template <typename K>
+static int batch_grid_fill(BatchGrid* g, K k0, K k1, K k2, const BatchGrid** out) {
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   BatchGrid* e = &g[dev & 3];
   if (e->dev != dev) {
     int cus = 0, per[BATCH_CLASSES] = {};
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[0], k_compose_batch<batch_class_cap(0)>,
-                                                         batch_class_cap(0) / 2, 0));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[1], k_compose_batch<batch_class_cap(1)>,
-                                                         batch_class_cap(1) / 2, 0));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[2], k_compose_batch<batch_class_cap(2)>,
-                                                         batch_class_cap(2) / 2, 0));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[0], k0, batch_class_cap(0) / 2, 0));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[1], k1, batch_class_cap(1) / 2, 0));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[2], k2, batch_class_cap(2) / 2, 0));
     for (int c = 0; c < BATCH_CLASSES; ++c) e->wg[c] = (per[c] > 0 ? per[c] : 1) * (cus > 0 ? cus : 1);
     e->dev = dev;
   }
   *out = e;
   return SMX_OK;
+}
+static int batch_grid_of(const BatchGrid** out) {
+  static thread_local BatchGrid g[4];
+  return batch_grid_fill(g, k_compose_batch<batch_class_cap(0)>, k_compose_batch<batch_class_cap(1)>,
+                         k_compose_batch<batch_class_cap(2)>, out);
+}
+static int batch_shared_grid_of(const BatchGrid** out) {
+  static thread_local BatchGrid g[4];
+  return batch_grid_fill(g, k_compose_batch_shared<batch_class_cap(0)>, k_compose_batch_shared<batch_class_cap(1)>,
+                         k_compose_batch_shared<batch_class_cap(2)>, out);
 }
 
 extern "C" int smx_compose_batch_workspace_bytes(int64_t n_merges, size_t* bytes) {
@@ -3366,6 +3373,57 @@ extern "C" int smx_compose_batch(const smx_batch* b, void* workspace, size_t wor
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_compose_batch<batch_class_cap(2)>, grid(2), dim3(batch_class_cap(2) / 2), 0, st, *b, cnt + 2,
                        lists + 2 * (stride / 4));
+    HIP_TRY(hipGetLastError());
+  } catch (const std::exception& e) {
+    return set_err(SMX_E_HIP, e.what());
+  }
+  return SMX_OK;
+}
+
+extern "C" int smx_compose_batch_shared_workspace_bytes(int64_t n_merges, size_t* bytes) {
+  return smx_compose_batch_workspace_bytes(n_merges, bytes);  // the same class counts and lists
+}
+
+extern "C" int smx_compose_batch_shared(const smx_batch_shared* b, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+  if (!b) return set_err(SMX_E_ARG, "null batch");
+  if (b->n_merges < 0 || b->n_merges > 0x7fffffffll || b->n_total < 0 || b->n_sym < 0 || b->n_shared < 0 ||
+      b->grid_cap < 0)
+    return set_err(SMX_E_ARG, "negative size");
+  if (b->n_shared > b->n_total) return set_err(SMX_E_ARG, "n_shared over n_total");
+  if (b->shared_is_b != 0 && b->shared_is_b != 1) return set_err(SMX_E_ARG, "shared_is_b is neither 0 nor 1");
+  if (b->n_sym > 0xffffffffll) return set_err(SMX_E_ARG, "n_sym over 2^32 - 1");
+  if (b->n_merges == 0) return SMX_OK;
+  if (!b->off || !b->conf_off || !b->counts || !b->conflicts)
+    return set_err(SMX_E_ARG, "null off / conf_off / counts / conflicts");
+  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1 || !b->order ||
+                         !b->addr || !b->file || !b->ctx))
+    return set_err(SMX_E_ARG, "null column or result array");
+  const size_t stride = batch_list_bytes(b->n_merges);
+  if (!workspace || workspace_bytes < BATCH_HDR + BATCH_CLASSES * stride)
+    return set_err(SMX_E_WORKSPACE, "workspace too small (smx_compose_batch_shared_workspace_bytes)");
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  try {
+    const BatchGrid* G;
+    if (int rc = batch_shared_grid_of(&G)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    u32* cnt = (u32*)workspace;
+    u32* lists = (u32*)((char*)workspace + BATCH_HDR);
+    hipLaunchKernelGGL(k_batch_shared_classify, dim3(1), dim3(256), 0, st, *b, cnt, lists, stride / 4);
+    HIP_TRY(hipGetLastError());
+    auto grid = [&](int c) {
+      i64 g = G->wg[c] < b->n_merges ? (i64)G->wg[c] : b->n_merges;
+      if (b->grid_cap > 0 && g > b->grid_cap) g = b->grid_cap;
+      return dim3((unsigned)g);
+    };
+    hipLaunchKernelGGL(k_compose_batch_shared<batch_class_cap(0)>, grid(0), dim3(batch_class_cap(0) / 2), 0, st, *b,
+                       cnt + 0, lists);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_compose_batch_shared<batch_class_cap(1)>, grid(1), dim3(batch_class_cap(1) / 2), 0, st, *b,
+                       cnt + 1, lists + stride / 4);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_compose_batch_shared<batch_class_cap(2)>, grid(2), dim3(batch_class_cap(2) / 2), 0, st, *b,
+                       cnt + 2, lists + 2 * (stride / 4));
     HIP_TRY(hipGetLastError());
   } catch (const std::exception& e) {
     return set_err(SMX_E_HIP, e.what());

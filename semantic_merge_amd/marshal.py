@@ -262,3 +262,79 @@ def marshal_native(delta_a: Sequence[Any], delta_b: Sequence[Any], cols: Optiona
         id_mode, hi, lo = _encode_ids(ids)
     return SoA(len(delta_a), len(delta_b), kind, ts, hi, lo, sym, v0, v1, max(n_sym, 1),
                strings, ts_mode, id_mode)
+
+
+_COLS = ("kind", "ts", "oid_hi", "oid_lo", "sym", "v0", "v1")
+
+
+@dataclass
+class SharedSoA:
+    """Host image of ``smx_batch_shared`` (include/smx.h): one shared log, stored once as
+    ops ``[0, n_shared)`` of the columns, and M branch logs, branch m at
+    ``[off[m], off[m + 1])``.  Symbols, strings, equality classes and the timestamp / id
+    encodings are one domain for the whole batch."""
+
+    n_shared: int
+    off: np.ndarray       # i64 [M + 1], off[0] >= n_shared
+    kind: np.ndarray      # the columns of SoA, off[M] entries
+    ts: np.ndarray
+    oid_hi: np.ndarray
+    oid_lo: np.ndarray
+    sym: np.ndarray
+    v0: np.ndarray
+    v1: np.ndarray
+    n_sym: int
+    strings: List[str] = field(default_factory=list)
+    ts_mode: int = TS_ISO
+    id_mode: int = ID_UUID
+
+    @property
+    def n_merges(self) -> int:
+        return len(self.off) - 1
+
+    @property
+    def n_total(self) -> int:
+        return len(self.kind)
+
+    def merge(self, m: int, shared_is_b: bool = False) -> SoA:
+        """Merge m as an ordinary SoA of its own (copies of the columns): (shared, branch m),
+        or (branch m, shared) with shared_is_b.  Ids stay in the batch's domain (``strings``,
+        ``n_sym``)."""
+        o0, o1 = int(self.off[m]), int(self.off[m + 1])
+        parts = (slice(o0, o1), slice(0, self.n_shared)) if shared_is_b else (slice(0, self.n_shared), slice(o0, o1))
+        cols = [np.concatenate([np.asarray(getattr(self, c))[p] for p in parts]) for c in _COLS]
+        n_a = o1 - o0 if shared_is_b else self.n_shared
+        return SoA(n_a, self.n_shared + o1 - o0 - n_a, *cols, self.n_sym, self.strings, self.ts_mode, self.id_mode)
+
+
+def marshal_shared(shared: Sequence[Any], branches: Sequence[Sequence[Any]], cols: Optional[dict] = None) -> SharedSoA:
+    """Build the SharedSoA of ``[compose_oplogs(shared, b) for b in branches]`` (or of
+    ``compose_oplogs(b, shared)``: the side is chosen when composing) in one pass of the
+    native host module over ``shared + branches[0] + branches[1] + ...``: the shared log is
+    marshalled once, with one symbol table, one string table and one equality-class table.
+    The timestamp and id encodings are chosen once for the batch; a dense-rank fallback
+    ranks over the union of the logs, which keeps every merge's order.  Same exceptions as
+    ``marshal``.  cols: preallocated output columns of all the ops (as ``marshal_native``)."""
+    from ._host import host
+    ops = list(shared)
+    n_shared = len(ops)
+    off = [n_shared]
+    for b in branches:
+        ops.extend(b)
+        off.append(len(ops))
+    n = len(ops)
+    if cols is None:
+        kind, ts, hi, lo = np.empty(n, np.uint8), np.empty(n, np.uint64), np.empty(n, np.uint64), np.empty(n, np.uint64)
+        sym, v0, v1 = np.empty(n, np.uint32), np.empty(n, np.int32), np.empty(n, np.int32)
+    else:
+        kind, ts, hi, lo, sym, v0, v1 = (cols[k] for k in _COLS)
+    n_sym, strings, ts_ok, id_mode, ts_str, ids = host().marshal_ops(
+        ops, KIND_RANK, KIND_UNKNOWN, KIND_MOVE, KIND_RENAME, DEFAULT_TIMESTAMP, eq_key,
+        kind, ts, hi, lo, sym, v0, v1)
+    ts_mode = TS_ISO
+    if not ts_ok:
+        ts_mode, ts = _encode_ts(ts_str)
+    if id_mode < 0:
+        id_mode, hi, lo = _encode_ids(ids)
+    return SharedSoA(n_shared, np.asarray(off, np.int64), kind, ts, hi, lo, sym, v0, v1, max(n_sym, 1),
+                     strings, ts_mode, id_mode)

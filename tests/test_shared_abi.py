@@ -1,0 +1,120 @@
+"""smx_compose_batch_shared's C ABI without a GPU: the ctypes mirror of smx_batch_shared has
+the header's layout, the library exports the new symbols, and the argument errors come back
+before any HIP call."""
+import ctypes as C
+import os
+import subprocess
+import tempfile
+
+import pytest
+
+from semantic_merge_amd import _abi
+from semantic_merge_amd._lib import LIB_PATH
+
+HDR_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+SMX_OK, SMX_E_ARG, SMX_E_WORKSPACE = 0, -1, -4
+
+
+def test_smx_batch_shared_matches_header():
+    py = _abi.SmxBatchShared
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "smx.h"', "int main(void) {",
+             'printf("size %zu\\n", sizeof(smx_batch_shared));']
+    for fname, _ in py._fields_:
+        lines.append(f'printf("{fname} %zu\\n", offsetof(smx_batch_shared, {fname}));')
+    lines.append("return 0; }")
+    with tempfile.TemporaryDirectory() as d:
+        src, exe = os.path.join(d, "l.c"), os.path.join(d, "l")
+        open(src, "w").write("\n".join(lines))
+        r = subprocess.run(["gcc", "-I", HDR_DIR, "-o", exe, src], capture_output=True, text=True)
+        if r.returncode != 0 and "not found" in r.stderr:
+            pytest.skip("no C compiler")
+        assert r.returncode == 0, r.stderr
+        out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")
+    got = {line.split()[0]: int(line.split()[1]) for line in filter(None, out)}
+    assert got.pop("size") == C.sizeof(py)
+    assert set(got) == {f for f, _ in py._fields_}
+    for fname, _ in py._fields_:
+        assert got[fname] == getattr(py, fname).offset, fname
+
+
+@pytest.fixture(scope="module")
+def lib():
+    assert os.path.exists(LIB_PATH), "build libsmx.so first (__graft_entry__.build())"
+    return _abi.declare(C.CDLL(LIB_PATH))
+
+
+def test_symbols_exported(lib):
+    for name in ("smx_compose_batch_shared_workspace_bytes", "smx_compose_batch_shared"):
+        assert name in _abi.EXPORTS
+        assert hasattr(lib, name), name
+    assert lib.smx_compose_batch_shared.argtypes[0] is C.POINTER(_abi.SmxBatchShared)
+
+
+def test_workspace_query(lib):
+    size = C.c_size_t(0)
+    assert lib.smx_compose_batch_shared_workspace_bytes(1000, C.byref(size)) == SMX_OK
+    assert size.value > 0
+    assert lib.smx_compose_batch_shared_workspace_bytes(-1, C.byref(size)) == SMX_E_ARG
+    assert lib.smx_last_error()
+    assert lib.smx_compose_batch_shared_workspace_bytes(1 << 31, C.byref(size)) == SMX_E_ARG
+    assert lib.smx_compose_batch_shared_workspace_bytes(5, None) == SMX_E_ARG
+    assert lib.smx_compose_batch_shared_workspace_bytes(0, C.byref(size)) == SMX_OK
+
+
+def _batch(n_merges, n_total, buf, n_shared=3):
+    """A batch whose every pointer is the (host) buffer `buf`: the calls below fail before
+    anything reads it."""
+    p = C.addressof(buf) if buf is not None else 0
+    return _abi.SmxBatchShared(n_merges, n_total, 4, n_shared, *([p] * 15), 0, 0)
+
+
+def test_argument_errors_without_gpu(lib):
+    buf = (C.c_uint8 * 4096)()
+    ws = (C.c_uint8 * 4096)()
+    need = C.c_size_t(0)
+    assert lib.smx_compose_batch_shared_workspace_bytes(1, C.byref(need)) == SMX_OK
+    assert 0 < need.value <= 4096
+
+    def call(b, w=ws, nbytes=4096):
+        rc = lib.smx_compose_batch_shared(C.byref(b) if b is not None else None, w, nbytes, None)
+        if rc != SMX_OK:
+            assert lib.smx_last_error(), "an error code without a message"
+        return rc
+
+    # negative sizes
+    for b in (_batch(-1, 10, buf), _batch(1, -1, buf, 0), _batch(1, 10, buf, -1)):
+        assert call(b) == SMX_E_ARG
+    for field, value in (("n_sym", -1), ("grid_cap", -1), ("n_sym", 1 << 32), ("n_shared", 11),
+                         ("shared_is_b", 2), ("shared_is_b", -1)):
+        b = _batch(1, 10, buf)
+        setattr(b, field, value)
+        assert call(b) == SMX_E_ARG, (field, value)
+    assert b"shared_is_b" in lib.smx_last_error()
+    # the bounds that are still arguments: the largest n_sym, n_shared = n_total, both sides
+    # (they reach the workspace check, which fails before any HIP call)
+    for field, value in (("n_sym", (1 << 32) - 1), ("n_shared", 10), ("shared_is_b", 1)):
+        b = _batch(1, 10, buf)
+        setattr(b, field, value)
+        assert call(b, ws, need.value - 1) == SMX_E_WORKSPACE, (field, value)
+    # null columns with one merge; then each pointer alone
+    assert call(_batch(1, 10, None)) == SMX_E_ARG
+    n_ptr = 0
+    for fname, ft in _abi.SmxBatchShared._fields_:
+        if ft is C.c_void_p:
+            b = _batch(1, 10, buf)
+            setattr(b, fname, None)
+            assert call(b) == SMX_E_ARG, fname
+            n_ptr += 1
+    assert n_ptr == 15
+    assert call(None) == SMX_E_ARG
+    # a short or missing workspace
+    b = _batch(1, 10, buf)
+    assert call(b, ws, need.value - 1) == SMX_E_WORKSPACE
+    assert call(b, None, 4096) == SMX_E_WORKSPACE
+    assert b"workspace" in lib.smx_last_error()
+
+
+def test_no_merges_is_ok(lib):
+    assert lib.smx_compose_batch_shared(C.byref(_batch(0, 0, None, 0)), None, 0, None) == SMX_OK
+    buf = (C.c_uint8 * 64)()
+    assert lib.smx_compose_batch_shared(C.byref(_batch(0, 10, buf)), None, 0, None) == SMX_OK
