@@ -10,6 +10,8 @@
  *                    each, in one call (a merge queue, a rebase, a monorepo)
  *   smx_compose_batch_shared <- the same, for merges that all have one log on one side,
  *                    stored once
+ *   smx_screen    <- the conflict list of the same loop alone (what semmerge/__main__.py
+ *                    looks at first), for many pairs of logs, from the logs' renames
  *   smx_rga_replay <- semmerge/crdt.py:23-57  RGA.insert/move/delete/materialize,
  *                    batched over many independent lists
  *
@@ -248,6 +250,63 @@ int smx_compose_batch_shared_workspace_bytes(int64_t n_merges, size_t* bytes);
  * null only when n_total = 0) and SMX_E_WORKSPACE are reported before any HIP call;
  * n_merges = 0 returns SMX_OK and launches nothing. */
 int smx_compose_batch_shared(const smx_batch_shared* b, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Conflict screen: which of n_pairs pairs of logs, taken from n_logs logs stored once, have
+ * DivergentRename conflicts, and which ones -- without composing any pair (a merge queue asking
+ * which pull requests conflict with the target branch, or with each other).  The conflict
+ * list of smx_compose on two logs is a function of the two logs' renames alone: each log's
+ * renames in (ts, oid_hi, oid_lo, index) order, merged A first on equal keys, and the
+ * reference's two-head walk over them (compose.py:16-21, 60-70, 88-98).  So each log's
+ * renames are extracted and sorted once, however many pairs hold the log, and a pair costs
+ * one merge and one walk of two short lists.  The limits are on renames, not on ops.
+ *
+ * Log l's ops are [log_off[l], log_off[l+1]) of the columns (entries that no log of a pair
+ * covers are never read).  Pair p screens (log pair_a[p] as A, log pair_b[p] as B);
+ * pair_a[p] == pair_b[p] is an ordinary pair.  For every valid pair, counts[p] and the written
+ * conflict pairs equal counts[1] and conflicts of smx_compose on that pair alone, in the same
+ * order: (A index, B index) into A||B, the A index in [0, len_a), the B index len_a + j.
+ * counts[p] is the full number of conflicts; the first conf_off[p+1] - conf_off[p] pairs are
+ * written at conflicts[2 * conf_off[p]] and nothing at or past the pair's region.  conflicts
+ * and conf_off both NULL: capacity 0 for every pair (counts only).
+ *
+ * kind is read for every op of a log that a call holds; ts, oid_hi, oid_lo, sym and v0 are
+ * read for renames only.  sym is only compared for equality, so it has no bound (there is
+ * no n_sym), and there is no v1.
+ *
+ * Checked on the device:
+ *   counts[p] = -1  pair_a[p] or pair_b[p] outside [0, n_logs); conf_off[p] negative or
+ *                   conf_off[p+1] < conf_off[p]; or either log is invalid: log_off[l] < 0 or
+ *                   below an earlier offset (log_off decreases: the log that ends early and
+ *                   every log that starts before an earlier offset), log_off[l+1] < log_off[l]
+ *                   or > n_total, or an op with kind >= 18
+ *   counts[p] = -2  a log of the pair has more than 2048 renames, or the pair's renames
+ *                   together exceed 2048: send that pair through smx_compose
+ * A failed pair writes nothing else and does not affect its neighbours.
+ *
+ * Stream-ordered as smx_compose_batch: six launches whatever the data, no host
+ * synchronisation, no allocation, no read-back.  A device pre-pass sorts the pairs into
+ * size classes by their renames (128, 512, 2048) and one launch per class runs them.  One
+ * workgroup extracts a log's renames, so a log of many millions of ops is served slowly.
+ *
+ * The struct and the function share their name, so C callers write `struct smx_screen`.
+ */
+struct smx_screen {
+  int64_t n_logs, n_total, n_pairs;
+  const int64_t* log_off;          /* device [n_logs+1]: log l's ops are [log_off[l], log_off[l+1]) */
+  const uint8_t* kind; const uint64_t* ts, *oid_hi, *oid_lo;
+  const uint32_t* sym; const int32_t* v0;          /* as smx_ops, n_total entries; no v1 */
+  const int32_t* pair_a, *pair_b;  /* device [n_pairs]: pair p screens (log pair_a[p], log pair_b[p]) */
+  int32_t* conflicts; const int64_t* conf_off;     /* as smx_batch, per pair; both NULL: capacity 0 everywhere */
+  int64_t* counts;                 /* device [n_pairs] */
+  int32_t grid_cap;                /* as smx_batch; also caps the per-log launch */
+};
+/* Workspace (8-byte aligned) for n_logs and n_pairs in 0 .. 2^31 - 1: about 36 bytes per op. */
+int smx_screen_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs, size_t* bytes);
+/* SMX_E_ARG (negative sizes, grid_cap < 0, exactly one of conflicts / conf_off null, a null
+ * log_off / pair_a / pair_b / counts, a null column with n_total > 0) and SMX_E_WORKSPACE are
+ * reported before any HIP call; n_pairs = 0 or n_logs = 0 returns SMX_OK and launches nothing. */
+int smx_screen(const struct smx_screen* s, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Sharded single merge: one process per GPU, shard r of G.

@@ -2,7 +2,8 @@
 from .ops import Op, Target  # noqa: F401
 from .conflict import Conflict  # noqa: F401
 
-__all__ = ["Op", "Target", "Conflict", "compose_oplogs", "compose_many", "compose_against"]
+__all__ = ["Op", "Target", "Conflict", "compose_oplogs", "compose_many", "compose_against",
+           "screen_conflicts"]
 
 
 def __getattr__(name):
@@ -16,4 +17,7 @@ def __getattr__(name):
     if name == "compose_against":
         from .compose import compose_against
         return compose_against
+    if name == "screen_conflicts":
+        from .compose import screen_conflicts
+        return screen_conflicts
     raise AttributeError(name)

@@ -89,6 +89,29 @@ class SmxBatchShared(C.Structure):
     ]
 
 
+class SmxScreen(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_int64),
+        ("n_total", C.c_int64),
+        ("n_pairs", C.c_int64),
+        ("log_off", C.c_void_p),
+        ("kind", C.c_void_p),
+        ("ts", C.c_void_p),
+        ("oid_hi", C.c_void_p),
+        ("oid_lo", C.c_void_p),
+        ("sym", C.c_void_p),
+        ("v0", C.c_void_p),
+        ("pair_a", C.c_void_p),
+        ("pair_b", C.c_void_p),
+        ("conflicts", C.c_void_p),
+        ("conf_off", C.c_void_p),
+        ("counts", C.c_void_p),
+        ("grid_cap", C.c_int32),
+    ]
+
+
+SCREEN_MAX_RENAMES = 2048     # renames per pair of smx_screen, both logs together (more: counts -2)
+SCREEN_CLASSES = (128, 512, 2048)  # its size classes, in renames (csrc/smx_screen.h)
 BATCH_MAX_OPS = 2048          # ops per merge of smx_compose_batch (larger: counts -2)
 BATCH_CLASSES = (256, 1024, 2048)  # its size classes (csrc/smx_batch.h)
 
@@ -171,6 +194,8 @@ EXPORTS = (
     "smx_compose_batch",
     "smx_compose_batch_shared_workspace_bytes",
     "smx_compose_batch_shared",
+    "smx_screen_workspace_bytes",
+    "smx_screen",
     "smx_shard_step",
     "smx_shard_range_info",
     "smx_set_profiling",
@@ -213,6 +238,11 @@ def declare(lib: C.CDLL) -> C.CDLL:
         lib.smx_compose_batch_shared_workspace_bytes.restype = C.c_int
         lib.smx_compose_batch_shared.argtypes = [C.POINTER(SmxBatchShared), C.c_void_p, C.c_size_t, C.c_void_p]
         lib.smx_compose_batch_shared.restype = C.c_int
+    if hasattr(lib, "smx_screen"):  # (older builds, e.g. A/B baselines, lack it)
+        lib.smx_screen_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]
+        lib.smx_screen_workspace_bytes.restype = C.c_int
+        lib.smx_screen.argtypes = [C.POINTER(SmxScreen), C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.smx_screen.restype = C.c_int
     lib.smx_shard_step.argtypes = [C.POINTER(SmxOps), C.POINTER(SmxShard), C.POINTER(SmxComposeOut),
                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
     lib.smx_shard_step.restype = C.c_int

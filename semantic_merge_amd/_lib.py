@@ -372,6 +372,97 @@ class DeviceBatchShared:
         return out
 
 
+def _rename_counts(kind, log_off) -> np.ndarray:
+    """Renames per log (i64 [n_logs]) of a LogsSoA's kind column."""
+    csum = np.concatenate([[0], np.cumsum(np.asarray(kind) == 1, dtype=np.int64)])  # SMX_KIND_RENAME
+    off = np.clip(np.asarray(log_off, np.int64), 0, len(csum) - 1)
+    return np.maximum(csum[off[1:]] - csum[off[:-1]], 0)
+
+
+class DeviceScreen:
+    """Device-resident inputs, outputs and workspace for repeated smx_screen calls on a
+    LogsSoA and a list of (i, j) pairs (tests, tools/screen_probe.py).  The optional
+    arguments reach the corners of the C ABI (include/smx.h smx_screen):
+    conflict_caps per-pair capacities of the conflict pairs (default: min of the two logs'
+                  renames, which always suffices); "null": conflicts and conf_off are NULL;
+    grid_cap      smx_screen.grid_cap;
+    log_off       the offsets passed instead of the LogsSoA's own;
+    n_total       smx_screen.n_total passed instead of the columns' real length;
+    fill          every output word (conflict pairs, counts) starts as this value, and
+                  CONF_GUARD such words follow the last pair's conflict region."""
+
+    CONF_GUARD = 64
+
+    def __init__(self, lsoa, pairs, device: str = "cuda", conflict_caps=None, grid_cap: int = 0, log_off=None,
+                 n_total: Optional[int] = None, fill: Optional[int] = None) -> None:
+        torch = _torch()
+        self.torch = torch
+        dev = self.device = torch.device(device)
+        self.lsoa = lsoa
+        L = self.n_logs = lsoa.n_logs
+        self.pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+        P = self.n_pairs = len(self.pairs)
+        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
+        tot = self.n_total = int(lsoa.n_total)
+        self.null_conf = isinstance(conflict_caps, str) and conflict_caps == "null"
+        if conflict_caps is None:
+            ren = _rename_counts(lsoa.kind, lsoa.log_off)
+            ok = ((self.pairs >= 0) & (self.pairs < L)).all(axis=1)
+            pa, pb = np.where(ok, self.pairs[:, 0], 0), np.where(ok, self.pairs[:, 1], 0)
+            caps = np.where(ok, np.minimum(ren[pa], ren[pb]), 0) if L else np.zeros(P, np.int64)
+        else:
+            caps = np.zeros(P, np.int64) if self.null_conf else conflict_caps
+        self.conf_off = np.zeros(P + 1, np.int64)
+        np.cumsum(caps, out=self.conf_off[1:])
+
+        def up(a, dt=None):
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(a.view(dt) if dt is not None else a).to(dev)
+
+        def col(name, dt, view):
+            return up(np.ascontiguousarray(getattr(lsoa, name)).astype(dt, copy=False), view)
+
+        self._in = [col("kind", np.uint8, None), col("ts", np.uint64, np.int64), col("oid_hi", np.uint64, np.int64),
+                    col("oid_lo", np.uint64, np.int64), col("sym", np.uint32, np.int32), col("v0", np.int32, None)]
+        self._idx = [up(self.log_off), up(self.pairs[:, 0]), up(self.pairs[:, 1]), up(self.conf_off)]
+        f = 0 if fill is None else fill
+        self.conf = torch.full((2 * int(self.conf_off[-1]) + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        self.counts = torch.full((max(P, 1),), f, dtype=torch.int64, device=dev)
+        ws = C.c_size_t(0)
+        check(lib().smx_screen_workspace_bytes(L, tot, P, C.byref(ws)))
+        self.ws_bytes = ws.value
+        self.ws = torch.empty(max(ws.value, 1), dtype=torch.uint8, device=dev)
+        self._s = _abi.SmxScreen(L, tot if n_total is None else n_total, P, self._idx[0].data_ptr(),
+                                 *[_ptr(t) for t in self._in], _ptr(self._idx[1]), _ptr(self._idx[2]),
+                                 0 if self.null_conf else self.conf.data_ptr(),
+                                 0 if self.null_conf else self._idx[3].data_ptr(), self.counts.data_ptr(), grid_cap)
+
+    def run(self, stream=None) -> None:
+        """Enqueue one smx_screen on `stream` (default: torch's current stream)."""
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().smx_screen(C.byref(self._s), self.ws.data_ptr(), self.ws_bytes, s.cuda_stream))
+
+    def raw(self) -> dict:
+        """Every output array as the device holds it (after a device sync), on the host."""
+        self.torch.cuda.synchronize(self.device)
+        return {k: getattr(self, k).cpu().numpy() for k in ("conf", "counts")}
+
+    def results(self, raw: Optional[dict] = None):
+        """Per pair its conflict pairs trimmed to its count and its capacity, or its negative
+        counts[p] for a pair that failed."""
+        r = self.raw() if raw is None else raw
+        out = []
+        for p in range(self.n_pairs):
+            nc = int(r["counts"][p])
+            if nc < 0:
+                out.append(nc)
+                continue
+            c = int(self.conf_off[p])
+            nc = min(nc, int(self.conf_off[p + 1]) - c)
+            out.append(r["conf"][2 * c: 2 * (c + nc)].reshape(nc, 2))
+        return out
+
+
 def _al(x: int) -> int:
     return (x + 255) & ~255
 
@@ -720,6 +811,113 @@ class ComposeSession:
             self.last = last  # (the batch's legs; the routed merges are compose()'s)
         return res
 
+    # -- conflict screen (smx_screen): many pairs of logs stored once, conflicts only ---------
+
+    _SCREEN_IN = _IN[:6]  # (no v1)
+
+    def _screen_layout(self, n_total: int, n_logs: int, n_pairs: int, n_conf: int = 0):
+        """Byte offsets of a screen in the staging areas: the six input columns for n_total
+        ops, then log_off / pair_a / pair_b / conf_off; the conflict pairs and the counts."""
+        lay, o = {"n_total": n_total}, 0
+        for name, w in self._SCREEN_IN:
+            lay[name] = o
+            o += _al(n_total * w)
+        lay["col_bytes"] = o
+        for name, nbytes in (("log_off", (n_logs + 1) * 8), ("pair_a", n_pairs * 4), ("pair_b", n_pairs * 4),
+                             ("conf_off", (n_pairs + 1) * 8)):
+            lay[name] = o
+            o += _al(nbytes)
+        lay["in_bytes"] = o
+        lay["conf"], lay["counts"] = 0, _al(8 * n_conf + 8)
+        lay["out_bytes"] = lay["counts"] + 8 * n_pairs
+        return lay
+
+    def staging_logs(self, n_total: int, n_logs: int, n_pairs: int) -> dict:
+        """The input columns of a screen of n_total ops as views of the pinned staging area,
+        laid out as screen() copies them (plus a v1 column of its own, which the marshaller
+        fills and the screen does not read): a LogsSoA marshalled into them is not packed
+        again."""
+        lay = self._screen_layout(n_total, n_logs, n_pairs)
+        self._ensure_batch(lay, 0)
+        hin = self.h_in.numpy()
+        cols = {name: hin[lay[name]: lay[name] + n_total * w].view(self._DT[name]) for name, w in self._SCREEN_IN}
+        cols["v1"] = np.empty(n_total, np.int32)
+        return cols
+
+    def screen(self, lsoa, pairs):
+        """The conflict pairs (an (n, 2) int32 array of (A index, B index) into
+        log i || log j, as compose()'s fifth result) of every (i, j) of `pairs` over a
+        LogsSoA: one host-to-device copy of the six columns (33 bytes per op, each log once),
+        one smx_screen, one copy back of the counts and the conflict pairs, one stream sync.
+        Pairs whose renames exceed SCREEN_MAX_RENAMES (the library sends them back, counts -2)
+        go through compose(lsoa.pair(i, j)) afterwards, keeping only the conflicts.  Invalid
+        input raises SmxError naming the pair."""
+        import time
+        t0 = time.perf_counter()
+        pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        P, L, tot = len(pairs), lsoa.n_logs, int(lsoa.n_total)
+        self.last = {"pack_s": 0.0, "device_s": 0.0, "unpack_s": 0.0, "in_bytes": 0, "out_bytes": 0, "routed": 0}
+        if P == 0:
+            return []
+        bad = np.flatnonzero(((pairs < 0) | (pairs >= L)).any(axis=1))
+        if len(bad):
+            raise SmxError(-1, f"pair {int(bad[0])}: a log index outside [0, {L})")
+        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
+        ren = _rename_counts(lsoa.kind, log_off)
+        conf_off = np.zeros(P + 1, np.int64)
+        np.cumsum(np.minimum(ren[pairs[:, 0]], ren[pairs[:, 1]]), out=conf_off[1:])  # never truncates
+        lay = self._screen_layout(tot, L, P, int(conf_off[-1]))
+        ws = C.c_size_t(0)
+        check(lib().smx_screen_workspace_bytes(L, tot, P, C.byref(ws)))
+        self._ensure_batch(lay, ws.value)
+        hin, hout = self.h_in.numpy(), self.h_out.numpy()
+        h0 = hin.ctypes.data
+        for name, w in self._SCREEN_IN:
+            col, at = getattr(lsoa, name), lay[name]
+            if not (isinstance(col, np.ndarray) and col.ctypes.data == h0 + at and col.nbytes == tot * w):
+                hin[at: at + tot * w] = np.ascontiguousarray(col).view(np.uint8).reshape(-1)
+        for name, arr in (("log_off", log_off), ("pair_a", np.ascontiguousarray(pairs[:, 0])),
+                          ("pair_b", np.ascontiguousarray(pairs[:, 1])), ("conf_off", conf_off)):
+            hin[lay[name]: lay[name] + arr.nbytes] = arr.view(np.uint8)
+        t1 = time.perf_counter()
+        hip = _hiprt()
+        st = self.stream.cuda_stream
+        d0, o0 = self.d_in.data_ptr(), self.d_out.data_ptr()
+        _hip_check(hip.hipMemcpyAsync(d0, self.h_in.data_ptr(), lay["in_bytes"], 1, st), "hipMemcpyAsync (inputs)")
+        s = _abi.SmxScreen(L, tot, P, d0 + lay["log_off"], *[d0 + lay[name] for name, _ in self._SCREEN_IN],
+                           d0 + lay["pair_a"], d0 + lay["pair_b"], o0 + lay["conf"], d0 + lay["conf_off"],
+                           o0 + lay["counts"], 0)
+        check(lib().smx_screen(C.byref(s), self.ws.data_ptr(), ws.value, st))
+        _hip_check(hip.hipMemcpyAsync(self.h_out.data_ptr(), o0, lay["out_bytes"], 2, st), "hipMemcpyAsync (outputs)")
+        _hip_check(hip.hipStreamSynchronize(st), "hipStreamSynchronize")
+        t2 = time.perf_counter()
+        counts = hout[lay["counts"]: lay["counts"] + 8 * P].view(np.int64)
+        bad = np.flatnonzero((counts < 0) & (counts != -2))
+        if len(bad):
+            p = int(bad[0])
+            raise SmxError(-1, f"pair {p} (logs {int(pairs[p, 0])}, {int(pairs[p, 1])}): invalid input: "
+                               "log offsets that decrease or leave the columns, or kind >= 18")
+        over = np.flatnonzero(counts > conf_off[1:] - conf_off[:-1])
+        if len(over):
+            raise SmxError(-2, f"pair {int(over[0])}: {int(counts[over[0]])} conflicts exceed its capacity")
+        conf = hout[lay["conf"]: lay["conf"] + 8 * int(conf_off[-1])].view(np.int32).reshape(-1, 2)
+        res = [None if counts[p] < 0 else conf[int(conf_off[p]): int(conf_off[p]) + int(counts[p])].copy()
+               for p in range(P)]
+        routed = [p for p in range(P) if res[p] is None]
+        self.last = {"pack_s": t1 - t0, "device_s": t2 - t1, "unpack_s": time.perf_counter() - t2,
+                     "in_bytes": lay["in_bytes"], "out_bytes": lay["out_bytes"], "routed": len(routed)}
+        if routed:
+            # (copies: the columns may be views of the staging area that compose() packs into)
+            soas = [lsoa.pair(int(pairs[p, 0]), int(pairs[p, 1])) for p in routed]
+            last = self.last
+            for p, soa in zip(routed, soas):
+                try:
+                    res[p] = self.compose(soa)[4]
+                except SmxError as e:
+                    raise SmxError(e.code, f"pair {p}: {e}") from None
+            self.last = last  # (the screen's legs; the routed pairs are compose()'s)
+        return res
+
 
 _sessions = {}
 
@@ -775,6 +973,14 @@ def compose_soa_shared(ssoa, shared_is_b: bool = False, device: str = "cuda"):
     drop-in merge of this thread holds that session)."""
     s = session(device)
     return (s if not s.busy else ComposeSession(device)).compose_shared(ssoa, shared_is_b)
+
+
+def screen_soa(lsoa, pairs, device: str = "cuda"):
+    """[conflict_pairs] of the (i, j) of `pairs` over a LogsSoA (ComposeSession.screen on the
+    thread's session, or on buffers of its own while a drop-in merge of this thread holds
+    that session)."""
+    s = session(device)
+    return (s if not s.busy else ComposeSession(device)).screen(lsoa, pairs)
 
 
 def set_small_limit(n: int) -> int:

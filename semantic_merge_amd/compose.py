@@ -13,14 +13,14 @@ it into the reference CLI, rebind the module attribute the CLI looks up
 """
 from __future__ import annotations
 
-from typing import Any, List, Sequence, Tuple
+from typing import Any, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from ._abi import BATCH_MAX_OPS
 from ._lib import dropin_session
-from .marshal import marshal_native, marshal_shared
-from .materialize import materialize_conflicts, materialize_ops_native
+from .marshal import marshal_logs, marshal_native, marshal_shared
+from .materialize import conflict_factory, materialize_conflicts, materialize_ops_native
 
 
 def compose_oplogs(delta_a: Sequence[Any], delta_b: Sequence[Any]) -> Tuple[List[Any], List[Any]]:
@@ -91,4 +91,36 @@ def compose_against(shared: Sequence[Any], branches: Sequence[Sequence[Any]],
             k = np.concatenate([k_own, k_sh] if is_b else [k_sh, k_own])
             res.append((materialize_ops_native(ops, k, ssoa.strings, order, addr, file, ctx),
                         materialize_conflicts(ops, cpairs)))
+    return res
+
+
+def screen_conflicts(logs: Sequence[Sequence[Any]],
+                     pairs: Optional[Sequence[Tuple[int, int]]] = None) -> List[List[Any]]:
+    """``[compose_oplogs(logs[i], logs[j])[1] for i, j in pairs]`` -- the DivergentRename
+    conflicts alone, no composed ops -- for a caller that asks which of many logs conflict
+    (a merge queue: every pull request against the target branch, or against each other
+    before they share a merge train).  ``pairs=None``: all ``i < j``.  Every log is
+    marshalled, copied to the GPU and has its renames sorted once, whatever the number of
+    pairs that hold it; a pair costs one merge of two short lists (one copy in, one
+    smx_screen, one copy back, one sync).  Pairs of more than 2048 renames follow through
+    the full composition one by one.  Inputs are never mutated and no ``Op`` is cloned: the
+    conflicts are built from the input objects, as in the reference."""
+    ops = [list(x) for x in logs]
+    if pairs is None:
+        pairs = [(i, j) for i in range(len(ops)) for j in range(i + 1, len(ops))]
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    for i, j in pairs:
+        if not (0 <= i < len(ops) and 0 <= j < len(ops)):
+            raise IndexError(f"pair ({i}, {j}) outside the {len(ops)} logs")
+    if not pairs:
+        return []
+    make = conflict_factory()
+    with dropin_session() as sess:
+        # marshalled straight into the session's pinned staging columns
+        lsoa = marshal_logs(ops, sess.staging_logs(sum(len(x) for x in ops), len(ops), len(pairs)))
+        found = sess.screen(lsoa, pairs)
+    res: List[List[Any]] = []
+    for (i, j), cp in zip(pairs, found):
+        a, b, na = ops[i], ops[j], len(ops[i])
+        res.append([make(a[x], b[y - na]) for x, y in cp.tolist()])
     return res

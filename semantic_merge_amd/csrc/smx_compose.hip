@@ -39,6 +39,7 @@
 #include "smx_window.h"
 #include "smx_small.h"
 #include "smx_batch.h"
+#include "smx_screen.h"
 #include "smx_tables.h"
 
 
@@ -3424,6 +3425,91 @@ extern "C" int smx_compose_batch_shared(const smx_batch_shared* b, void* workspa
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_compose_batch_shared<batch_class_cap(2)>, grid(2), dim3(batch_class_cap(2) / 2), 0, st, *b,
                        cnt + 2, lists + 2 * (stride / 4));
+    HIP_TRY(hipGetLastError());
+  } catch (const std::exception& e) {
+    return set_err(SMX_E_HIP, e.what());
+  }
+  return SMX_OK;
+}
+
+// Workgroups of k_screen_extract and of each screen class that one device holds at once.
+struct ScreenGrid {
+  int dev = -1;
+  int wg1 = 1;
+  int wg[SCREEN_CLASSES] = {};
+};
+static int screen_grid_of(const ScreenGrid** out) {
+  static thread_local ScreenGrid g[4];
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  ScreenGrid* e = &g[dev & 3];
+  if (e->dev != dev) {
+    int cus = 0, per1 = 0, per[SCREEN_CLASSES] = {};
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per1, k_screen_extract, SCREEN_T1, 0));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[0], k_screen_pairs<screen_class_cap(0)>,
+                                                         screen_class_cap(0) / 2, 0));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[1], k_screen_pairs<screen_class_cap(1)>,
+                                                         screen_class_cap(1) / 2, 0));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[2], k_screen_pairs<screen_class_cap(2)>,
+                                                         screen_class_cap(2) / 2, 0));
+    if (cus <= 0) cus = 1;
+    e->wg1 = (per1 > 0 ? per1 : 1) * cus;
+    for (int c = 0; c < SCREEN_CLASSES; ++c) e->wg[c] = (per[c] > 0 ? per[c] : 1) * cus;
+    e->dev = dev;
+  }
+  *out = e;
+  return SMX_OK;
+}
+
+extern "C" int smx_screen_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs, size_t* bytes) {
+  if (!bytes) return set_err(SMX_E_ARG, "null bytes");
+  if (n_logs < 0 || n_logs > 0x7fffffffll || n_pairs < 0 || n_pairs > 0x7fffffffll || n_total < 0)
+    return set_err(SMX_E_ARG, "n_logs or n_pairs outside 0 .. 2^31 - 1, or n_total negative");
+  *bytes = screen_ws_bytes(n_logs, n_total, n_pairs);
+  return SMX_OK;
+}
+
+extern "C" int smx_screen(const struct smx_screen* s, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!s) return set_err(SMX_E_ARG, "null screen");
+  if (s->n_logs < 0 || s->n_logs > 0x7fffffffll || s->n_pairs < 0 || s->n_pairs > 0x7fffffffll || s->n_total < 0 ||
+      s->grid_cap < 0)
+    return set_err(SMX_E_ARG, "negative size");
+  if ((s->conflicts == nullptr) != (s->conf_off == nullptr))
+    return set_err(SMX_E_ARG, "conflicts and conf_off are both null or both set");
+  if (s->n_pairs == 0 || s->n_logs == 0) return SMX_OK;
+  if (!s->log_off || !s->pair_a || !s->pair_b || !s->counts)
+    return set_err(SMX_E_ARG, "null log_off / pair_a / pair_b / counts");
+  if (s->n_total > 0 && (!s->kind || !s->ts || !s->oid_hi || !s->oid_lo || !s->sym || !s->v0))
+    return set_err(SMX_E_ARG, "null column");
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < screen_ws_bytes(s->n_logs, s->n_total, s->n_pairs))
+    return set_err(SMX_E_WORKSPACE, "workspace too small or not 8-byte aligned (smx_screen_workspace_bytes)");
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  try {
+    const ScreenGrid* G;
+    if (int rc = screen_grid_of(&G)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const ScreenWs w = screen_ws(workspace, s->n_logs, s->n_total, s->n_pairs);
+    auto grid = [&](int resident, i64 items) {
+      i64 g = resident < items ? (i64)resident : items;
+      if (s->grid_cap > 0 && g > s->grid_cap) g = s->grid_cap;
+      return dim3((unsigned)g);
+    };
+    hipLaunchKernelGGL(k_screen_logs, dim3(1), dim3(1024), 0, st, *s, w);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_extract, grid(G->wg1, s->n_logs), dim3(SCREEN_T1), 0, st, *s, w);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_classify, dim3((unsigned)SMX_CEIL_DIV(s->n_pairs, (i64)SCREEN_CHUNK)), dim3(256), 0, st,
+                       *s, w);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_pairs<screen_class_cap(0)>, grid(G->wg[0], s->n_pairs), dim3(screen_class_cap(0) / 2), 0,
+                       st, *s, w, w.cnt + 0, w.lists);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_pairs<screen_class_cap(1)>, grid(G->wg[1], s->n_pairs), dim3(screen_class_cap(1) / 2), 0,
+                       st, *s, w, w.cnt + 1, w.lists + w.list_stride);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_pairs<screen_class_cap(2)>, grid(G->wg[2], s->n_pairs), dim3(screen_class_cap(2) / 2), 0,
+                       st, *s, w, w.cnt + 2, w.lists + 2 * w.list_stride);
     HIP_TRY(hipGetLastError());
   } catch (const std::exception& e) {
     return set_err(SMX_E_HIP, e.what());

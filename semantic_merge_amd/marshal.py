@@ -338,3 +338,50 @@ def marshal_shared(shared: Sequence[Any], branches: Sequence[Sequence[Any]], col
         id_mode, hi, lo = _encode_ids(ids)
     return SharedSoA(n_shared, np.asarray(off, np.int64), kind, ts, hi, lo, sym, v0, v1, max(n_sym, 1),
                      strings, ts_mode, id_mode)
+
+
+@dataclass
+class LogsSoA:
+    """Host image of ``smx_screen``'s logs (include/smx.h): N logs stored once, log l at
+    ``[log_off[l], log_off[l + 1])`` of the columns.  Symbols, strings, equality classes and
+    the timestamp / id encodings are one domain for all the logs, so any two of them form a
+    merge."""
+
+    log_off: np.ndarray   # i64 [N + 1]
+    kind: np.ndarray      # the columns of SoA, log_off[N] entries
+    ts: np.ndarray
+    oid_hi: np.ndarray
+    oid_lo: np.ndarray
+    sym: np.ndarray
+    v0: np.ndarray
+    v1: np.ndarray
+    n_sym: int
+    strings: List[str] = field(default_factory=list)
+    ts_mode: int = TS_ISO
+    id_mode: int = ID_UUID
+
+    @property
+    def n_logs(self) -> int:
+        return len(self.log_off) - 1
+
+    @property
+    def n_total(self) -> int:
+        return len(self.kind)
+
+    def pair(self, i: int, j: int) -> SoA:
+        """(log i, log j) as an ordinary SoA of its own (copies of the columns).  Ids stay
+        in the logs' common domain (``strings``, ``n_sym``)."""
+        a = slice(int(self.log_off[i]), int(self.log_off[i + 1]))
+        b = slice(int(self.log_off[j]), int(self.log_off[j + 1]))
+        cols = [np.concatenate([np.asarray(getattr(self, c))[a], np.asarray(getattr(self, c))[b]]) for c in _COLS]
+        return SoA(a.stop - a.start, b.stop - b.start, *cols, self.n_sym, self.strings, self.ts_mode, self.id_mode)
+
+
+def marshal_logs(logs: Sequence[Sequence[Any]], cols: Optional[dict] = None) -> LogsSoA:
+    """Build the LogsSoA of ``logs`` in one pass of the native host module over
+    ``logs[0] + logs[1] + ...`` (``marshal_shared`` with no shared log): every log is
+    marshalled once, whatever the number of pairs that hold it.  Same exceptions as
+    ``marshal``.  cols: preallocated output columns of all the ops (as ``marshal_native``)."""
+    s = marshal_shared((), logs, cols)
+    return LogsSoA(s.off, s.kind, s.ts, s.oid_hi, s.oid_lo, s.sym, s.v0, s.v1, s.n_sym, s.strings,
+                   s.ts_mode, s.id_mode)
