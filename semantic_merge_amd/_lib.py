@@ -200,7 +200,82 @@ class DeviceCompose:
                 self.conf[: 2 * nc].cpu().numpy().reshape(nc, 2))
 
 
-class DeviceBatch:
+_COLS = (("kind", np.uint8, None), ("ts", np.uint64, np.int64), ("oid_hi", np.uint64, np.int64),
+         ("oid_lo", np.uint64, np.int64), ("sym", np.uint32, np.int32), ("v0", np.int32, None), ("v1", np.int32, None))
+
+
+class _DeviceMany:
+    """What DeviceBatch, DeviceBatchShared and DeviceScreen share: the uploads, the outputs
+    filled with one value and followed by CONF_GUARD such words, the workspace, and run /
+    raw / results.  A subclass builds its struct (_arg) for its entry point (_call), names
+    its output arrays (_OUT) and says where item m's results start (_start)."""
+
+    CONF_GUARD = 64
+    _OUT = ("order", "addr", "file", "ctx", "conf", "counts")
+    _PER = 2  # counts words per item: (composed ops, conflicts), or the conflicts alone
+
+    def _open(self, device: str) -> None:
+        self.torch = _torch()
+        self.device = self.torch.device(device)
+
+    def _up(self, a, dt=None):
+        a = np.ascontiguousarray(a)
+        return self.torch.from_numpy(a.view(dt) if dt is not None else a).to(self.device)
+
+    def _upload_cols(self, sources, n_cols: int = 7) -> None:
+        """_in: the first n_cols columns of the sources, one after another, on the device."""
+        self._in = [self._up(np.concatenate([np.ascontiguousarray(getattr(s, name)).astype(dt, copy=False)
+                                             for s in sources]) if sources else np.zeros(0, dt), view)
+                    for name, dt, view in _COLS[:n_cols]]
+
+    def _alloc(self, n: int, caps, n_out: int, fill: Optional[int], query, *sizes) -> None:
+        """conf_off from the n items' capacities; every output array of _OUT filled (the
+        results n_out entries long); the workspace that `query(*sizes)` asks for."""
+        torch, dev = self.torch, self.device
+        self.conf_off = np.zeros(n + 1, np.int64)
+        np.cumsum(caps, out=self.conf_off[1:])
+        f = 0 if fill is None else fill
+        for name in self._OUT[:-2]:
+            setattr(self, name, torch.full((max(n_out, 1),), f, dtype=torch.int32, device=dev))
+        self.conf = torch.full((2 * int(self.conf_off[-1]) + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        self.counts = torch.full((self._PER * max(n, 1),), f, dtype=torch.int64, device=dev)
+        ws = C.c_size_t(0)
+        check(query(*sizes, C.byref(ws)))
+        self.ws_bytes = ws.value
+        self.ws = torch.empty(max(ws.value, 1), dtype=torch.uint8, device=dev)
+
+    def run(self, stream=None) -> None:
+        """Enqueue one call of the entry point on `stream` (default: torch's current stream)."""
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(self._call(C.byref(self._arg), self.ws.data_ptr(), self.ws_bytes, s.cuda_stream))
+
+    def raw(self) -> dict:
+        """Every output array as the device holds it (after a device sync), on the host."""
+        self.torch.cuda.synchronize(self.device)
+        return {k: getattr(self, k).cpu().numpy() for k in self._OUT}
+
+    def results(self, raw: Optional[dict] = None):
+        """Per item its result arrays (if it has any) and conflict pairs, trimmed to its counts
+        and its conflict capacity, or its negative count for an item that failed."""
+        r = self.raw() if raw is None else raw
+        out = []
+        for m in range(len(self.conf_off) - 1):
+            k, nc = int(r["counts"][self._PER * m]), int(r["counts"][self._PER * (m + 1) - 1])
+            if k < 0:
+                out.append(k)
+                continue
+            c = int(self.conf_off[m])
+            nc = min(nc, int(self.conf_off[m + 1]) - c)
+            pairs = r["conf"][2 * c: 2 * (c + nc)].reshape(nc, 2)
+            if self._PER == 1:
+                out.append(pairs)
+            else:
+                o = self._start(m)
+                out.append(tuple(r[x][o: o + k] for x in self._OUT[:-2]) + (pairs,))
+        return out
+
+
+class DeviceBatch(_DeviceMany):
     """Device-resident inputs, outputs and workspace for repeated smx_compose_batch calls
     on a list of merges (tests, tools/batch_probe.py).  The optional arguments reach the
     corners of the C ABI (include/smx.h smx_batch):
@@ -212,78 +287,31 @@ class DeviceBatch:
     fill          every output word (results, conflict pairs, counts) starts as this value,
                   and CONF_GUARD such words follow the last merge's conflict region."""
 
-    CONF_GUARD = 64
-
     def __init__(self, soas, device: str = "cuda", conflict_caps=None, grid_cap: int = 0, n_a=None,
                  n_sym: Optional[int] = None, fill: Optional[int] = None, n_total: Optional[int] = None) -> None:
-        torch = _torch()
-        self.torch = torch
-        dev = self.device = torch.device(device)
+        self._open(device)
         soas = self.soas = list(soas)
         M = self.n_merges = len(soas)
         self.off = np.zeros(M + 1, np.int64)
         np.cumsum([s.n for s in soas], out=self.off[1:])
         tot = self.n_total = int(self.off[-1])
         self.n_a = np.asarray([s.n_a for s in soas] if n_a is None else n_a, np.int64).reshape(M)
-        caps = [min(s.n_a, s.n_b) for s in soas] if conflict_caps is None else conflict_caps
-        self.conf_off = np.zeros(M + 1, np.int64)
-        np.cumsum(caps, out=self.conf_off[1:])
         self.n_sym = max([int(s.n_sym) for s in soas] + [1]) if n_sym is None else n_sym
+        self._upload_cols(soas)
+        self._alloc(M, [min(s.n_a, s.n_b) for s in soas] if conflict_caps is None else conflict_caps, tot, fill,
+                    lib().smx_compose_batch_workspace_bytes, M)
+        self._idx = [self._up(self.off), self._up(self.n_a), self._up(self.conf_off)]
+        self._call = lib().smx_compose_batch
+        self._arg = _abi.SmxBatch(M, tot if n_total is None else n_total, self.n_sym, self._idx[0].data_ptr(),
+                                  self._idx[1].data_ptr(), *[t.data_ptr() for t in self._in], self.order.data_ptr(),
+                                  self.addr.data_ptr(), self.file.data_ptr(), self.ctx.data_ptr(), self.conf.data_ptr(),
+                                  self._idx[2].data_ptr(), self.counts.data_ptr(), grid_cap)
 
-        def up(a, dt=None):
-            a = np.ascontiguousarray(a)
-            return torch.from_numpy(a.view(dt) if dt is not None else a).to(dev)
-
-        def col(name, dt, view):
-            parts = [np.ascontiguousarray(getattr(s, name)).astype(dt, copy=False) for s in soas]
-            return up(np.concatenate(parts) if parts else np.zeros(0, dt), view)
-
-        self._in = [col("kind", np.uint8, None), col("ts", np.uint64, np.int64), col("oid_hi", np.uint64, np.int64),
-                    col("oid_lo", np.uint64, np.int64), col("sym", np.uint32, np.int32), col("v0", np.int32, None),
-                    col("v1", np.int32, None)]
-        self._idx = [up(self.off), up(self.n_a), up(self.conf_off)]
-        f = 0 if fill is None else fill
-        self.order, self.addr, self.file, self.ctx = (
-            torch.full((max(tot, 1),), f, dtype=torch.int32, device=dev) for _ in range(4))
-        self.conf = torch.full((2 * int(self.conf_off[-1]) + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
-        self.counts = torch.full((2 * max(M, 1),), f, dtype=torch.int64, device=dev)
-        ws = C.c_size_t(0)
-        check(lib().smx_compose_batch_workspace_bytes(M, C.byref(ws)))
-        self.ws_bytes = ws.value
-        self.ws = torch.empty(max(ws.value, 1), dtype=torch.uint8, device=dev)
-        self._b = _abi.SmxBatch(M, tot if n_total is None else n_total, self.n_sym, self._idx[0].data_ptr(), self._idx[1].data_ptr(),
-                                *[t.data_ptr() for t in self._in], self.order.data_ptr(), self.addr.data_ptr(),
-                                self.file.data_ptr(), self.ctx.data_ptr(), self.conf.data_ptr(),
-                                self._idx[2].data_ptr(), self.counts.data_ptr(), grid_cap)
-
-    def run(self, stream=None) -> None:
-        """Enqueue one smx_compose_batch on `stream` (default: torch's current stream)."""
-        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
-        check(lib().smx_compose_batch(C.byref(self._b), self.ws.data_ptr(), self.ws_bytes, s.cuda_stream))
-
-    def raw(self) -> dict:
-        """Every output array as the device holds it (after a device sync), on the host."""
-        self.torch.cuda.synchronize(self.device)
-        return {k: getattr(self, k).cpu().numpy() for k in ("order", "addr", "file", "ctx", "conf", "counts")}
-
-    def results(self, raw: Optional[dict] = None):
-        """Per merge (order, addr, file, ctx, pairs) trimmed to its counts and its conflict
-        capacity, or its negative counts[2m] for a merge that failed."""
-        r = self.raw() if raw is None else raw
-        out = []
-        for m in range(self.n_merges):
-            k, nc = int(r["counts"][2 * m]), int(r["counts"][2 * m + 1])
-            if k < 0:
-                out.append(k)
-                continue
-            o, c = int(self.off[m]), int(self.conf_off[m])
-            nc = min(nc, int(self.conf_off[m + 1]) - c)
-            out.append(tuple(r[x][o: o + k] for x in ("order", "addr", "file", "ctx"))
-                       + (r["conf"][2 * c: 2 * (c + nc)].reshape(nc, 2),))
-        return out
+    def _start(self, m: int) -> int:
+        return int(self.off[m])
 
 
-class DeviceBatchShared:
+class DeviceBatchShared(_DeviceMany):
     """Device-resident inputs, outputs and workspace for repeated smx_compose_batch_shared
     calls on a SharedSoA (tests, tools/shared_probe.py).  The optional arguments reach the
     corners of the C ABI (include/smx.h smx_batch_shared):
@@ -296,80 +324,33 @@ class DeviceBatchShared:
     fill          every output word (results, conflict pairs, counts) starts as this value,
                   and CONF_GUARD such words follow the last merge's conflict region."""
 
-    CONF_GUARD = 64
-
     def __init__(self, ssoa, device: str = "cuda", shared_is_b: bool = False, conflict_caps=None, grid_cap: int = 0,
                  off=None, n_sym: Optional[int] = None, fill: Optional[int] = None,
                  n_total: Optional[int] = None) -> None:
-        torch = _torch()
-        self.torch = torch
-        dev = self.device = torch.device(device)
+        self._open(device)
         self.ssoa = ssoa
         M = self.n_merges = ssoa.n_merges
         S = self.n_shared = int(ssoa.n_shared)
         self.off = np.asarray(ssoa.off if off is None else off, np.int64).reshape(M + 1)
         tot = self.n_total = int(ssoa.n_total)
         lens = np.diff(np.asarray(ssoa.off, np.int64))
-        caps = np.minimum(lens, S) if conflict_caps is None else conflict_caps
-        self.conf_off = np.zeros(M + 1, np.int64)
-        np.cumsum(caps, out=self.conf_off[1:])
         self.n_sym = int(ssoa.n_sym) if n_sym is None else n_sym
         self.n_out = tot - S + M * S
-
-        def up(a, dt=None):
-            a = np.ascontiguousarray(a)
-            return torch.from_numpy(a.view(dt) if dt is not None else a).to(dev)
-
-        def col(name, dt, view):
-            return up(np.ascontiguousarray(getattr(ssoa, name)).astype(dt, copy=False), view)
-
-        self._in = [col("kind", np.uint8, None), col("ts", np.uint64, np.int64), col("oid_hi", np.uint64, np.int64),
-                    col("oid_lo", np.uint64, np.int64), col("sym", np.uint32, np.int32), col("v0", np.int32, None),
-                    col("v1", np.int32, None)]
-        self._idx = [up(self.off), up(self.conf_off)]
-        f = 0 if fill is None else fill
-        self.order, self.addr, self.file, self.ctx = (
-            torch.full((max(self.n_out, 1),), f, dtype=torch.int32, device=dev) for _ in range(4))
-        self.conf = torch.full((2 * int(self.conf_off[-1]) + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
-        self.counts = torch.full((2 * max(M, 1),), f, dtype=torch.int64, device=dev)
-        ws = C.c_size_t(0)
-        check(lib().smx_compose_batch_shared_workspace_bytes(M, C.byref(ws)))
-        self.ws_bytes = ws.value
-        self.ws = torch.empty(max(ws.value, 1), dtype=torch.uint8, device=dev)
-        self._b = _abi.SmxBatchShared(M, tot if n_total is None else n_total, self.n_sym, S, self._idx[0].data_ptr(),
-                                      *[t.data_ptr() for t in self._in], self.order.data_ptr(), self.addr.data_ptr(),
-                                      self.file.data_ptr(), self.ctx.data_ptr(), self.conf.data_ptr(),
-                                      self._idx[1].data_ptr(), self.counts.data_ptr(), grid_cap, int(shared_is_b))
+        self._upload_cols([ssoa])
+        self._alloc(M, np.minimum(lens, S) if conflict_caps is None else conflict_caps, self.n_out, fill,
+                    lib().smx_compose_batch_shared_workspace_bytes, M)
+        self._idx = [self._up(self.off), self._up(self.conf_off)]
+        self._call = lib().smx_compose_batch_shared
+        self._arg = _abi.SmxBatchShared(M, tot if n_total is None else n_total, self.n_sym, S, self._idx[0].data_ptr(),
+                                        *[t.data_ptr() for t in self._in], self.order.data_ptr(), self.addr.data_ptr(),
+                                        self.file.data_ptr(), self.ctx.data_ptr(), self.conf.data_ptr(),
+                                        self._idx[1].data_ptr(), self.counts.data_ptr(), grid_cap, int(shared_is_b))
 
     def slot(self, m: int) -> int:
         """r(m): where merge m's results start in order / addr / file / ctx."""
         return int(self.off[m]) + (m - 1) * self.n_shared
 
-    def run(self, stream=None) -> None:
-        """Enqueue one smx_compose_batch_shared on `stream` (default: torch's current stream)."""
-        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
-        check(lib().smx_compose_batch_shared(C.byref(self._b), self.ws.data_ptr(), self.ws_bytes, s.cuda_stream))
-
-    def raw(self) -> dict:
-        """Every output array as the device holds it (after a device sync), on the host."""
-        self.torch.cuda.synchronize(self.device)
-        return {k: getattr(self, k).cpu().numpy() for k in ("order", "addr", "file", "ctx", "conf", "counts")}
-
-    def results(self, raw: Optional[dict] = None):
-        """Per merge (order, addr, file, ctx, pairs) trimmed to its counts and its conflict
-        capacity, or its negative counts[2m] for a merge that failed."""
-        r = self.raw() if raw is None else raw
-        out = []
-        for m in range(self.n_merges):
-            k, nc = int(r["counts"][2 * m]), int(r["counts"][2 * m + 1])
-            if k < 0:
-                out.append(k)
-                continue
-            o, c = self.slot(m), int(self.conf_off[m])
-            nc = min(nc, int(self.conf_off[m + 1]) - c)
-            out.append(tuple(r[x][o: o + k] for x in ("order", "addr", "file", "ctx"))
-                       + (r["conf"][2 * c: 2 * (c + nc)].reshape(nc, 2),))
-        return out
+    _start = slot
 
 
 def _rename_counts(kind, log_off) -> np.ndarray:
@@ -379,7 +360,7 @@ def _rename_counts(kind, log_off) -> np.ndarray:
     return np.maximum(csum[off[1:]] - csum[off[:-1]], 0)
 
 
-class DeviceScreen:
+class DeviceScreen(_DeviceMany):
     """Device-resident inputs, outputs and workspace for repeated smx_screen calls on a
     LogsSoA and a list of (i, j) pairs (tests, tools/screen_probe.py).  The optional
     arguments reach the corners of the C ABI (include/smx.h smx_screen):
@@ -391,13 +372,12 @@ class DeviceScreen:
     fill          every output word (conflict pairs, counts) starts as this value, and
                   CONF_GUARD such words follow the last pair's conflict region."""
 
-    CONF_GUARD = 64
+    _OUT = ("conf", "counts")
+    _PER = 1
 
     def __init__(self, lsoa, pairs, device: str = "cuda", conflict_caps=None, grid_cap: int = 0, log_off=None,
                  n_total: Optional[int] = None, fill: Optional[int] = None) -> None:
-        torch = _torch()
-        self.torch = torch
-        dev = self.device = torch.device(device)
+        self._open(device)
         self.lsoa = lsoa
         L = self.n_logs = lsoa.n_logs
         self.pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
@@ -412,59 +392,34 @@ class DeviceScreen:
             caps = np.where(ok, np.minimum(ren[pa], ren[pb]), 0) if L else np.zeros(P, np.int64)
         else:
             caps = np.zeros(P, np.int64) if self.null_conf else conflict_caps
-        self.conf_off = np.zeros(P + 1, np.int64)
-        np.cumsum(caps, out=self.conf_off[1:])
-
-        def up(a, dt=None):
-            a = np.ascontiguousarray(a)
-            return torch.from_numpy(a.view(dt) if dt is not None else a).to(dev)
-
-        def col(name, dt, view):
-            return up(np.ascontiguousarray(getattr(lsoa, name)).astype(dt, copy=False), view)
-
-        self._in = [col("kind", np.uint8, None), col("ts", np.uint64, np.int64), col("oid_hi", np.uint64, np.int64),
-                    col("oid_lo", np.uint64, np.int64), col("sym", np.uint32, np.int32), col("v0", np.int32, None)]
-        self._idx = [up(self.log_off), up(self.pairs[:, 0]), up(self.pairs[:, 1]), up(self.conf_off)]
-        f = 0 if fill is None else fill
-        self.conf = torch.full((2 * int(self.conf_off[-1]) + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
-        self.counts = torch.full((max(P, 1),), f, dtype=torch.int64, device=dev)
-        ws = C.c_size_t(0)
-        check(lib().smx_screen_workspace_bytes(L, tot, P, C.byref(ws)))
-        self.ws_bytes = ws.value
-        self.ws = torch.empty(max(ws.value, 1), dtype=torch.uint8, device=dev)
-        self._s = _abi.SmxScreen(L, tot if n_total is None else n_total, P, self._idx[0].data_ptr(),
-                                 *[_ptr(t) for t in self._in], _ptr(self._idx[1]), _ptr(self._idx[2]),
-                                 0 if self.null_conf else self.conf.data_ptr(),
-                                 0 if self.null_conf else self._idx[3].data_ptr(), self.counts.data_ptr(), grid_cap)
-
-    def run(self, stream=None) -> None:
-        """Enqueue one smx_screen on `stream` (default: torch's current stream)."""
-        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
-        check(lib().smx_screen(C.byref(self._s), self.ws.data_ptr(), self.ws_bytes, s.cuda_stream))
-
-    def raw(self) -> dict:
-        """Every output array as the device holds it (after a device sync), on the host."""
-        self.torch.cuda.synchronize(self.device)
-        return {k: getattr(self, k).cpu().numpy() for k in ("conf", "counts")}
-
-    def results(self, raw: Optional[dict] = None):
-        """Per pair its conflict pairs trimmed to its count and its capacity, or its negative
-        counts[p] for a pair that failed."""
-        r = self.raw() if raw is None else raw
-        out = []
-        for p in range(self.n_pairs):
-            nc = int(r["counts"][p])
-            if nc < 0:
-                out.append(nc)
-                continue
-            c = int(self.conf_off[p])
-            nc = min(nc, int(self.conf_off[p + 1]) - c)
-            out.append(r["conf"][2 * c: 2 * (c + nc)].reshape(nc, 2))
-        return out
+        self._upload_cols([lsoa], 6)  # (no v1)
+        self._alloc(P, caps, 0, fill, lib().smx_screen_workspace_bytes, L, tot, P)
+        self._idx = [self._up(self.log_off), self._up(self.pairs[:, 0]), self._up(self.pairs[:, 1]),
+                     self._up(self.conf_off)]
+        self._call = lib().smx_screen
+        self._arg = _abi.SmxScreen(L, tot if n_total is None else n_total, P, self._idx[0].data_ptr(),
+                                   *[_ptr(t) for t in self._in], _ptr(self._idx[1]), _ptr(self._idx[2]),
+                                   0 if self.null_conf else self.conf.data_ptr(),
+                                   0 if self.null_conf else self._idx[3].data_ptr(), self.counts.data_ptr(), grid_cap)
 
 
 def _al(x: int) -> int:
     return (x + 255) & ~255
+
+
+def _pack(hin, h0: int, col, at: int, nbytes: int) -> None:
+    """`col` (nbytes long) into the pinned staging area `hin` (at address h0) at byte `at`,
+    unless it is that very memory: a column marshalled into staging*() is in place already."""
+    if not (isinstance(col, np.ndarray) and col.ctypes.data == h0 + at and col.nbytes == nbytes):
+        hin[at: at + nbytes] = np.ascontiguousarray(col).view(np.uint8).reshape(-1)
+
+
+def _sliced(hout, q: int, start: int, k: int, conf_at: int, nc: int):
+    """One merge's results in the output staging area `hout`: k entries from entry `start` of
+    each of the four arrays (q bytes apart), and nc conflict pairs from byte conf_at."""
+    a, b = 4 * start, 4 * (start + k)
+    return (hout[a: b].view(np.int32), hout[q + a: q + b].view(np.int32), hout[2 * q + a: 2 * q + b].view(np.int32),
+            hout[3 * q + a: 3 * q + b].view(np.int32), hout[conf_at: conf_at + 8 * nc].view(np.int32).reshape(nc, 2))
 
 
 class ComposeSession:
@@ -518,6 +473,17 @@ class ComposeSession:
         if grown:  # new buffers come from the current stream's pool: ready before the session's stream uses them
             torch.cuda.synchronize(self.device)
 
+    def _copy_in(self, st, nbytes: int) -> None:
+        _hip_check(_hiprt().hipMemcpyAsync(self.d_in.data_ptr(), self.h_in.data_ptr(), nbytes, 1, st),
+                   "hipMemcpyAsync (inputs)")
+
+    def _copy_back(self, st, nbytes: int) -> None:
+        """The first nbytes of the outputs to the host, and the stream sync that ends a merge."""
+        hip = _hiprt()
+        _hip_check(hip.hipMemcpyAsync(self.h_out.data_ptr(), self.d_out.data_ptr(), nbytes, 2, st),
+                   "hipMemcpyAsync (outputs)")
+        _hip_check(hip.hipStreamSynchronize(st), "hipStreamSynchronize")
+
     def compose(self, soa: SoA, copy: bool = True):
         """(order, addr, file, ctx, conflict_pairs) of one merge, computed on the GPU.
         copy=False: views of the session's pinned staging area, valid until its next merge
@@ -536,15 +502,12 @@ class ComposeSession:
         d0 = self.d_in.data_ptr()
         h0 = hin.ctypes.data
         for name, w in self._IN:   # pack the columns into the pinned staging area (laid out for n)
-            col = getattr(soa, name)
-            if not (isinstance(col, np.ndarray) and col.ctypes.data == h0 + off and col.nbytes == n * w):
-                hin[off: off + n * w] = np.ascontiguousarray(col).view(np.uint8).reshape(-1)
-            ptrs[name] = d0 + off  # (a column marshalled into staging() is in place already)
+            _pack(hin, h0, getattr(soa, name), off, n * w)
+            ptrs[name] = d0 + off
             off += _al(n * w)
         t1 = time.perf_counter()
-        hip = _hiprt()
         st = self.stream.cuda_stream
-        _hip_check(hip.hipMemcpyAsync(d0, self.h_in.data_ptr(), off, 1, st), "hipMemcpyAsync (inputs)")
+        self._copy_in(st, off)
         ccap = max(min(soa.n_a, soa.n_b), 1)
         o0 = self.d_out.data_ptr()
         q = _al(n * 4)             # outputs laid out for n: one contiguous copy back
@@ -556,8 +519,7 @@ class ComposeSession:
         hout = self.h_out.numpy()
 
         def copy_back():
-            _hip_check(hip.hipMemcpyAsync(self.h_out.data_ptr(), o0, cnt_off + 16, 2, st), "hipMemcpyAsync (outputs)")
-            _hip_check(hip.hipStreamSynchronize(st), "hipStreamSynchronize")
+            self._copy_back(st, cnt_off + 16)
             return (int(x) for x in hout[cnt_off: cnt_off + 16].view(np.int64))
         if n < self.ASYNC_MAX:
             # merges below the early-verdict size: the asynchronous part, the copy back and
@@ -576,37 +538,104 @@ class ComposeSession:
             raise SmxError(-1, "invalid input: sym >= n_sym or kind >= 18")
         if nc > ccap:
             raise SmxError(-2, f"{nc} conflicts exceed capacity {ccap}")
-        res = tuple(hout[i * q: i * q + 4 * k].view(np.int32) for i in range(4))
-        pairs = hout[4 * q: 4 * q + 8 * nc].view(np.int32).reshape(nc, 2)
+        res = _sliced(hout, q, 0, k, 4 * q, nc)
         if copy:
-            res, pairs = tuple(x.copy() for x in res), pairs.copy()
+            res = tuple(x.copy() for x in res)
         self.last = {"pack_s": t1 - t0, "device_s": t2 - t1, "unpack_s": time.perf_counter() - t2}
-        return res + (pairs,)
+        return res
 
+    # -- the batched calls: one layout, one staged call, one unpack, one fallback ------------
 
-    # -- batched compose (smx_compose_batch): many small merges, one launch sequence --------
-
-    def _batch_layout(self, ns):
-        """Byte offsets of a batch of merges of ns ops in the staging areas: the input
-        columns for sum(ns) ops, then off / n_a / conf_off; the four outputs, the conflict
-        pairs (at most sum(ns) / 2) and the counts."""
-        m, tot = len(ns), int(sum(ns))
-        lay, o = {"n_total": tot}, 0
-        for name, w in self._IN:
+    @staticmethod
+    def _layout(n_total: int, segments, q: int, conf_bytes: int, counts_bytes: int) -> dict:
+        """Byte offsets in the staging areas.  In: the (name, nbytes) segments one after
+        another, each 256-byte aligned.  Out: four result arrays of q bytes each (0: none),
+        the conflict pairs (conf_bytes, and 8 more so that the region is never empty) and
+        the counts."""
+        lay, o = {"n_total": n_total}, 0
+        for name, nbytes in segments:
             lay[name] = o
-            o += _al(tot * w)
-        for name, cnt in (("off", m + 1), ("n_a", m), ("conf_off", m + 1)):
-            lay[name] = o
-            o += _al(cnt * 8)
+            o += _al(nbytes)
         lay["in_bytes"] = o
-        q = _al(tot * 4)
-        lay["q"], lay["conf"], lay["counts"] = q, 4 * q, 4 * q + _al(4 * tot + 8)
-        lay["out_bytes"] = lay["counts"] + 16 * m
+        lay["conf"], lay["counts"] = 4 * q, 4 * q + _al(conf_bytes + 8)
+        lay["out_bytes"] = lay["counts"] + counts_bytes
         return lay
 
     def _ensure_batch(self, lay, ws_bytes: int) -> None:
         # (_ensure sizes the areas per op: 37 input bytes and 20 output bytes each at least)
         self._ensure(max(-(-lay["in_bytes"] // 37), -(-lay["out_bytes"] // 20)), ws_bytes)
+
+    def _staged_call(self, query, sizes, lay, cols, index, make_arg, fn):
+        """One batched call through the staging areas: the workspace `query(*sizes)` asks
+        for, the columns `cols` ((name, column, byte offset, nbytes)) and the index arrays
+        `index` ((name, array)) packed at their places in `lay`, one host-to-device copy,
+        fn(make_arg(d_in address, d_out address)), one copy back, one stream sync.  Returns
+        the times after the pack and after the sync."""
+        import time
+        ws = C.c_size_t(0)
+        check(query(*sizes, C.byref(ws)))
+        self._ensure_batch(lay, ws.value)
+        hin = self.h_in.numpy()
+        h0 = hin.ctypes.data
+        for col, at, nbytes in cols:
+            _pack(hin, h0, col, at, nbytes)
+        for name, arr in index:
+            _pack(hin, h0, arr, lay[name], arr.nbytes)
+        t1 = time.perf_counter()
+        st = self.stream.cuda_stream
+        self._copy_in(st, lay["in_bytes"])
+        arg = make_arg(self.d_in.data_ptr(), self.d_out.data_ptr())
+        check(fn(C.byref(arg), self.ws.data_ptr(), ws.value, st))
+        self._copy_back(st, lay["out_bytes"])
+        return t1, time.perf_counter()
+
+    def _batch_results(self, lay, conf_off, starts, labels):
+        """Per merge of a batch that ran: its results (views of the output staging area,
+        from entry starts[m] of the four arrays), or None for a merge the library sent back
+        (counts -2).  labels[m] names merge m in an error."""
+        hout = self.h_out.numpy()
+        counts = hout[lay["counts"]: lay["counts"] + 16 * len(labels)].view(np.int64).tolist()
+        q, conf, co, starts = lay["q"], lay["conf"], conf_off.tolist(), starts.tolist()
+        res = []
+        for m, i in enumerate(labels):
+            k, nc = counts[2 * m], counts[2 * m + 1]
+            if k == -2:
+                res.append(None)
+                continue
+            if k < 0:
+                raise SmxError(-1, f"merge {i}: invalid input: sym >= n_sym or kind >= 18")
+            if nc > co[m + 1] - co[m]:
+                raise SmxError(-2, f"merge {i}: {nc} conflicts exceed capacity {co[m + 1] - co[m]}")
+            res.append(_sliced(hout, q, starts[m], k, conf + 8 * co[m], nc))
+        return res
+
+    def _compose_routed(self, res, routed, soas, what: str, keep_last: bool = True) -> None:
+        """res[i] = compose(soa) for the items the batched call did not take; an error names
+        the item (`what` i).  keep_last: `last` stays the batched call's (the routed items'
+        legs are compose()'s own)."""
+        last = self.last
+        for i, soa in zip(routed, soas):
+            try:
+                res[i] = self.compose(soa)
+            except SmxError as e:
+                raise SmxError(e.code, f"{what} {i}: {e}") from None
+        if keep_last:
+            self.last = last
+
+    # -- batched compose (smx_compose_batch): many small merges, one launch sequence --------
+
+    @staticmethod
+    def _batch_layout(ns):
+        """Byte offsets of a batch of merges of ns ops in the staging areas: the input
+        columns for sum(ns) ops, then off / n_a / conf_off; the four outputs, the conflict
+        pairs (at most sum(ns) / 2) and the counts."""
+        m, tot = len(ns), int(sum(ns))
+        q = _al(tot * 4)
+        lay = ComposeSession._layout(tot, [(name, tot * w) for name, w in ComposeSession._IN]
+                                     + [("off", (m + 1) * 8), ("n_a", m * 8), ("conf_off", (m + 1) * 8)],
+                                     q, 4 * tot, 16 * m)
+        lay["q"] = q
+        return lay
 
     def staging_many(self, ns):
         """The input columns of a batch of merges of ns ops (each at most BATCH_MAX_OPS) as
@@ -635,83 +664,50 @@ class ComposeSession:
             M = len(small)
             ns = [soas[i].n for i in small]
             lay = self._batch_layout(ns)
-            ws = C.c_size_t(0)
-            check(lib().smx_compose_batch_workspace_bytes(M, C.byref(ws)))
-            self._ensure_batch(lay, ws.value)
-            hin, hout = self.h_in.numpy(), self.h_out.numpy()
-            h0 = hin.ctypes.data
             off = np.zeros(M + 1, np.int64)
             np.cumsum(ns, out=off[1:])
             n_a = np.fromiter((soas[i].n_a for i in small), np.int64, M)
             conf_off = np.zeros(M + 1, np.int64)
             np.cumsum(np.minimum(n_a, off[1:] - off[:-1] - n_a), out=conf_off[1:])  # min(n_a, n_b): never truncates
-            n_sym = 1
+            n_sym, cols = 1, []
             for m, i in enumerate(small):
                 soa, n = soas[i], ns[m]
                 n_sym = max(n_sym, int(soa.n_sym))
                 if n and int(np.max(soa.sym)) >= soa.n_sym:  # (the batch has one bound for all its merges)
                     raise SmxError(-1, f"merge {i}: invalid input: sym >= n_sym")
-                for name, w in self._IN:
-                    col, at = getattr(soa, name), lay[name] + int(off[m]) * w
-                    if not (isinstance(col, np.ndarray) and col.ctypes.data == h0 + at and col.nbytes == n * w):
-                        hin[at: at + n * w] = np.ascontiguousarray(col).view(np.uint8).reshape(-1)
-            for name, arr in (("off", off), ("n_a", n_a), ("conf_off", conf_off)):
-                hin[lay[name]: lay[name] + arr.nbytes] = arr.view(np.uint8)
-            hip = _hiprt()
-            st = self.stream.cuda_stream
-            d0, o0 = self.d_in.data_ptr(), self.d_out.data_ptr()
-            _hip_check(hip.hipMemcpyAsync(d0, self.h_in.data_ptr(), lay["in_bytes"], 1, st), "hipMemcpyAsync (inputs)")
+                cols += [(getattr(soa, name), lay[name] + int(off[m]) * w, n * w) for name, w in self._IN]
             q = lay["q"]
-            b = _abi.SmxBatch(M, lay["n_total"], n_sym, d0 + lay["off"], d0 + lay["n_a"],
-                              *[d0 + lay[name] for name, _ in self._IN],
-                              o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"], d0 + lay["conf_off"],
-                              o0 + lay["counts"], 0)
-            check(lib().smx_compose_batch(C.byref(b), self.ws.data_ptr(), ws.value, st))
-            _hip_check(hip.hipMemcpyAsync(self.h_out.data_ptr(), o0, lay["out_bytes"], 2, st), "hipMemcpyAsync (outputs)")
-            _hip_check(hip.hipStreamSynchronize(st), "hipStreamSynchronize")
-            counts = hout[lay["counts"]: lay["counts"] + 16 * M].view(np.int64)
-            keep = copy or bool(routed)
-            for m, i in enumerate(small):
-                k, nc = int(counts[2 * m]), int(counts[2 * m + 1])
-                if k == -2:
+            self._staged_call(
+                lib().smx_compose_batch_workspace_bytes, (M,), lay, cols,
+                (("off", off), ("n_a", n_a), ("conf_off", conf_off)),
+                lambda d0, o0: _abi.SmxBatch(M, lay["n_total"], n_sym, d0 + lay["off"], d0 + lay["n_a"],
+                                             *[d0 + lay[name] for name, _ in self._IN],
+                                             o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"],
+                                             d0 + lay["conf_off"], o0 + lay["counts"], 0),
+                lib().smx_compose_batch)
+            for i, r in zip(small, self._batch_results(lay, conf_off, off[:-1], small)):
+                res[i] = r
+                if r is None:
                     routed.append(i)
-                    keep = True
-                    continue
-                if k < 0:
-                    raise SmxError(-1, f"merge {i}: invalid input: sym >= n_sym or kind >= 18")
-                if nc > conf_off[m + 1] - conf_off[m]:
-                    raise SmxError(-2, f"merge {i}: {nc} conflicts exceed capacity {conf_off[m + 1] - conf_off[m]}")
-                o = 4 * int(off[m])
-                c = lay["conf"] + 8 * int(conf_off[m])
-                res[i] = tuple(hout[j * q + o: j * q + o + 4 * k].view(np.int32) for j in range(4)) + (
-                    hout[c: c + 8 * nc].view(np.int32).reshape(nc, 2),)
-            if keep:  # (compose() below reuses the staging area)
+            if copy or routed:  # (compose() below reuses the staging area)
                 res = [r if r is None else tuple(x.copy() for x in r) for r in res]
-        for i in sorted(routed):
-            try:
-                res[i] = self.compose(soas[i])
-            except SmxError as e:
-                raise SmxError(e.code, f"merge {i}: {e}") from None
+        routed.sort()
+        self._compose_routed(res, routed, [soas[i] for i in routed], "merge", keep_last=False)
         return res
 
     # -- batched compose against one shared log (smx_compose_batch_shared) -------------------
 
-    def _shared_layout(self, n_total: int, n_shared: int, m: int):
+    @staticmethod
+    def _shared_layout(n_total: int, n_shared: int, m: int):
         """Byte offsets of a shared-log batch in the staging areas: the input columns for
         n_total ops (the shared log once), then off / conf_off; the four outputs of
         n_total - n_shared + m * n_shared entries, the conflict pairs (at most
         n_total - n_shared) and the counts."""
-        lay, o = {"n_total": n_total}, 0
-        for name, w in self._IN:
-            lay[name] = o
-            o += _al(n_total * w)
-        for name in ("off", "conf_off"):
-            lay[name] = o
-            o += _al((m + 1) * 8)
-        lay["in_bytes"] = o
         q = _al((n_total - n_shared + m * n_shared) * 4)
-        lay["q"], lay["conf"], lay["counts"] = q, 4 * q, 4 * q + _al(8 * (n_total - n_shared) + 8)
-        lay["out_bytes"] = lay["counts"] + 16 * m
+        lay = ComposeSession._layout(n_total, [(name, n_total * w) for name, w in ComposeSession._IN]
+                                     + [("off", (m + 1) * 8), ("conf_off", (m + 1) * 8)],
+                                     q, 8 * (n_total - n_shared), 16 * m)
+        lay["q"] = q
         return lay
 
     def staging_shared(self, n_total: int, n_shared: int, n_merges: int) -> dict:
@@ -748,51 +744,23 @@ class ComposeSession:
                 at = o0 + int(np.argmax(sym[o0:o1] >= ssoa.n_sym))
                 raise SmxError(-1, f"merge {int(np.searchsorted(off, at, 'right')) - 1}: invalid input: sym >= n_sym")
         res = [None] * M
-        routed = []
         self.last = {"pack_s": 0.0, "device_s": 0.0, "unpack_s": 0.0, "in_bytes": 0}
         if M and (S + lens <= _abi.BATCH_MAX_OPS).any():
             lay = self._shared_layout(tot, S, M)
-            ws = C.c_size_t(0)
-            check(lib().smx_compose_batch_shared_workspace_bytes(M, C.byref(ws)))
-            self._ensure_batch(lay, ws.value)
-            hin, hout = self.h_in.numpy(), self.h_out.numpy()
-            h0 = hin.ctypes.data
             conf_off = np.zeros(M + 1, np.int64)
             np.cumsum(np.minimum(lens, S), out=conf_off[1:])  # min(n_a, n_b): never truncates
-            for name, w in self._IN:
-                col, at = getattr(ssoa, name), lay[name]
-                if not (isinstance(col, np.ndarray) and col.ctypes.data == h0 + at and col.nbytes == tot * w):
-                    hin[at: at + tot * w] = np.ascontiguousarray(col).view(np.uint8).reshape(-1)
-            for name, arr in (("off", off), ("conf_off", conf_off)):
-                hin[lay[name]: lay[name] + arr.nbytes] = arr.view(np.uint8)
-            t1 = time.perf_counter()
-            hip = _hiprt()
-            st = self.stream.cuda_stream
-            d0, o0 = self.d_in.data_ptr(), self.d_out.data_ptr()
-            _hip_check(hip.hipMemcpyAsync(d0, self.h_in.data_ptr(), lay["in_bytes"], 1, st), "hipMemcpyAsync (inputs)")
             q = lay["q"]
-            b = _abi.SmxBatchShared(M, tot, int(ssoa.n_sym), S, d0 + lay["off"],
-                                    *[d0 + lay[name] for name, _ in self._IN],
-                                    o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"], d0 + lay["conf_off"],
-                                    o0 + lay["counts"], 0, int(bool(shared_is_b)))
-            check(lib().smx_compose_batch_shared(C.byref(b), self.ws.data_ptr(), ws.value, st))
-            _hip_check(hip.hipMemcpyAsync(self.h_out.data_ptr(), o0, lay["out_bytes"], 2, st), "hipMemcpyAsync (outputs)")
-            _hip_check(hip.hipStreamSynchronize(st), "hipStreamSynchronize")
-            t2 = time.perf_counter()
-            counts = hout[lay["counts"]: lay["counts"] + 16 * M].view(np.int64)
-            for m in range(M):
-                k, nc = int(counts[2 * m]), int(counts[2 * m + 1])
-                if k == -2:
-                    routed.append(m)
-                    continue
-                if k < 0:
-                    raise SmxError(-1, f"merge {m}: invalid input: sym >= n_sym or kind >= 18")
-                if nc > conf_off[m + 1] - conf_off[m]:
-                    raise SmxError(-2, f"merge {m}: {nc} conflicts exceed capacity {conf_off[m + 1] - conf_off[m]}")
-                o = 4 * (int(off[m]) + (m - 1) * S)
-                c = lay["conf"] + 8 * int(conf_off[m])
-                res[m] = tuple(hout[j * q + o: j * q + o + 4 * k].view(np.int32) for j in range(4)) + (
-                    hout[c: c + 8 * nc].view(np.int32).reshape(nc, 2),)
+            t1, t2 = self._staged_call(
+                lib().smx_compose_batch_shared_workspace_bytes, (M,), lay,
+                [(getattr(ssoa, name), lay[name], tot * w) for name, w in self._IN],
+                (("off", off), ("conf_off", conf_off)),
+                lambda d0, o0: _abi.SmxBatchShared(M, tot, int(ssoa.n_sym), S, d0 + lay["off"],
+                                                   *[d0 + lay[name] for name, _ in self._IN],
+                                                   o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"],
+                                                   d0 + lay["conf_off"], o0 + lay["counts"], 0, int(bool(shared_is_b))),
+                lib().smx_compose_batch_shared)
+            res = self._batch_results(lay, conf_off, off[:-1] + (np.arange(M) - 1) * S, range(M))
+            routed = [m for m in range(M) if res[m] is None]
             if copy or routed:  # (compose() below reuses the staging area)
                 res = [r if r is None else tuple(x.copy() for x in r) for r in res]
             self.last = {"pack_s": t1 - t0, "device_s": t2 - t1, "unpack_s": time.perf_counter() - t2,
@@ -801,35 +769,22 @@ class ComposeSession:
             routed = list(range(M))
         if routed:
             # (copies: the columns may be views of the staging area that compose() packs into)
-            merges = [ssoa.merge(m, shared_is_b) for m in routed]
-            last = self.last
-            for m, soa in zip(routed, merges):
-                try:
-                    res[m] = self.compose(soa)
-                except SmxError as e:
-                    raise SmxError(e.code, f"merge {m}: {e}") from None
-            self.last = last  # (the batch's legs; the routed merges are compose()'s)
+            self._compose_routed(res, routed, [ssoa.merge(m, shared_is_b) for m in routed], "merge")
         return res
 
     # -- conflict screen (smx_screen): many pairs of logs stored once, conflicts only ---------
 
     _SCREEN_IN = _IN[:6]  # (no v1)
 
-    def _screen_layout(self, n_total: int, n_logs: int, n_pairs: int, n_conf: int = 0):
+    @staticmethod
+    def _screen_layout(n_total: int, n_logs: int, n_pairs: int, n_conf: int = 0):
         """Byte offsets of a screen in the staging areas: the six input columns for n_total
         ops, then log_off / pair_a / pair_b / conf_off; the conflict pairs and the counts."""
-        lay, o = {"n_total": n_total}, 0
-        for name, w in self._SCREEN_IN:
-            lay[name] = o
-            o += _al(n_total * w)
-        lay["col_bytes"] = o
-        for name, nbytes in (("log_off", (n_logs + 1) * 8), ("pair_a", n_pairs * 4), ("pair_b", n_pairs * 4),
-                             ("conf_off", (n_pairs + 1) * 8)):
-            lay[name] = o
-            o += _al(nbytes)
-        lay["in_bytes"] = o
-        lay["conf"], lay["counts"] = 0, _al(8 * n_conf + 8)
-        lay["out_bytes"] = lay["counts"] + 8 * n_pairs
+        lay = ComposeSession._layout(n_total, [(name, n_total * w) for name, w in ComposeSession._SCREEN_IN]
+                                     + [("log_off", (n_logs + 1) * 8), ("pair_a", n_pairs * 4),
+                                        ("pair_b", n_pairs * 4), ("conf_off", (n_pairs + 1) * 8)],
+                                     0, 8 * n_conf, 8 * n_pairs)
+        lay["col_bytes"] = lay["log_off"]
         return lay
 
     def staging_logs(self, n_total: int, n_logs: int, n_pairs: int) -> dict:
@@ -867,30 +822,16 @@ class ComposeSession:
         conf_off = np.zeros(P + 1, np.int64)
         np.cumsum(np.minimum(ren[pairs[:, 0]], ren[pairs[:, 1]]), out=conf_off[1:])  # never truncates
         lay = self._screen_layout(tot, L, P, int(conf_off[-1]))
-        ws = C.c_size_t(0)
-        check(lib().smx_screen_workspace_bytes(L, tot, P, C.byref(ws)))
-        self._ensure_batch(lay, ws.value)
-        hin, hout = self.h_in.numpy(), self.h_out.numpy()
-        h0 = hin.ctypes.data
-        for name, w in self._SCREEN_IN:
-            col, at = getattr(lsoa, name), lay[name]
-            if not (isinstance(col, np.ndarray) and col.ctypes.data == h0 + at and col.nbytes == tot * w):
-                hin[at: at + tot * w] = np.ascontiguousarray(col).view(np.uint8).reshape(-1)
-        for name, arr in (("log_off", log_off), ("pair_a", np.ascontiguousarray(pairs[:, 0])),
-                          ("pair_b", np.ascontiguousarray(pairs[:, 1])), ("conf_off", conf_off)):
-            hin[lay[name]: lay[name] + arr.nbytes] = arr.view(np.uint8)
-        t1 = time.perf_counter()
-        hip = _hiprt()
-        st = self.stream.cuda_stream
-        d0, o0 = self.d_in.data_ptr(), self.d_out.data_ptr()
-        _hip_check(hip.hipMemcpyAsync(d0, self.h_in.data_ptr(), lay["in_bytes"], 1, st), "hipMemcpyAsync (inputs)")
-        s = _abi.SmxScreen(L, tot, P, d0 + lay["log_off"], *[d0 + lay[name] for name, _ in self._SCREEN_IN],
-                           d0 + lay["pair_a"], d0 + lay["pair_b"], o0 + lay["conf"], d0 + lay["conf_off"],
-                           o0 + lay["counts"], 0)
-        check(lib().smx_screen(C.byref(s), self.ws.data_ptr(), ws.value, st))
-        _hip_check(hip.hipMemcpyAsync(self.h_out.data_ptr(), o0, lay["out_bytes"], 2, st), "hipMemcpyAsync (outputs)")
-        _hip_check(hip.hipStreamSynchronize(st), "hipStreamSynchronize")
-        t2 = time.perf_counter()
+        t1, t2 = self._staged_call(
+            lib().smx_screen_workspace_bytes, (L, tot, P), lay,
+            [(getattr(lsoa, name), lay[name], tot * w) for name, w in self._SCREEN_IN],
+            (("log_off", log_off), ("pair_a", pairs[:, 0]), ("pair_b", pairs[:, 1]), ("conf_off", conf_off)),
+            lambda d0, o0: _abi.SmxScreen(L, tot, P, d0 + lay["log_off"],
+                                          *[d0 + lay[name] for name, _ in self._SCREEN_IN],
+                                          d0 + lay["pair_a"], d0 + lay["pair_b"], o0 + lay["conf"],
+                                          d0 + lay["conf_off"], o0 + lay["counts"], 0),
+            lib().smx_screen)
+        hout = self.h_out.numpy()
         counts = hout[lay["counts"]: lay["counts"] + 8 * P].view(np.int64)
         bad = np.flatnonzero((counts < 0) & (counts != -2))
         if len(bad):
@@ -908,14 +849,9 @@ class ComposeSession:
                      "in_bytes": lay["in_bytes"], "out_bytes": lay["out_bytes"], "routed": len(routed)}
         if routed:
             # (copies: the columns may be views of the staging area that compose() packs into)
-            soas = [lsoa.pair(int(pairs[p, 0]), int(pairs[p, 1])) for p in routed]
-            last = self.last
-            for p, soa in zip(routed, soas):
-                try:
-                    res[p] = self.compose(soa)[4]
-                except SmxError as e:
-                    raise SmxError(e.code, f"pair {p}: {e}") from None
-            self.last = last  # (the screen's legs; the routed pairs are compose()'s)
+            self._compose_routed(res, routed, [lsoa.pair(int(pairs[p, 0]), int(pairs[p, 1])) for p in routed], "pair")
+            for p in routed:
+                res[p] = res[p][4]
         return res
 
 

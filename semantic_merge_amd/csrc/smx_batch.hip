@@ -1,0 +1,205 @@
+// smx_batch.hip — the batched entry points of include/smx.h: smx_compose_batch and
+// smx_compose_batch_shared (kernels in smx_batch.h) and smx_screen
+// (kernels in smx_screen.h).
+//
+// All three have one shape: a pre-pass sorts the items (merges, pairs) into three size
+// classes, then one kernel per class runs its list on a grid capped by what the device
+// holds at once.  That shape is here once: the residency cache (resident_of) and the
+// per-class launch (launch_classes).  Nothing here waits, allocates or reads back.
+#include <exception>
+
+// (the small kernel's phase stamps belong to the single merge: smx_compose.hip defines the
+// array and reads it, and the batch kernels compiled here keep none)
+#undef SMALL_STAMPS
+#include "smx_batch.h"
+#include "smx_screen.h"
+
+// The kernels with a residency-capped grid, and the threads of a workgroup of each.
+enum { R_BATCH = 0, R_SHARED = 3, R_EXTRACT = 6, R_SCREEN = 7, R_N = 10 };
+template <typename B>
+using BatchKernel = void (*)(B, const u32*, const u32*);
+template <typename B>
+static constexpr BatchKernel<B> kBatchKernels[BATCH_CLASSES] = {
+    k_compose_batch<batch_class_cap(0), B>, k_compose_batch<batch_class_cap(1), B>,
+    k_compose_batch<batch_class_cap(2), B>};
+typedef void (*ScreenKernel)(ScreenArgs, ScreenWs, const u32*, const u32*);
+static constexpr ScreenKernel kScreenKernels[SCREEN_CLASSES] = {
+    k_screen_pairs<screen_class_cap(0)>, k_screen_pairs<screen_class_cap(1)>, k_screen_pairs<screen_class_cap(2)>};
+static constexpr int kBatchCaps[BATCH_CLASSES] = {batch_class_cap(0), batch_class_cap(1), batch_class_cap(2)};
+static constexpr int kScreenCaps[SCREEN_CLASSES] = {screen_class_cap(0), screen_class_cap(1), screen_class_cap(2)};
+
+// Workgroups of each of those kernels that one device holds at once (the grid cap of its
+// launch): the runtime's occupancy figure for the kernel times the CU count, asked once
+// per device and host thread.
+static int resident_of(const int** out) {
+  struct Entry {
+    int dev = -1;
+    int wg[R_N] = {};
+  };
+  static thread_local Entry g[4];
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  Entry* e = &g[dev & 3];
+  if (e->dev != dev) {
+    const void* fn[R_N];
+    int threads[R_N];
+    for (int c = 0; c < BATCH_CLASSES; ++c) {
+      fn[R_BATCH + c] = (const void*)kBatchKernels<smx_batch>[c];
+      fn[R_SHARED + c] = (const void*)kBatchKernels<smx_batch_shared>[c];
+      threads[R_BATCH + c] = threads[R_SHARED + c] = kBatchCaps[c] / 2;
+    }
+    fn[R_EXTRACT] = (const void*)k_screen_extract;
+    threads[R_EXTRACT] = SCREEN_T1;
+    for (int c = 0; c < SCREEN_CLASSES; ++c) {
+      fn[R_SCREEN + c] = (const void*)kScreenKernels[c];
+      threads[R_SCREEN + c] = kScreenCaps[c] / 2;
+    }
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    for (int k = 0; k < R_N; ++k) {
+      int per = 0;
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn[k], threads[k], 0));
+      e->wg[k] = (per > 0 ? per : 1) * (cus > 0 ? cus : 1);
+    }
+    e->dev = dev;
+  }
+  *out = e->wg;
+  return SMX_OK;
+}
+
+// min(resident, items) workgroups, at most grid_cap when that is positive.
+static dim3 capped_grid(int resident, i64 items, i64 grid_cap) {
+  i64 g = resident < items ? (i64)resident : items;
+  if (grid_cap > 0 && g > grid_cap) g = grid_cap;
+  return dim3((unsigned)g);
+}
+
+// One kernel per size class: class c's kernel on cap[c] / 2 threads, with its count
+// cnt + c and its list lists + c * stride after the kernel's own arguments.
+template <typename K, typename... A>
+static int launch_classes(K* const (&kern)[3], const int (&cap)[3], const int* resident, i64 items, i64 grid_cap,
+                          hipStream_t st, const u32* cnt, const u32* lists, size_t stride, const A&... args) {
+  for (int c = 0; c < 3; ++c) {
+    hipLaunchKernelGGL(kern[c], capped_grid(resident[c], items, grid_cap), dim3(cap[c] / 2), 0, st, args..., cnt + c,
+                       lists + c * stride);
+    HIP_TRY(hipGetLastError());
+  }
+  return SMX_OK;
+}
+
+extern "C" int smx_compose_batch_workspace_bytes(int64_t n_merges, size_t* bytes) {
+  if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
+  if (n_merges < 0 || n_merges > 0x7fffffffll) return smx_set_error(SMX_E_ARG, "n_merges outside 0 .. 2^31 - 1");
+  *bytes = BATCH_HDR + BATCH_CLASSES * batch_list_bytes(n_merges);
+  return SMX_OK;
+}
+
+extern "C" int smx_compose_batch_shared_workspace_bytes(int64_t n_merges, size_t* bytes) {
+  return smx_compose_batch_workspace_bytes(n_merges, bytes);  // the same class counts and lists
+}
+
+// What the two batch structs are checked for alike, from n_sym's bound on; `index_ok`: the
+// struct's own index arrays are set, `index_names` names them.  (A batch of no merges is
+// valid whatever else it holds; batch_run returns at once on it.)
+template <typename B>
+static int batch_check_args(const B* b, bool index_ok, const char* index_names, const void* workspace,
+                            size_t workspace_bytes, const char* ws_query) {
+  if (b->n_sym > 0xffffffffll) return smx_set_error(SMX_E_ARG, "n_sym over 2^32 - 1");
+  if (b->n_merges == 0) return SMX_OK;
+  if (!index_ok || !b->conf_off || !b->counts || !b->conflicts)
+    return smx_set_error(SMX_E_ARG, (std::string("null ") + index_names + " / conf_off / counts / conflicts").c_str());
+  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1 || !b->order ||
+                         !b->addr || !b->file || !b->ctx))
+    return smx_set_error(SMX_E_ARG, "null column or result array");
+  if (!workspace || workspace_bytes < BATCH_HDR + BATCH_CLASSES * batch_list_bytes(b->n_merges))
+    return smx_set_error(SMX_E_WORKSPACE, (std::string("workspace too small (") + ws_query + ")").c_str());
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  return SMX_OK;
+}
+
+// k_batch_classify, then the three classes' k_compose_batch.
+template <typename B>
+static int batch_run(const B* b, int first, void* workspace, void* stream) {
+  if (b->n_merges == 0) return SMX_OK;
+  try {
+    const int* resident;
+    if (int rc = resident_of(&resident)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t stride = batch_list_bytes(b->n_merges) / 4;
+    u32* cnt = (u32*)workspace;
+    u32* lists = (u32*)((char*)workspace + BATCH_HDR);
+    hipLaunchKernelGGL(k_batch_classify<B>, dim3(1), dim3(256), 0, st, *b, cnt, lists, stride);
+    HIP_TRY(hipGetLastError());
+    return launch_classes(kBatchKernels<B>, kBatchCaps, resident + first, b->n_merges, b->grid_cap, st, cnt, lists,
+                          stride, *b);
+  } catch (const std::exception& e) {
+    return smx_set_error(SMX_E_HIP, e.what());
+  }
+}
+
+extern "C" int smx_compose_batch(const smx_batch* b, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!b) return smx_set_error(SMX_E_ARG, "null batch");
+  if (b->n_merges < 0 || b->n_merges > 0x7fffffffll || b->n_total < 0 || b->n_sym < 0 || b->grid_cap < 0)
+    return smx_set_error(SMX_E_ARG, "negative size");
+  if (int rc = batch_check_args(b, b->off && b->n_a, "off / n_a", workspace, workspace_bytes,
+                                "smx_compose_batch_workspace_bytes"))
+    return rc;
+  return batch_run(b, R_BATCH, workspace, stream);
+}
+
+extern "C" int smx_compose_batch_shared(const smx_batch_shared* b, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+  if (!b) return smx_set_error(SMX_E_ARG, "null batch");
+  if (b->n_merges < 0 || b->n_merges > 0x7fffffffll || b->n_total < 0 || b->n_sym < 0 || b->n_shared < 0 ||
+      b->grid_cap < 0)
+    return smx_set_error(SMX_E_ARG, "negative size");
+  if (b->n_shared > b->n_total) return smx_set_error(SMX_E_ARG, "n_shared over n_total");
+  if (b->shared_is_b != 0 && b->shared_is_b != 1) return smx_set_error(SMX_E_ARG, "shared_is_b is neither 0 nor 1");
+  if (int rc = batch_check_args(b, b->off != nullptr, "off", workspace, workspace_bytes,
+                                "smx_compose_batch_shared_workspace_bytes"))
+    return rc;
+  return batch_run(b, R_SHARED, workspace, stream);
+}
+
+extern "C" int smx_screen_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs, size_t* bytes) {
+  if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
+  if (n_logs < 0 || n_logs > 0x7fffffffll || n_pairs < 0 || n_pairs > 0x7fffffffll || n_total < 0)
+    return smx_set_error(SMX_E_ARG, "n_logs or n_pairs outside 0 .. 2^31 - 1, or n_total negative");
+  *bytes = screen_ws_bytes(n_logs, n_total, n_pairs);
+  return SMX_OK;
+}
+
+extern "C" int smx_screen(const struct smx_screen* s, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!s) return smx_set_error(SMX_E_ARG, "null screen");
+  if (s->n_logs < 0 || s->n_logs > 0x7fffffffll || s->n_pairs < 0 || s->n_pairs > 0x7fffffffll || s->n_total < 0 ||
+      s->grid_cap < 0)
+    return smx_set_error(SMX_E_ARG, "negative size");
+  if ((s->conflicts == nullptr) != (s->conf_off == nullptr))
+    return smx_set_error(SMX_E_ARG, "conflicts and conf_off are both null or both set");
+  if (s->n_pairs == 0 || s->n_logs == 0) return SMX_OK;
+  if (!s->log_off || !s->pair_a || !s->pair_b || !s->counts)
+    return smx_set_error(SMX_E_ARG, "null log_off / pair_a / pair_b / counts");
+  if (s->n_total > 0 && (!s->kind || !s->ts || !s->oid_hi || !s->oid_lo || !s->sym || !s->v0))
+    return smx_set_error(SMX_E_ARG, "null column");
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < screen_ws_bytes(s->n_logs, s->n_total, s->n_pairs))
+    return smx_set_error(SMX_E_WORKSPACE, "workspace too small or not 8-byte aligned (smx_screen_workspace_bytes)");
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  try {
+    const int* resident;
+    if (int rc = resident_of(&resident)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const ScreenWs w = screen_ws(workspace, s->n_logs, s->n_total, s->n_pairs);
+    hipLaunchKernelGGL(k_screen_logs, dim3(1), dim3(1024), 0, st, *s, w);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_extract, capped_grid(resident[R_EXTRACT], s->n_logs, s->grid_cap), dim3(SCREEN_T1), 0,
+                       st, *s, w);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_classify, dim3((unsigned)SMX_CEIL_DIV(s->n_pairs, (i64)SCREEN_CHUNK)), dim3(256), 0, st,
+                       *s, w);
+    HIP_TRY(hipGetLastError());
+    return launch_classes(kScreenKernels, kScreenCaps, resident + R_SCREEN, s->n_pairs, s->grid_cap, st, w.cnt, w.lists,
+                          w.list_stride, *s, w);
+  } catch (const std::exception& e) {
+    return smx_set_error(SMX_E_HIP, e.what());
+  }
+}

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 #include "../../include/smx.h"
 
 // Diagnostic build (-DSMX_DIAG=1, tools/build_variants.sh): environment knobs and the
@@ -308,3 +310,11 @@ __device__ __forceinline__ T block_excl_scan(T v, T* s, T* total) {
 
 // Records the thread-local error message returned by smx_last_error(); returns code.
 int smx_set_error(int code, const char* msg);
+
+// A failed HIP call ends the enclosing entry point: SMX_E_HIP, "<the call>: <HIP's text>".
+#define HIP_TRY(x)                                                                               \
+  do {                                                                                           \
+    hipError_t _e = (x);                                                                         \
+    if (_e != hipSuccess)                                                                        \
+      return smx_set_error(SMX_E_HIP, (std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); \
+  } while (0)

@@ -27,6 +27,9 @@
 //   tables      per-symbol last writers: bucket by symbol range, LDS max-reduce
 //   k_emit      compacted output of every op after the move block: order, addr,
 //               file, ctx
+// A merge of at most SMALL_N ops skips all of that: k_compose_small, one workgroup
+// (smx_small.h).  The entry points that take many merges or log pairs at once are a unit of
+// their own, smx_batch.hip.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -38,8 +41,6 @@
 #include "smx_sort.h"
 #include "smx_window.h"
 #include "smx_small.h"
-#include "smx_batch.h"
-#include "smx_screen.h"
 #include "smx_tables.h"
 
 
@@ -51,12 +52,6 @@ static int set_err(int code, const std::string& msg) {
   return code;
 }
 int smx_set_error(int code, const char* msg) { return set_err(code, msg ? msg : ""); }
-#define HIP_TRY(x)                                                                 \
-  do {                                                                             \
-    hipError_t _e = (x);                                                           \
-    if (_e != hipSuccess)                                                          \
-      return set_err(SMX_E_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 // gsort: the generic plan's sort and window planning; segsort: its segmented sort's
 // kernels alone (inside gsort); window_g: the generic window kernel; window: the
@@ -2730,6 +2725,13 @@ static int early_fail_of(int dev, EarlyFail* e) {
 #define SMX_SMALL 1  // merges of at most SMALL_N ops: one workgroup, one launch (k_compose_small)
 #endif
 
+// smx_compose's one-workgroup plan: the SMALL_N instance of smx_small.h (the header is
+// shared with the batch kernels' unit, so the kernel lives with its one launch)
+__global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_compose_out out, ComposeMeta* meta,
+                                                                u64* hrec, u64 hseq) {
+  compose_small<SMALL_N, true>(ops, out, meta, hrec, hseq);
+}
+
 // Largest merge (ops) the one-workgroup path takes (smx_set_small_limit; 0: never).
 static std::atomic<int64_t> g_small_max{SMX_SMALL ? SMALL_N : 0};
 // (symbol ids index the small kernel's hash table with 0xffffffff as its empty mark)
@@ -3294,227 +3296,6 @@ extern "C" int smx_compose(const smx_ops* ops, const smx_compose_out* out, void*
     return set_err(SMX_E_HIP, e.what());
   }
   return rc;
-}
-
-// Workgroups of each batch class that one device holds at once (the grid cap of its
-// launch): the runtime's occupancy figure for the instance times the CU count, asked once
-// per device and host thread.
-struct BatchGrid {
-  int dev = -1;
-  int wg[BATCH_CLASSES] = {};
-};
-template <typename K>
-static int batch_grid_fill(BatchGrid* g, K k0, K k1, K k2, const BatchGrid** out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  BatchGrid* e = &g[dev & 3];
-  if (e->dev != dev) {
-    int cus = 0, per[BATCH_CLASSES] = {};
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[0], k0, batch_class_cap(0) / 2, 0));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[1], k1, batch_class_cap(1) / 2, 0));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[2], k2, batch_class_cap(2) / 2, 0));
-    for (int c = 0; c < BATCH_CLASSES; ++c) e->wg[c] = (per[c] > 0 ? per[c] : 1) * (cus > 0 ? cus : 1);
-    e->dev = dev;
-  }
-  *out = e;
-  return SMX_OK;
-}
-static int batch_grid_of(const BatchGrid** out) {
-  static thread_local BatchGrid g[4];
-  return batch_grid_fill(g, k_compose_batch<batch_class_cap(0)>, k_compose_batch<batch_class_cap(1)>,
-                         k_compose_batch<batch_class_cap(2)>, out);
-}
-static int batch_shared_grid_of(const BatchGrid** out) {
-  static thread_local BatchGrid g[4];
-  return batch_grid_fill(g, k_compose_batch_shared<batch_class_cap(0)>, k_compose_batch_shared<batch_class_cap(1)>,
-                         k_compose_batch_shared<batch_class_cap(2)>, out);
-}
-
-extern "C" int smx_compose_batch_workspace_bytes(int64_t n_merges, size_t* bytes) {
-  if (!bytes) return set_err(SMX_E_ARG, "null bytes");
-  if (n_merges < 0 || n_merges > 0x7fffffffll) return set_err(SMX_E_ARG, "n_merges outside 0 .. 2^31 - 1");
-  *bytes = BATCH_HDR + BATCH_CLASSES * batch_list_bytes(n_merges);
-  return SMX_OK;
-}
-
-extern "C" int smx_compose_batch(const smx_batch* b, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!b) return set_err(SMX_E_ARG, "null batch");
-  if (b->n_merges < 0 || b->n_merges > 0x7fffffffll || b->n_total < 0 || b->n_sym < 0 || b->grid_cap < 0)
-    return set_err(SMX_E_ARG, "negative size");
-  if (b->n_sym > 0xffffffffll) return set_err(SMX_E_ARG, "n_sym over 2^32 - 1");
-  if (b->n_merges == 0) return SMX_OK;
-  if (!b->off || !b->n_a || !b->conf_off || !b->counts || !b->conflicts)
-    return set_err(SMX_E_ARG, "null off / n_a / conf_off / counts / conflicts");
-  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1 || !b->order ||
-                         !b->addr || !b->file || !b->ctx))
-    return set_err(SMX_E_ARG, "null column or result array");
-  const size_t stride = batch_list_bytes(b->n_merges);
-  if (!workspace || workspace_bytes < BATCH_HDR + BATCH_CLASSES * stride)
-    return set_err(SMX_E_WORKSPACE, "workspace too small (smx_compose_batch_workspace_bytes)");
-  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
-  try {
-    const BatchGrid* G;
-    if (int rc = batch_grid_of(&G)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    u32* cnt = (u32*)workspace;
-    u32* lists = (u32*)((char*)workspace + BATCH_HDR);
-    hipLaunchKernelGGL(k_batch_classify, dim3(1), dim3(256), 0, st, *b, cnt, lists, stride / 4);
-    HIP_TRY(hipGetLastError());
-    auto grid = [&](int c) {
-      i64 g = G->wg[c] < b->n_merges ? (i64)G->wg[c] : b->n_merges;
-      if (b->grid_cap > 0 && g > b->grid_cap) g = b->grid_cap;
-      return dim3((unsigned)g);
-    };
-    hipLaunchKernelGGL(k_compose_batch<batch_class_cap(0)>, grid(0), dim3(batch_class_cap(0) / 2), 0, st, *b, cnt + 0,
-                       lists);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_compose_batch<batch_class_cap(1)>, grid(1), dim3(batch_class_cap(1) / 2), 0, st, *b, cnt + 1,
-                       lists + stride / 4);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_compose_batch<batch_class_cap(2)>, grid(2), dim3(batch_class_cap(2) / 2), 0, st, *b, cnt + 2,
-                       lists + 2 * (stride / 4));
-    HIP_TRY(hipGetLastError());
-  } catch (const std::exception& e) {
-    return set_err(SMX_E_HIP, e.what());
-  }
-  return SMX_OK;
-}
-
-extern "C" int smx_compose_batch_shared_workspace_bytes(int64_t n_merges, size_t* bytes) {
-  return smx_compose_batch_workspace_bytes(n_merges, bytes);  // the same class counts and lists
-}
-
-extern "C" int smx_compose_batch_shared(const smx_batch_shared* b, void* workspace, size_t workspace_bytes,
-                                        void* stream) {
-  if (!b) return set_err(SMX_E_ARG, "null batch");
-  if (b->n_merges < 0 || b->n_merges > 0x7fffffffll || b->n_total < 0 || b->n_sym < 0 || b->n_shared < 0 ||
-      b->grid_cap < 0)
-    return set_err(SMX_E_ARG, "negative size");
-  if (b->n_shared > b->n_total) return set_err(SMX_E_ARG, "n_shared over n_total");
-  if (b->shared_is_b != 0 && b->shared_is_b != 1) return set_err(SMX_E_ARG, "shared_is_b is neither 0 nor 1");
-  if (b->n_sym > 0xffffffffll) return set_err(SMX_E_ARG, "n_sym over 2^32 - 1");
-  if (b->n_merges == 0) return SMX_OK;
-  if (!b->off || !b->conf_off || !b->counts || !b->conflicts)
-    return set_err(SMX_E_ARG, "null off / conf_off / counts / conflicts");
-  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1 || !b->order ||
-                         !b->addr || !b->file || !b->ctx))
-    return set_err(SMX_E_ARG, "null column or result array");
-  const size_t stride = batch_list_bytes(b->n_merges);
-  if (!workspace || workspace_bytes < BATCH_HDR + BATCH_CLASSES * stride)
-    return set_err(SMX_E_WORKSPACE, "workspace too small (smx_compose_batch_shared_workspace_bytes)");
-  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
-  try {
-    const BatchGrid* G;
-    if (int rc = batch_shared_grid_of(&G)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    u32* cnt = (u32*)workspace;
-    u32* lists = (u32*)((char*)workspace + BATCH_HDR);
-    hipLaunchKernelGGL(k_batch_shared_classify, dim3(1), dim3(256), 0, st, *b, cnt, lists, stride / 4);
-    HIP_TRY(hipGetLastError());
-    auto grid = [&](int c) {
-      i64 g = G->wg[c] < b->n_merges ? (i64)G->wg[c] : b->n_merges;
-      if (b->grid_cap > 0 && g > b->grid_cap) g = b->grid_cap;
-      return dim3((unsigned)g);
-    };
-    hipLaunchKernelGGL(k_compose_batch_shared<batch_class_cap(0)>, grid(0), dim3(batch_class_cap(0) / 2), 0, st, *b,
-                       cnt + 0, lists);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_compose_batch_shared<batch_class_cap(1)>, grid(1), dim3(batch_class_cap(1) / 2), 0, st, *b,
-                       cnt + 1, lists + stride / 4);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_compose_batch_shared<batch_class_cap(2)>, grid(2), dim3(batch_class_cap(2) / 2), 0, st, *b,
-                       cnt + 2, lists + 2 * (stride / 4));
-    HIP_TRY(hipGetLastError());
-  } catch (const std::exception& e) {
-    return set_err(SMX_E_HIP, e.what());
-  }
-  return SMX_OK;
-}
-
-// Workgroups of k_screen_extract and of each screen class that one device holds at once.
-struct ScreenGrid {
-  int dev = -1;
-  int wg1 = 1;
-  int wg[SCREEN_CLASSES] = {};
-};
-static int screen_grid_of(const ScreenGrid** out) {
-  static thread_local ScreenGrid g[4];
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  ScreenGrid* e = &g[dev & 3];
-  if (e->dev != dev) {
-    int cus = 0, per1 = 0, per[SCREEN_CLASSES] = {};
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per1, k_screen_extract, SCREEN_T1, 0));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[0], k_screen_pairs<screen_class_cap(0)>,
-                                                         screen_class_cap(0) / 2, 0));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[1], k_screen_pairs<screen_class_cap(1)>,
-                                                         screen_class_cap(1) / 2, 0));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[2], k_screen_pairs<screen_class_cap(2)>,
-                                                         screen_class_cap(2) / 2, 0));
-    if (cus <= 0) cus = 1;
-    e->wg1 = (per1 > 0 ? per1 : 1) * cus;
-    for (int c = 0; c < SCREEN_CLASSES; ++c) e->wg[c] = (per[c] > 0 ? per[c] : 1) * cus;
-    e->dev = dev;
-  }
-  *out = e;
-  return SMX_OK;
-}
-
-extern "C" int smx_screen_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs, size_t* bytes) {
-  if (!bytes) return set_err(SMX_E_ARG, "null bytes");
-  if (n_logs < 0 || n_logs > 0x7fffffffll || n_pairs < 0 || n_pairs > 0x7fffffffll || n_total < 0)
-    return set_err(SMX_E_ARG, "n_logs or n_pairs outside 0 .. 2^31 - 1, or n_total negative");
-  *bytes = screen_ws_bytes(n_logs, n_total, n_pairs);
-  return SMX_OK;
-}
-
-extern "C" int smx_screen(const struct smx_screen* s, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!s) return set_err(SMX_E_ARG, "null screen");
-  if (s->n_logs < 0 || s->n_logs > 0x7fffffffll || s->n_pairs < 0 || s->n_pairs > 0x7fffffffll || s->n_total < 0 ||
-      s->grid_cap < 0)
-    return set_err(SMX_E_ARG, "negative size");
-  if ((s->conflicts == nullptr) != (s->conf_off == nullptr))
-    return set_err(SMX_E_ARG, "conflicts and conf_off are both null or both set");
-  if (s->n_pairs == 0 || s->n_logs == 0) return SMX_OK;
-  if (!s->log_off || !s->pair_a || !s->pair_b || !s->counts)
-    return set_err(SMX_E_ARG, "null log_off / pair_a / pair_b / counts");
-  if (s->n_total > 0 && (!s->kind || !s->ts || !s->oid_hi || !s->oid_lo || !s->sym || !s->v0))
-    return set_err(SMX_E_ARG, "null column");
-  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < screen_ws_bytes(s->n_logs, s->n_total, s->n_pairs))
-    return set_err(SMX_E_WORKSPACE, "workspace too small or not 8-byte aligned (smx_screen_workspace_bytes)");
-  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
-  try {
-    const ScreenGrid* G;
-    if (int rc = screen_grid_of(&G)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const ScreenWs w = screen_ws(workspace, s->n_logs, s->n_total, s->n_pairs);
-    auto grid = [&](int resident, i64 items) {
-      i64 g = resident < items ? (i64)resident : items;
-      if (s->grid_cap > 0 && g > s->grid_cap) g = s->grid_cap;
-      return dim3((unsigned)g);
-    };
-    hipLaunchKernelGGL(k_screen_logs, dim3(1), dim3(1024), 0, st, *s, w);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_screen_extract, grid(G->wg1, s->n_logs), dim3(SCREEN_T1), 0, st, *s, w);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_screen_classify, dim3((unsigned)SMX_CEIL_DIV(s->n_pairs, (i64)SCREEN_CHUNK)), dim3(256), 0, st,
-                       *s, w);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_screen_pairs<screen_class_cap(0)>, grid(G->wg[0], s->n_pairs), dim3(screen_class_cap(0) / 2), 0,
-                       st, *s, w, w.cnt + 0, w.lists);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_screen_pairs<screen_class_cap(1)>, grid(G->wg[1], s->n_pairs), dim3(screen_class_cap(1) / 2), 0,
-                       st, *s, w, w.cnt + 1, w.lists + w.list_stride);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_screen_pairs<screen_class_cap(2)>, grid(G->wg[2], s->n_pairs), dim3(screen_class_cap(2) / 2), 0,
-                       st, *s, w, w.cnt + 2, w.lists + 2 * w.list_stride);
-    HIP_TRY(hipGetLastError());
-  } catch (const std::exception& e) {
-    return set_err(SMX_E_HIP, e.what());
-  }
-  return SMX_OK;
 }
 
 extern "C" int smx_last_plan(void) { return g_plan; }

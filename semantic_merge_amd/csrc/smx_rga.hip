@@ -21,13 +21,6 @@
 
 #include "smx_scan.h"
 
-#define RGA_TRY(x)                                                                     \
-  do {                                                                                 \
-    hipError_t _e = (x);                                                               \
-    if (_e != hipSuccess)                                                              \
-      return smx_set_error(SMX_E_HIP, (std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); \
-  } while (0)
-
 // Event record, 2 u64 words, grouped by list by the partition below:
 //   w0 = anchor << 32 | t' >> 32   (t' = t with the sign bit flipped: order-preserving)
 //   w1 = value << 32 | op << 30 | event index   (index = creation order)
@@ -1629,8 +1622,8 @@ static int rga_impl(const smx_rga_ops* ops, const smx_rga_out* out, void* ws, si
     return smx_set_error(SMX_E_ARG, "bad sizes");
   if (!out || !out->out_offsets || !out->counts) return smx_set_error(SMX_E_ARG, "null output");
   if (n == 0) {
-    RGA_TRY(hipMemsetAsync(out->out_offsets, 0, (size_t)(nl + 1) * 8, st));
-    RGA_TRY(hipMemsetAsync(out->counts, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(out->out_offsets, 0, (size_t)(nl + 1) * 8, st));
+    HIP_TRY(hipMemsetAsync(out->counts, 0, 8, st));
     return SMX_OK;
   }
   if (nl < 1) return smx_set_error(SMX_E_ARG, "n_lists must be >= 1");
@@ -1659,11 +1652,11 @@ static int rga_impl(const smx_rga_ops* ops, const smx_rga_out* out, void* ws, si
   const smx_rga_ops o = *ops;
   const int grid = (int)(SMX_CEIL_DIV(n, (i64)BLOCK) < 8192 ? SMX_CEIL_DIV(n, (i64)BLOCK) : 8192);
 
-  RGA_TRY(hipMemsetAsync(err, 0, 32, st));
+  HIP_TRY(hipMemsetAsync(err, 0, 32, st));
   if (g_rr_grid == 0) {  // persistent scatter workgroups
     int dev = 0, cus = 0;
-    RGA_TRY(hipGetDevice(&dev));
-    RGA_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     g_cus = cus > 0 ? cus : 256;
     g_rr_grid = g_cus * RR_PER_CU;
   }
@@ -1735,15 +1728,15 @@ static int rga_impl(const smx_rga_ops* ops, const smx_rga_out* out, void* ws, si
     hipLaunchKernelGGL(k_rga_out_fused, dim3(SMX_CEIL_DIV(nl, (i64)(BLOCK / WAVE * RGA_OUT_LPW))), dim3(BLOCK), 0, st, tmp_v,
                        tmp_s, lstart, scnt, nl, *out, (const i32*)err);
   } else {
-    RGA_TRY((scan_excl<OpSum, u32, u32>(scnt, soff, nl, nullptr, part, totals, st)));
+    HIP_TRY((scan_excl<OpSum, u32, u32>(scnt, soff, nl, nullptr, part, totals, st)));
     hipLaunchKernelGGL(k_rga_out, dim3(SMX_CEIL_DIV(nl, (i64)(BLOCK / WAVE))), dim3(BLOCK), 0, st, tmp_v, tmp_s,
                        lstart, scnt, soff, nl, *out, (const i32*)err);
     hipLaunchKernelGGL(k_rga_fin, dim3(1), dim3(1), 0, st, totals, nl, *out, (const i32*)err);
   }
-  RGA_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   i32 herr = 0;
-  RGA_TRY(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
-  RGA_TRY(stream_wait(st));
+  HIP_TRY(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(stream_wait(st));
   if (herr & RGA_E_INPUT) return smx_set_error(SMX_E_ARG, "invalid input: list >= n_lists or op > 2");
   if (herr & RGA_E_UNGROUPED) return rga_impl(ops, out, ws, wsb, st, false);  // (not grouped after all)
   return SMX_OK;

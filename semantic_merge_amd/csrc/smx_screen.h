@@ -29,6 +29,7 @@
 //                      reference's `<=`), the position and next-rename arrays, and the wave
 //                      walk of smx_small.h step 2 without skip marks, chains and emit.
 // Nothing here waits, allocates or reads back: six launches on the caller's stream.
+// The entry point (argument checks, residency-capped grids, the launches) is in smx_batch.hip.
 #pragma once
 
 #include "smx_common.h"

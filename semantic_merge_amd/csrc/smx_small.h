@@ -50,10 +50,10 @@ constexpr int small_log2(int x) { return x <= 1 ? 0 : 1 + small_log2(x >> 1); }
 
 // One merge of at most N ops (a power of two, 128..SMALL_N) by the N / 2 threads of the
 // calling workgroup: two ops per thread, which the stable split by kind (1d) assumes.
-// SINGLE: smx_compose's call, which also fills the meta block and the verdict word; a
-// batch (smx_batch.h) calls it merge after merge with a barrier between two merges: every
-// piece of LDS state is set up again inside the call.  Invalid input writes counts -1 and
-// nothing else.
+// SINGLE: smx_compose's call (k_compose_small, smx_compose.hip), which also fills the meta
+// block and the verdict word; a batch (smx_batch.h) calls it merge after merge with a barrier
+// between two merges: every piece of LDS state is set up again inside the call.  Invalid
+// input writes counts -1 and nothing else.
 template <int N, bool SINGLE>
 __device__ __forceinline__ void compose_small(const smx_ops& ops, const smx_compose_out& out, ComposeMeta* meta,
                                               u64* hrec, u64 hseq) {
@@ -592,10 +592,4 @@ __device__ __forceinline__ void compose_small(const smx_ops& ops, const smx_comp
   __syncthreads();
   SMALL_STAMP(10);
 #endif
-}
-
-// smx_compose's one-workgroup plan: the SMALL_N instance
-__global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_compose_out out, ComposeMeta* meta,
-                                                                u64* hrec, u64 hseq) {
-  compose_small<SMALL_N, true>(ops, out, meta, hrec, hseq);
 }

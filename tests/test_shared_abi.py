@@ -3,38 +3,19 @@ the header's layout, the library exports the new symbols, and the argument error
 before any HIP call."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import pytest
 
 from semantic_merge_amd import _abi
 from semantic_merge_amd._lib import LIB_PATH
 
-HDR_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+from _util import assert_header_layout
+
 SMX_OK, SMX_E_ARG, SMX_E_WORKSPACE = 0, -1, -4
 
 
 def test_smx_batch_shared_matches_header():
-    py = _abi.SmxBatchShared
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "smx.h"', "int main(void) {",
-             'printf("size %zu\\n", sizeof(smx_batch_shared));']
-    for fname, _ in py._fields_:
-        lines.append(f'printf("{fname} %zu\\n", offsetof(smx_batch_shared, {fname}));')
-    lines.append("return 0; }")
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "l.c"), os.path.join(d, "l")
-        open(src, "w").write("\n".join(lines))
-        r = subprocess.run(["gcc", "-I", HDR_DIR, "-o", exe, src], capture_output=True, text=True)
-        if r.returncode != 0 and "not found" in r.stderr:
-            pytest.skip("no C compiler")
-        assert r.returncode == 0, r.stderr
-        out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")
-    got = {line.split()[0]: int(line.split()[1]) for line in filter(None, out)}
-    assert got.pop("size") == C.sizeof(py)
-    assert set(got) == {f for f, _ in py._fields_}
-    for fname, _ in py._fields_:
-        assert got[fname] == getattr(py, fname).offset, fname
+    assert_header_layout({"smx_batch_shared": _abi.SmxBatchShared})
 
 
 @pytest.fixture(scope="module")
