@@ -60,8 +60,8 @@ struct ComposeMeta {
   u64 n_win;                 // windows of the plan that ran
   u32 kmask[2];              // presorted plan: kinds present per branch (k_khist)
   u64 cs_done;               // k_cscan_mid blocks done (the last one writes base[])
-  u32 wk_done[2];            // k_boundary / k_replay_q blocks done (fused walk steps:
-                             // the last block runs the next single-block step, resets it)
+  u32 wk_done[2];            // unused (no kernel counts its blocks here any more); kept so that
+                             // the meta's size, which the kernels zero by, stays as it was
 };
 
 // Per-symbol final states (addr, file, ctx).  When the bit widths of (value + 1)
@@ -70,9 +70,6 @@ struct ComposeMeta {
 //   <= 48 bits: 6-byte entries, 21 per 128-byte line (6.1 MB at 2^20 symbols); one
 //               4-byte-aligned 8-byte load per lookup, never crossing a line
 //   <= 64 bits: 8-byte entries
-#ifndef SMX_FIN48
-#define SMX_FIN48 1
-#endif
 struct FinPack {
   u32 wa, wf;
   bool packed;  // 6- or 8-byte entries
@@ -83,7 +80,7 @@ __device__ __forceinline__ u32 bit_width32(u32 x) { return x ? 32u - (u32)__clz(
 
 __device__ __forceinline__ FinPack fin_pack_make(u32 wa, u32 wf, u32 wc, bool allow) {
   const bool packed = allow && wa + wf + wc <= 64;
-  return FinPack{wa, wf, packed, SMX_FIN48 && packed && wa + wf + wc <= 48};
+  return FinPack{wa, wf, packed, packed && wa + wf + wc <= 48};
 }
 
 __device__ __forceinline__ FinPack fin_pack_of(const u32* vbits, bool allow) {
@@ -143,20 +140,6 @@ __device__ __forceinline__ i64 xcd_item(i64 b, i64 n) {
 __device__ __forceinline__ u64 lanemask_lt() {
   const int lane = threadIdx.x & (WAVE - 1);
   return (lane == 0) ? 0ull : (~0ull >> (WAVE - lane));
-}
-
-// The kernel's argument block read through an opaque pointer: field loads are issued
-// where the pointer is taken, not hoisted to the kernel's start (where long-lived
-// scalars end up spilled to VGPR lanes in large kernels).
-template <class T>
-__device__ __forceinline__ const T* kernarg_late() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const T* p = (const T*)(const void*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return p;
-#else
-  return nullptr;
-#endif
 }
 
 __device__ __forceinline__ void wave_lds_sync() {  // LDS writes of this wave visible to its lanes

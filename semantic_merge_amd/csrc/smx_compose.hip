@@ -32,7 +32,6 @@
 // their own, smx_batch.hip.
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -230,16 +229,6 @@ __global__ void k_meta_init(ComposeMeta* meta) {
     for (int q = 0; q < 3; ++q) meta->key_and[s][q] = ~0ull;
 }
 
-#ifndef SMX_KHIST_LONG
-#define SMX_KHIST_LONG 1     // k_fpart flags timestamp groups longer than a window (from k_khist's samples)
-#endif
-#ifndef SMX_FPART_FAILCHK
-#define SMX_FPART_FAILCHK 0  // k_fpart skips its snap and writes on a failed plan (off: plan 0.135 -> 0.14 ms on config 3, profiles/r03_x/ab_plan_checks.txt)
-#endif
-#ifndef SMX_CSCAN_FAILCHK
-#define SMX_CSCAN_FAILCHK 0  // the chunk scans leave on a failed plan (off, as k_fpart)
-#endif
-
 // Presorted windows: boundary k sits at the merge-path split of diagonal k*tgt
 // (timestamps, A first on ties), snapped down to the first op of that timestamp on
 // both branches, so every (timestamp) group lands whole in one window.
@@ -260,7 +249,7 @@ __device__ __forceinline__ void fpart_body(const u64* __restrict__ ts, const u64
                                            i64 W, i64 tgt, i64 D, i64* __restrict__ bnd, ComposeMeta* meta,
                                            u32* long_host, i64 blk, i64 nblk, LongW lw = LongW{}) {
   const i64 k = blk * BLOCK + threadIdx.x;
-  bool chk = SMX_KHIST_LONG;
+  bool chk = true;  // flag timestamp groups longer than a window (from k_khist's samples)
   u64 fl = F_LONG;
   if (lw.tgt_w) {
     if ((__hip_atomic_load(&meta->f_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & F_LONG) == F_LONG) {
@@ -299,7 +288,6 @@ __device__ __forceinline__ void fpart_body(const u64* __restrict__ ts, const u64
     }
   }
   if (k > W) return;
-  const u64 failed = SMX_FPART_FAILCHK ? meta->f_fail : 0ull;  // (k_khist saw a group no window holds; used after the search)
   const i64 n = na + nb;
   const u64* A = ts;
   const u64* B = tsB;
@@ -331,7 +319,6 @@ __device__ __forceinline__ void fpart_body(const u64* __restrict__ ts, const u64
       else hi = mid;
     }
   }
-  if (failed) return;
   const i64 a = lo, b = d - lo;
   const u64 tau = (a < na && (b >= nb || A[a] <= B[b])) ? A[a] : B[b];
   // first index of each branch with ts >= tau: at or before the split
@@ -396,9 +383,6 @@ __global__ void k_gpart(const u64* __restrict__ sts, const u64* __restrict__ shi
 #define KH_NT 512                  // 32 chunks per block: a column's counts fill a 128-byte line
 #endif
 #define CH_PER_BLOCK (KH_NT / 16)   // 16 lanes x 16 kind bytes per 256-op chunk
-#ifndef KH_BF
-#define KH_BF 0                    // branch-free byte counting: plan 0.134 -> 0.137 ms (round 4); off
-#endif
 #ifndef KH_R
 #define KH_R 1                     // chunk rounds per block (4 measured slower: profiles/r02_k/khist_rounds_ab.txt)
 #endif
@@ -481,13 +465,12 @@ __global__ void __launch_bounds__(KH_NT) k_khist(const u8* __restrict__ kind, co
     u32 pk[3] = {0u, 0u, 0u};  // kind k: bits 5 * (k % 6) of word k / 6
 #pragma unroll
     for (int y = 0; y < 16; ++y) {
-      if (!KH_BF && y >= nv) break;
-      const bool ok = !KH_BF || y < nv;  // (branch-free: a lane past its chunk's end adds 0)
+      if (y >= nv) break;
       u32 k = (w[rd][y >> 2] >> (8 * (y & 3))) & 0xffu;
-      bad |= ok & (k >= SMX_N_KINDS);
+      bad |= k >= SMX_N_KINDS;
       k = k < SMX_N_KINDS ? k : SMX_N_KINDS - 1;
       const u32 wd = (k * 43u) >> 8;  // k / 6 for k < 18
-      const u32 inc = ok ? 1u << (5u * (k - 6u * wd)) : 0u;
+      const u32 inc = 1u << (5u * (k - 6u * wd));
       pk[0] += wd == 0 ? inc : 0u;
       pk[1] += wd == 1 ? inc : 0u;
       pk[2] += wd == 2 ? inc : 0u;
@@ -521,7 +504,7 @@ __global__ void __launch_bounds__(KH_NT) k_khist(const u8* __restrict__ kind, co
     lg |= (chkA[rd] && farA[rd] == smpA[rd]) || (chkB[rd] && farB[rd] == smpB[rd]);
   }
   // a sample equal to the one Dl chunks (one window capacity) later: that timestamp group
-  // alone overflows a window (k_fpart's test, SMX_KHIST_LONG); published below, once per
+  // alone overflows a window (k_fpart's test); published below, once per
   // block, and to the host by the one block whose atomic set it (thousands of waves
   // storing to the pinned flag over the bus slowed this kernel and its completion)
   if (__ballot(lg) && (threadIdx.x & (WAVE - 1)) == 0) atomicOr(&lgb, 1u);
@@ -563,120 +546,6 @@ __global__ void __launch_bounds__(KH_NT) k_khist(const u8* __restrict__ kind, co
   }
 }
 
-// k_khist as a persistent grid (KH_PERSIST): each block walks groups of CH_PER_BLOCK
-// chunks with the next group's kind bytes loaded before the current group is counted,
-// counts branch-free, and publishes the kinds present once at its end.
-#ifndef KH_PERSIST
-#define KH_PERSIST 0  // off: config 3 plan 0.134 -> 0.151 ms with it (profiles/r04_h/ab_c3.txt)
-#endif
-#define KH_BLOCKS_PER_CU 4
-__device__ __forceinline__ void kh_load(const u8* __restrict__ kind, const u64* __restrict__ ts, i64 na, i64 nb,
-                                        i64 bgap, i64 CA, i64 CB, i64 g, int q, u64* __restrict__ sA,
-                                        u64* __restrict__ sB, uint4* w, int* nv_o) {
-  const int side = g >= CA;
-  const i64 cc = side ? g - CA : g;
-  const i64 len = side ? nb : na;
-  const i64 r0 = cc * CH + q * 16;
-  const int nv = g < CA + CB ? (int)(len - r0 < 0 ? 0 : (len - r0 < 16 ? len - r0 : 16)) : 0;
-  *nv_o = nv;
-  const u8* src = kind + (side ? na + bgap : 0) + r0;
-  if (g < CA + CB) {
-    if (!side && q == 0) sA[cc] = ts[cc * CH];
-    if (side && q == 15 && nv == 16) sB[cc] = ts[na + bgap + cc * CH + CH - 1];
-  }
-  uint4 v = make_uint4(0u, 0u, 0u, 0u);
-  if (nv == 16 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-    v = *reinterpret_cast<const uint4*>(src);
-  } else {
-    u32 x[4] = {0u, 0u, 0u, 0u};
-    for (int y = 0; y < nv; ++y) x[y >> 2] |= (u32)src[y] << (8 * (y & 3));
-    v = make_uint4(x[0], x[1], x[2], x[3]);
-  }
-  *w = v;
-}
-__global__ void __launch_bounds__(KH_NT) k_khist2(const u8* __restrict__ kind, const u64* __restrict__ ts,
-                                                  i64 na, i64 nb, i64 bgap, i64 CM, u32* __restrict__ cnt,
-                                                  u64* __restrict__ sA, u64* __restrict__ sB, ComposeMeta* meta,
-                                                  u32* long_host) {
-  __shared__ u32 c[CH_PER_BLOCK][SMX_N_KINDS];
-  __shared__ u32 km[2];
-  const i64 CA = SMX_CEIL_DIV(na, (i64)CH), CB = SMX_CEIL_DIV(nb, (i64)CH);
-  const i64 ngrp = SMX_CEIL_DIV(CA + CB, (i64)CH_PER_BLOCK);
-  const int j = threadIdx.x / 16, q = threadIdx.x % 16;
-  if (threadIdx.x < 2) km[threadIdx.x] = 0;
-  u32 m0 = 0, m1 = 0;
-  bool bad = false;
-  i64 blk = blockIdx.x;
-  uint4 w;
-  int nv = 0;
-  if (blk < ngrp) kh_load(kind, ts, na, nb, bgap, CA, CB, blk * CH_PER_BLOCK + j, q, sA, sB, &w, &nv);
-  for (; blk < ngrp; blk += gridDim.x) {
-    const uint4 cw = w;
-    const int cnv = nv;
-    if (blk + gridDim.x < ngrp)  // the next group's bytes, in flight while this one is counted
-      kh_load(kind, ts, na, nb, bgap, CA, CB, (blk + gridDim.x) * CH_PER_BLOCK + j, q, sA, sB, &w, &nv);
-    const u32 ww[4] = {cw.x, cw.y, cw.z, cw.w};
-    u32 pk[3] = {0u, 0u, 0u};  // kind k: bits 5 * (k % 6) of word k / 6
-#pragma unroll
-    for (int y = 0; y < 16; ++y) {
-      const bool ok = y < cnv;
-      u32 k = (ww[y >> 2] >> (8 * (y & 3))) & 0xffu;
-      bad |= ok & (k >= SMX_N_KINDS);
-      k = k < SMX_N_KINDS ? k : SMX_N_KINDS - 1;
-      const u32 wd = (k * 43u) >> 8;  // k / 6 for k < 18
-      const u32 inc = ok ? 1u << (5u * (k - 6u * wd)) : 0u;
-      pk[0] += wd == 0 ? inc : 0u;
-      pk[1] += wd == 1 ? inc : 0u;
-      pk[2] += wd == 2 ? inc : 0u;
-    }
-    u32 f[6];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      f[2 * i] = (pk[i] & 31u) | ((pk[i] >> 5) & 31u) << 10 | ((pk[i] >> 10) & 31u) << 20;
-      f[2 * i + 1] = ((pk[i] >> 15) & 31u) | ((pk[i] >> 20) & 31u) << 10 | ((pk[i] >> 25) & 31u) << 20;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      u32 v = f[i];
-      v += dpp_u32<0x111, 0xf>(v);  // row_shr:1
-      v += dpp_u32<0x112, 0xf>(v);  // row_shr:2
-      v += dpp_u32<0x114, 0xf>(v);  // row_shr:4
-      v += dpp_u32<0x118, 0xf>(v);  // row_shr:8
-      f[i] = v;
-    }
-    if (q == 15) {
-#pragma unroll
-      for (int k = 0; k < SMX_N_KINDS; ++k) c[j][k] = (f[k / 3] >> (10 * (k % 3))) & 1023u;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < CH_PER_BLOCK * SMX_N_KINDS; i += KH_NT) {
-      const int jj = i % CH_PER_BLOCK, k = i / CH_PER_BLOCK;
-      const i64 gg = blk * CH_PER_BLOCK + jj;
-      if (gg >= CA + CB) continue;
-      const int sd = gg >= CA;
-      const u32 v = c[jj][k];
-      cnt[((i64)sd * SMX_N_KINDS + k) * CM + (sd ? gg - CA : gg)] = v;
-      if (v) (sd ? m1 : m0) |= 1u << k;
-    }
-    __syncthreads();  // (c is rewritten by the next group)
-  }
-  if (__ballot(bad) && (threadIdx.x & (WAVE - 1)) == 0) {
-    meta->bad_sym = 1;
-    if (long_host) __hip_atomic_store(long_host + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  m0 = wave_or_to_last(m0);
-  m1 = wave_or_to_last(m1);
-  if ((threadIdx.x & (WAVE - 1)) == WAVE - 1) {
-    if (m0) atomicOr(&km[0], m0);
-    if (m1) atomicOr(&km[1], m1);
-  }
-  __syncthreads();
-  if (threadIdx.x < 2 && km[threadIdx.x]) {
-    const u32 cur = __hip_atomic_load(&meta->kmask[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((cur | km[threadIdx.x]) != cur) atomicOr(&meta->kmask[threadIdx.x], km[threadIdx.x]);
-  }
-}
-
 __device__ __forceinline__ bool cs_present(const ComposeMeta* meta, int col) {
   return (meta->kmask[col >= SMX_N_KINDS] >> (col % SMX_N_KINDS)) & 1u;
 }
@@ -690,7 +559,7 @@ __global__ void __launch_bounds__(BLOCK) k_cscan_up(const u32* __restrict__ cnt,
                                                     i64 NT, u32* __restrict__ tsum, const ComposeMeta* meta) {
   __shared__ u32 s[NWAVES + 1];
   const int col = blockIdx.y;
-  if (!cs_present(meta, col) || (SMX_CSCAN_FAILCHK && meta->f_fail)) return;  // all-zero column: its prefixes are its counts
+  if (!cs_present(meta, col)) return;  // all-zero column: its prefixes are its counts
   const i64 C = SMX_CEIL_DIV(col >= SMX_N_KINDS ? nb : na, (i64)CH);
   const i64 t0 = (i64)blockIdx.x * CS_TILE;
   if (t0 >= C) return;
@@ -720,7 +589,6 @@ __global__ void __launch_bounds__(BLOCK) k_cscan_mid(u32* __restrict__ tsum, i64
                                                      u64 nwin_long) {
   __shared__ u32 s[NWAVES + 1];
   const int col = blockIdx.x;
-  if (SMX_CSCAN_FAILCHK && meta->f_fail) return;  // (k_khist saw a group no window holds)
   const int side = col / SMX_N_KINDS, k = col % SMX_N_KINDS;
   const i64 C = SMX_CEIL_DIV(side ? nb : na, (i64)CH);
   const i64 nt = cs_present(meta, col) ? SMX_CEIL_DIV(C, (i64)CS_TILE) : 0;  // (absent: total 0)
@@ -756,7 +624,7 @@ __global__ void __launch_bounds__(BLOCK) k_cscan_down(u32* __restrict__ cnt, i64
                                                       const u32* __restrict__ tsum, const ComposeMeta* meta) {
   __shared__ u32 s[NWAVES + 1];
   const int col = blockIdx.y;
-  if (!cs_present(meta, col) || (SMX_CSCAN_FAILCHK && meta->f_fail)) return;
+  if (!cs_present(meta, col)) return;
   const i64 C = SMX_CEIL_DIV(col >= SMX_N_KINDS ? nb : na, (i64)CH);
   const i64 t0 = (i64)blockIdx.x * CS_TILE;
   if (t0 >= C) return;
@@ -827,9 +695,6 @@ __device__ __forceinline__ void cscan_small_body(u32* __restrict__ cnt, i64 na, 
     }
   }
 }
-#ifndef SMX_FPART_CS
-#define SMX_FPART_CS 1  // small merges: k_fpart and k_cscan_small in one launch
-#endif
 __global__ void __launch_bounds__(BLOCK) k_cscan_small(u32* __restrict__ cnt, i64 na, i64 nb, i64 CM,
                                                        ComposeMeta* meta, u64 nwin, u64 nwin_long) {
   __shared__ u32 s[NWAVES + 1];
@@ -873,7 +738,7 @@ __global__ void __launch_bounds__(WC_NT) k_wcount(const u8* __restrict__ kind, c
                                                   u32* __restrict__ wcnt, ComposeMeta* meta) {
   __shared__ u32 c[NCNT];
   if (perm != nullptr && meta->f_fail) return;  // the segmented sort failed: perm is not written
-  const i64 w = SMX_XCD_WIN ? xcd_item(blockIdx.x, W) : (i64)blockIdx.x;  // (the window's gathers stay in one L2)
+  const i64 w = xcd_item(blockIdx.x, W);  // (the window's gathers stay in one L2)
   if (threadIdx.x < NCNT) c[threadIdx.x] = 0;
   __syncthreads();
   const i64 a0 = bnd[2 * w], b0 = bnd[2 * w + 1], a1 = bnd[2 * w + 2], b1 = bnd[2 * w + 3];
@@ -1066,31 +931,14 @@ struct EmitArgs {
   u64 hseq;
 };
 
-#ifndef SMX_EMIT_NT
-#define SMX_EMIT_NT 1
-#endif
-#ifndef SMX_EMIT_NTST
-#define SMX_EMIT_NTST 1
-#endif
 // Streams read once and outputs written once: non-temporal, so that they do not evict
 // the gathered final-state table from L2 (k_emit4's aligned 16-byte stores; plain ones
 // measured emit 0.753 -> 0.821 ms on config 3, profiles/r06/ab_c3_emit_stores.txt).  A
 // wave's outputs are an aligned range, so no line is shared between waves; the partial
 // stores at the range's ends are plain (round 2 measured non-temporal partial-line
 // stores 1.4-1.8x slower than plain ones, when ranges were not aligned).
-#if SMX_EMIT_NT
 #define NTLD(p) __builtin_nontemporal_load(p)
-#else
-#define NTLD(p) (*(p))
-#endif
-#if SMX_EMIT_NTST
 #define NTST(v, p) __builtin_nontemporal_store((v), (p))
-#else
-#define NTST(v, p) (*(p) = (v))
-#endif
-#ifndef SMX_EMIT_NOGATHER
-#define SMX_EMIT_NOGATHER 0
-#endif
 #ifndef EMIT_WT
 #define EMIT_WT 1024  // positions per wave (2048: emit 0.753 -> 0.749 ms, within noise, profiles/r06/ab_c3_emit_stores.txt)
 #endif
@@ -1107,12 +955,7 @@ static_assert(EMIT_WT % (WAVE * EMIT_B) == 0, "a wave's output range is whole ba
 // found by one binary search per wave and a scalar walk over the (few) skips of
 // each 64-output step.  Renames see their symbol's final move state, the rest
 // also its last rename (compose.py:30-49).  Block 0 writes the call's counts.
-#ifdef EMIT_WPE
-#define EMIT_BOUNDS __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EMIT_WPE, EMIT_WPE)))
-#else
-#define EMIT_BOUNDS __launch_bounds__(BLOCK)
-#endif
-__global__ void EMIT_BOUNDS k_emit(EmitArgs E) {
+__global__ void __launch_bounds__(BLOCK) k_emit(EmitArgs E) {
   const ComposeMeta* M = E.meta;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     // -1 invalid input (sym >= n_sym or kind >= 18); -2 the plan failed, -3 moves
@@ -1182,10 +1025,7 @@ __global__ void EMIT_BOUNDS k_emit(EmitArgs E) {
       sy[j] = min(NTLD(&E.tsym[pp[j]]), E.smax);
     }
     int4 F[EMIT_B];
-    if (SMX_EMIT_NOGATHER) {  // diagnostics only: the stream without the table lookups
-#pragma unroll
-      for (int j = 0; j < EMIT_B; ++j) F[j] = make_int4((int)sy[j], 0, 0, 0);
-    } else if (FP.packed) {
+    if (FP.packed) {
       u64 x[EMIT_B];
 #pragma unroll
       for (int j = 0; j < EMIT_B; ++j) x[j] = fin_word(FP, E.fin, sy[j]);
@@ -1216,14 +1056,11 @@ __global__ void EMIT_BOUNDS k_emit(EmitArgs E) {
 // wave owns EMIT_WT consecutive output indices; a step is 256 outputs.  Four outputs
 // of a lane read four consecutive positions P unless a skipped rename falls between
 // them (rare): then each is read on its own.
-#ifndef EMIT_VEC
-#define EMIT_VEC 1
-#endif
 #define EMIT4_STEPS (EMIT_WT / (4 * WAVE))
 typedef u32 ev4u __attribute__((ext_vector_type(4)));
 typedef i32 ev4i __attribute__((ext_vector_type(4)));
 typedef ev4u __attribute__((aligned(4))) ev4u_a4;
-__global__ void EMIT_BOUNDS k_emit4(EmitArgs E) {
+__global__ void __launch_bounds__(BLOCK) k_emit4(EmitArgs E) {
   const ComposeMeta* M = E.meta;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     const bool bad = M->bad_sym != 0;
@@ -1549,11 +1386,6 @@ static WalkArgs walk_args(const Ctx& C, const smx_shard* sh) {
 
 // DivergentRename walk (smx_walk.h): conflicts, skip bits, sorted skip list.
 // Every size is read on the device from meta: no host sync.
-#ifndef SMX_WALK_LB
-#define SMX_WALK_LB 0  // 1: the one-block walk steps run in the last block of the grid before
-                       // them; slower: config 2 walk 0.040 -> 0.056 ms (profiles/r05_wlb/ab_c2.txt),
-                       // the device-scope fences of every block cost more than the launches
-#endif
 static int launch_walk(const Ctx& C, const smx_shard* sh) {
   hipStream_t st = C.st;
   ComposeMeta* meta = C.ws<ComposeMeta>(B_META);
@@ -1583,25 +1415,15 @@ static int launch_walk(const Ctx& C, const smx_shard* sh) {
 #define WALK_GSMALL 256  // (64 and 1024 measured the same on configs 2 and 3: profiles/r06/ab_c3_walk_grid.txt)
 #endif
   const int gsmall = WALK_GSMALL;  // grid for loops over the (few) candidates
-  // small single merges: the one-block steps run in the last block of the grid before
-  // them (k_boundary_cc, k_replay_q_cl), two launches fewer
-  const bool lb_cc = SMX_WALK_LB && !sh && Wmax <= WALK_CC_FUSED_MAXW;
-  const bool lb_cl = SMX_WALK_LB && !sh && n <= WALK_FUSED_MAXN;
-  if (lb_cc)
-    hipLaunchKernelGGL(k_boundary_cc, dim3(grid_for(Wmax)), dim3(BLOCK), 0, st, Wk, meta, cslot, wcand, wtot,
-                       skipbits, nskipw, wcoff, (u64)Wmax, ncand32, cand);
-  else
-    hipLaunchKernelGGL(k_boundary, dim3(grid_for(Wmax)), dim3(BLOCK), 0, st, Wk, meta, cslot, wcand, wtot, skipbits,
-                       nskipw);
+  hipLaunchKernelGGL(k_boundary, dim3(grid_for(Wmax)), dim3(BLOCK), 0, st, Wk, meta, cslot, wcand, wtot, skipbits,
+                     nskipw);
   if (sh && (sh->in_d > 0 || sh->in_state_dev))
     hipLaunchKernelGGL(k_replay_in, dim3(1), dim3(1), 0, st, Wk, (int)sh->in_ahead, (u32)sh->in_d,
                        (const i64*)sh->in_state_dev, meta, C.out->conflicts, (u64)C.out->conflict_cap, skiplist,
                        skipbits);
   // (one k_scan1 block over the window counts measured slower on config 3: walk 0.165 ->
   // 0.185 ms, round 3; small merges are launch-bound: one block)
-  if (lb_cc) {
-    // (k_boundary_cc's last block did the scan and the compaction)
-  } else if (Wmax <= WALK_CC_FUSED_MAXW) {
+  if (Wmax <= WALK_CC_FUSED_MAXW) {
     hipLaunchKernelGGL(k_cand_scan_compact, dim3(1), dim3(S1_NT), 0, st, Wk, wtot, wcoff, (u64)Wmax, ncand32, cslot,
                        cand);
   } else {
@@ -1612,10 +1434,7 @@ static int launch_walk(const Ctx& C, const smx_shard* sh) {
       HIP_TRY((scan_excl<OpSum, u32, u32>(wtot, wcoff, Wmax, &meta->n_win, part, ncand32, st)));
     hipLaunchKernelGGL(k_cand_compact, dim3(grid_for(Wmax)), dim3(BLOCK), 0, st, Wk, cslot, wcoff, ncand_dev, cand);
   }
-  if (lb_cl) {
-    hipLaunchKernelGGL(k_replay_q_cl, dim3(gsmall), dim3(BLOCK), 0, st, Wk, cand, meta, q, nconf, pm, nreal, coff,
-                       (u64)n, nconf32);
-  } else if (n <= WALK_FUSED_MAXN) {  // small merges: max scan, clusters and sum scan in one block
+  if (n <= WALK_FUSED_MAXN) {  // small merges: max scan, clusters and sum scan in one block
     hipLaunchKernelGGL(k_replay_q, dim3(gsmall), dim3(BLOCK), 0, st, Wk, cand, meta, q, nconf);
     hipLaunchKernelGGL(k_cluster_fused, dim3(1), dim3(S1_NT), 0, st, Wk, cand, q, pm, nconf, meta, nreal, coff,
                        (u64)n, nconf32);
@@ -1729,7 +1548,7 @@ static int launch_emit(const Ctx& C, bool packable, const smx_shard* sh) {
   const i64 ewaves = SMX_CEIL_DIV(n, (i64)EMIT_WT);
   const bool al16 = ((uintptr_t)C.out->order | (uintptr_t)C.out->addr | (uintptr_t)C.out->file |
                      (uintptr_t)C.out->ctx) % 16 == 0;
-  if (EMIT_VEC && al16)
+  if (al16)
     hipLaunchKernelGGL(k_emit4, dim3(SMX_CEIL_DIV(ewaves, (i64)NWAVES)), dim3(BLOCK), 0, st, E);
   else
     hipLaunchKernelGGL(k_emit, dim3(SMX_CEIL_DIV(ewaves, (i64)NWAVES)), dim3(BLOCK), 0, st, E);
@@ -1802,10 +1621,7 @@ static int side_stream(hipStream_t caller, SideStream** out) {
   // also fences at system scope -- an L2 write-back the next kernel on the recording
   // stream waits behind: ~11 us before k_boundary and ~6 us before the reduce on config 3,
   // profiles/r06/c3_timeline_start.txt)
-#ifndef SMX_SIDE_SYSFENCE
-#define SMX_SIDE_SYSFENCE 0
-#endif
-  const unsigned evf = hipEventDisableTiming | (SMX_SIDE_SYSFENCE ? 0u : hipEventDisableSystemFence);
+  const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
   HIP_TRY(hipEventCreateWithFlags(&S->fork, evf));
   HIP_TRY(hipEventCreateWithFlags(&S->join, evf));
   g_side[g_nside++] = S;
@@ -1813,9 +1629,6 @@ static int side_stream(hipStream_t caller, SideStream** out) {
   return SMX_OK;
 }
 
-#ifndef SMX_TB_OVERLAP
-#define SMX_TB_OVERLAP 1
-#endif
 #ifndef SMX_TB_UNSKIP_MAXN
 #define SMX_TB_UNSKIP_MAXN (1 << 22)  // up to: k_tb_reduce reads the skip bits; above: k_tb_unskip
 #endif
@@ -1827,8 +1640,7 @@ static bool n_side_needed(const smx_ops* ops) {
   u64 width = SMX_CEIL_DIV((u64)ops->n_sym, (u64)TB_NBK_TGT);
   if (width < 1) width = 1;
   if (width > TB_WIDTH) width = TB_WIDTH;
-  return SMX_TB_OVERLAP && SMX_CEIL_DIV((u64)ops->n_sym, width) <= TB_MAXBK &&
-         ops->n_a + ops->n_b >= SMX_TB_OVERLAP_MIN;
+  return SMX_CEIL_DIV((u64)ops->n_sym, width) <= TB_MAXBK && ops->n_a + ops->n_b >= SMX_TB_OVERLAP_MIN;
 }
 
 // Walk, tables, emit of a single merge.  The bucketed tables' scatter keeps every
@@ -1843,7 +1655,7 @@ static int launch_tail(const Ctx& C) {
   const u64 nbk = SMX_CEIL_DIV((u64)n_sym, width);
   // the smallest merges are launch-bound: below SMX_TB_OVERLAP_MIN the fork/join costs more than the overlap saves
   SideStream* S = nullptr;
-  if (SMX_TB_OVERLAP && nbk <= TB_MAXBK && C.n >= SMX_TB_OVERLAP_MIN && !knob("SMX_TB_SERIAL", 0)) {
+  if (nbk <= TB_MAXBK && C.n >= SMX_TB_OVERLAP_MIN && !knob("SMX_TB_SERIAL", 0)) {
     int rc = side_stream(C.st, &S);
     if (rc) return rc;
   }
@@ -1951,22 +1763,20 @@ static int launch_presorted_windows(const Ctx& C, i64 W, i64 CM, int level) {
   } else
 #endif
   if (wide) {
-    if (P.src_map) hipLaunchKernelGGL((k_window_f<WF_WIDE_CAP, WF_WIDE_NT, false, true, WF_RUNS_WIDE>), dim3(W), dim3(WF_WIDE_NT), 0, st, P);
-    else hipLaunchKernelGGL((k_window_f<WF_WIDE_CAP, WF_WIDE_NT, false, false, WF_RUNS_WIDE>), dim3(W), dim3(WF_WIDE_NT), 0, st, P);
+    if (P.src_map) hipLaunchKernelGGL((k_window_f<WF_WIDE_CAP, WF_WIDE_NT, false, true, true>), dim3(W), dim3(WF_WIDE_NT), 0, st, P);
+    else hipLaunchKernelGGL((k_window_f<WF_WIDE_CAP, WF_WIDE_NT, false, false, true>), dim3(W), dim3(WF_WIDE_NT), 0, st, P);
   } else if (level == WL_SMALL) {
     if (P.src_map) hipLaunchKernelGGL((k_window_f<WF_SMALL_CAP, WF_SMALL_NT, false, true>), dim3(W), dim3(WF_SMALL_NT), 0, st, P);
     else hipLaunchKernelGGL((k_window_f<WF_SMALL_CAP, WF_SMALL_NT, false, false>), dim3(W), dim3(WF_SMALL_NT), 0, st, P);
   } else if (P.src_map) {
-    hipLaunchKernelGGL((k_window_f<WF_CAP, WF_NT, false, true, WF_RUNS>), dim3(W), dim3(WF_NT), 0, st, P);
+    hipLaunchKernelGGL((k_window_f<WF_CAP, WF_NT, false, true, true>), dim3(W), dim3(WF_NT), 0, st, P);
   } else {
-    hipLaunchKernelGGL((k_window_f<WF_CAP, WF_NT, false, false, WF_RUNS>), dim3(W), dim3(WF_NT), 0, st, P);
+    hipLaunchKernelGGL((k_window_f<WF_CAP, WF_NT, false, false, true>), dim3(W), dim3(WF_NT), 0, st, P);
   }
   HIP_TRY(hipGetLastError());
   C.tm->end(stage);
   return SMX_OK;
 }
-
-
 
 // wide: WF_WIDE_CAP-op windows on WF_WIDE_NT threads (one per CU) for logs whose
 // equal-timestamp groups no WF_CAP window holds (config 5: 8192-op groups).
@@ -2003,34 +1813,19 @@ static int run_presorted(const Ctx& C, i64 tgt, const EarlyFail* early = nullptr
   u32* ccnt = C.ws<u32>(B_CCNT);
   u64* sA = C.ws<u64>(B_SMP);
   u64* sB = sA + SMX_CEIL_DIV(C.na, (i64)CH) + 1;
-  const bool lmode = early && defer && level == WL_NORMAL && !KH_PERSIST;
+  const bool lmode = early && defer && level == WL_NORMAL;
   LongW lw{};
   if (lmode) {
     lw.tgt_w = level_cap(WL_WIDE) - level_cap(WL_WIDE) % CH;  // (the first wide attempt of order_fallbacks)
     lw.W_w = SMX_CEIL_DIV(C.n, lw.tgt_w);
     lw.D_w = level_cap(WL_WIDE) / CH;
   }
-  if (KH_PERSIST) {
-    static int ncu_of[64] = {};  // CUs per device (a benign race: every writer stores the same)
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    int ncu = dev < 64 ? ncu_of[dev] : 0;
-    if (ncu == 0) {
-      HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-      if (dev < 64) ncu_of[dev] = ncu;
-    }
-    const i64 ngrp = SMX_CEIL_DIV(nchunk, (i64)CH_PER_BLOCK);
-    const i64 grid = ngrp < (i64)ncu * KH_BLOCKS_PER_CU ? ngrp : (i64)ncu * KH_BLOCKS_PER_CU;
-    hipLaunchKernelGGL(k_khist2, dim3(grid > 0 ? grid : 1), dim3(KH_NT), 0, st, C.ops->kind, C.ops->ts, C.na, C.nb,
-                       C.ops->b_gap, CM, ccnt, sA, sB, meta, early ? early->flag_dev : nullptr);
-  } else {
-    hipLaunchKernelGGL(k_khist, dim3(SMX_CEIL_DIV(nchunk, (i64)CH_PER_BLOCK * KH_R)), dim3(KH_NT), 0, st,
-                       C.ops->kind, C.ops->ts, C.na, C.nb, C.ops->b_gap, CM, ccnt, sA, sB, meta,
-                       early ? early->flag_dev : nullptr, lmode ? cap / CH : (i64)0);
-  }
+  hipLaunchKernelGGL(k_khist, dim3(SMX_CEIL_DIV(nchunk, (i64)CH_PER_BLOCK * KH_R)), dim3(KH_NT), 0, st,
+                     C.ops->kind, C.ops->ts, C.na, C.nb, C.ops->b_gap, CM, ccnt, sA, sB, meta,
+                     early ? early->flag_dev : nullptr, lmode ? cap / CH : (i64)0);
   if (lmode) HIP_TRY(hipEventRecord(early->ev, st));  // (k_khist's verdict)
   const i64 nfp = SMX_CEIL_DIV(W + 1, (i64)BLOCK);   // (>= the wide plan's W_w + 1 boundaries)
-  const bool fused = SMX_FPART_CS && cs_small && !early;
+  const bool fused = cs_small && !early;  // small merges: k_fpart and k_cscan_small in one launch
   if (fused)
     hipLaunchKernelGGL(k_fpart_cscan, dim3(nfp + 2 * SMX_N_KINDS), dim3(BLOCK), 0, st, C.ops->ts,
                        C.ops->ts + C.na + C.ops->b_gap, sA, sB, C.na, C.nb, W, tgt, cap / CH, bnd, meta,
@@ -2071,9 +1866,8 @@ __global__ void k_plan_rearm(ComposeMeta* meta, u64 nwin) {
   if (meta->f_fail == F_LONG) meta->f_fail = 0;
   meta->n_win = nwin;
 }
-// (the chunk scans must write base[] and the prefixes even when k_fpart flagged F_LONG:
-// with SMX_CSCAN_FAILCHK they would leave early and the wide windows read stale prefixes)
-static_assert(!SMX_CSCAN_FAILCHK, "run_presorted_rewide reuses the failed plan's chunk prefixes and bases");
+// (which is why the chunk scans never leave on a failed plan: they write base[] and the
+// prefixes even when k_fpart flagged F_LONG, or the wide windows would read stale prefixes)
 static int run_presorted_rewide(const Ctx& C, i64 tgt, int level = WL_WIDE) {
   hipStream_t st = C.st;
   ComposeMeta* meta = C.ws<ComposeMeta>(B_META);
@@ -2138,10 +1932,6 @@ __device__ __forceinline__ void seg_pass(u64 (&v)[8], u32 base, u32 b, u32 k, in
   }
 }
 
-#ifndef SEG_BUCKET
-#define SEG_BUCKET 1
-#endif
-#if SEG_BUCKET
 // Interpolation buckets (the default): element x of group [gs, ge) goes to bucket
 // (gs + (ge - gs) * hi32 / 2^32) / 2, i.e. two elements per bucket on random ids;
 // buckets are ordered like (group, hi), a counting sort places them and each element
@@ -2151,9 +1941,6 @@ __device__ __forceinline__ void seg_pass(u64 (&v)[8], u32 base, u32 b, u32 k, in
 #define SEGPAD(i) (i)
 #define SEG_NBK (SEG_CAP / 2)
 #define SEG_BKMAX 32
-#else
-#define SEGPAD(i) ((i) + ((i) >> 3))  // one pad word per 8 keys: spreads a thread's 8 keys over banks
-#endif
 
 // One tile of one branch (ts, hi, lo: the branch's columns; outputs at the branch's
 // offset; off: the branch's first op index in A||B).  Sort key, one u64 per element:
@@ -2186,9 +1973,7 @@ __global__ void __launch_bounds__(SEG_NT) k_segsort(const u64* __restrict__ ts, 
   __shared__ u64 key[SEGPAD(SEG_CAP)];
   __shared__ u32 wsum[SEG_NT / WAVE + 1];
   __shared__ i64 se[2];
-#if SEG_BUCKET
   __shared__ u32 bcnt[SEG_NBK / 2];  // two 16-bit bucket counters per word
-#endif
   const int t = threadIdx.x, lane = t & (WAVE - 1), wv = t / WAVE;
   const i64 p0 = (i64)blockIdx.x * SEG_H;
   // Layout: every adjacent pair of the nominal range (the nominal ranges cover the
@@ -2259,7 +2044,6 @@ __global__ void __launch_bounds__(SEG_NT) k_segsort(const u64* __restrict__ ts, 
     gk[k] = g;
     v[k] = x < (u32)size ? ((u64)g << 51) | ((hi[s + x] >> 26) << 13) | x : ~0ull;  // padding sorts last
   }
-#if SEG_BUCKET
   bool bitonic = false;
   {
     u32 ng = 1;  // groups in the tile
@@ -2330,48 +2114,45 @@ __global__ void __launch_bounds__(SEG_NT) k_segsort(const u64* __restrict__ ts, 
     }
   }
   if (bitonic) {
-#endif
-  // merge levels k = 2, 4, 8: keys 8t .. 8t+7 (b = 0)
-  seg_pass(v, (u32)t * 8, 0, 2, 0, 1);
-  seg_pass(v, (u32)t * 8, 0, 4, 1, 2);
-  seg_pass(v, (u32)t * 8, 0, 8, 2, 3);
-  // later levels: a pass per window b of three partner bits; the keys move between
-  // layouts through LDS (write in the old layout, read in the new one)
-  u32 cur = 0;  // layout of v
-  auto base_of = [&](u32 b) { return ((u32)t >> b << (b + 3)) | ((u32)t & ((1u << b) - 1)); };
-  for (u32 lk = 4; lk <= lgP; ++lk) {
-    const u32 k = 1u << lk;
-    for (int jb = (int)lk - 1; jb >= 0;) {
-      const u32 b = jb >= 2 ? (u32)jb - 2 : 0u;
-      if (b != cur) {
-        __syncthreads();  // the previous layout's reads are done
-        if (own) {
-          const u32 bo = base_of(cur);
+    // merge levels k = 2, 4, 8: keys 8t .. 8t+7 (b = 0)
+    seg_pass(v, (u32)t * 8, 0, 2, 0, 1);
+    seg_pass(v, (u32)t * 8, 0, 4, 1, 2);
+    seg_pass(v, (u32)t * 8, 0, 8, 2, 3);
+    // later levels: a pass per window b of three partner bits; the keys move between
+    // layouts through LDS (write in the old layout, read in the new one)
+    u32 cur = 0;  // layout of v
+    auto base_of = [&](u32 b) { return ((u32)t >> b << (b + 3)) | ((u32)t & ((1u << b) - 1)); };
+    for (u32 lk = 4; lk <= lgP; ++lk) {
+      const u32 k = 1u << lk;
+      for (int jb = (int)lk - 1; jb >= 0;) {
+        const u32 b = jb >= 2 ? (u32)jb - 2 : 0u;
+        if (b != cur) {
+          __syncthreads();  // the previous layout's reads are done
+          if (own) {
+            const u32 bo = base_of(cur);
 #pragma unroll
-          for (int m = 0; m < PER; ++m) key[SEGPAD(bo | ((u32)m << cur))] = v[m];
-        }
-        __syncthreads();
-        if (own) {
-          const u32 bn = base_of(b);
+            for (int m = 0; m < PER; ++m) key[SEGPAD(bo | ((u32)m << cur))] = v[m];
+          }
+          __syncthreads();
+          if (own) {
+            const u32 bn = base_of(b);
 #pragma unroll
-          for (int m = 0; m < PER; ++m) v[m] = key[SEGPAD(bn | ((u32)m << b))];
+            for (int m = 0; m < PER; ++m) v[m] = key[SEGPAD(bn | ((u32)m << b))];
+          }
+          cur = b;
         }
-        cur = b;
+        if (own) seg_pass(v, base_of(b), b, k, jb - (int)b, jb - (int)b + 1);
+        jb = (int)b - 1;
       }
-      if (own) seg_pass(v, base_of(b), b, k, jb - (int)b, jb - (int)b + 1);
-      jb = (int)b - 1;
     }
-  }
-  __syncthreads();
-  if (own) {
-    const u32 bo = base_of(cur);
+    __syncthreads();
+    if (own) {
+      const u32 bo = base_of(cur);
 #pragma unroll
-    for (int m = 0; m < PER; ++m) key[SEGPAD(bo | ((u32)m << cur))] = v[m];
+      for (int m = 0; m < PER; ++m) key[SEGPAD(bo | ((u32)m << cur))] = v[m];
+    }
+    __syncthreads();
   }
-  __syncthreads();
-#if SEG_BUCKET
-  }
-#endif
   // runs of equal (group, hi38): exact order on (oid_hi, oid_lo, index)
   for (u32 x = t; x + 1 < (u32)size; x += SEG_NT) {
     const u64 kx = key[SEGPAD(x)] >> 13;
@@ -2404,25 +2185,10 @@ __global__ void __launch_bounds__(SEG_NT) k_segsort(const u64* __restrict__ ts, 
   }
 }
 
-
-// Host wait for a stream: with SMX_SPIN_US > 0 a short spin on hipStreamQuery first, then
-// the blocking sync.  Off for the merges: spinning measured slower there (config 2
-// 0.161 -> 0.166 ms, profiles/r05_x/spin_ab.txt), while the RGA call gains from it
-// (smx_rga.hip RGA_SPIN_US).
-#ifndef SMX_SPIN_US
-#define SMX_SPIN_US 0
-#endif
-static hipError_t stream_wait(hipStream_t st) {
-  if (SMX_SPIN_US > 0) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-      const hipError_t e = hipStreamQuery(st);
-      if (e != hipErrorNotReady) return e;
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(SMX_SPIN_US)) break;
-    }
-  }
-  return hipStreamSynchronize(st);
-}
+// Host wait for a stream: the blocking sync.  No spin on hipStreamQuery before it for the
+// merges: spinning measured slower there (config 2 0.161 -> 0.166 ms,
+// profiles/r05_x/spin_ab.txt), while the RGA call gains from it (smx_rga.hip RGA_SPIN_US).
+static hipError_t stream_wait(hipStream_t st) { return hipStreamSynchronize(st); }
 
 static int read_meta(const Ctx& C, ComposeMeta* hm);
 
@@ -2713,17 +2479,13 @@ static int early_fail_of(int dev, EarlyFail* e) {
       HIP_TRY(hipHostGetDevicePointer((void**)&s.e.flag_dev, s.e.flag_host, 0));
       // (no system-scope fence: k_khist / k_fpart store the flag itself at system scope,
       // and a missed flag only costs the tail launched behind a plan that then fails)
-      HIP_TRY(hipEventCreateWithFlags(&s.e.ev, hipEventDisableTiming | (SMX_SIDE_SYSFENCE ? 0u : hipEventDisableSystemFence)));
+      HIP_TRY(hipEventCreateWithFlags(&s.e.ev, hipEventDisableTiming | hipEventDisableSystemFence));
       s.dev = dev;
       *e = s.e;
       return SMX_OK;
     }
   return SMX_E_HIP;  // (more than four devices per host thread: no early flag)
 }
-
-#ifndef SMX_SMALL
-#define SMX_SMALL 1  // merges of at most SMALL_N ops: one workgroup, one launch (k_compose_small)
-#endif
 
 // smx_compose's one-workgroup plan: the SMALL_N instance of smx_small.h (the header is
 // shared with the batch kernels' unit, so the kernel lives with its one launch)
@@ -2733,7 +2495,7 @@ __global__ void __launch_bounds__(SMALL_NT) k_compose_small(smx_ops ops, smx_com
 }
 
 // Largest merge (ops) the one-workgroup path takes (smx_set_small_limit; 0: never).
-static std::atomic<int64_t> g_small_max{SMX_SMALL ? SMALL_N : 0};
+static std::atomic<int64_t> g_small_max{SMALL_N};
 // (symbol ids index the small kernel's hash table with 0xffffffff as its empty mark)
 static inline bool small_merge(const smx_ops* ops) {
   return ops->n_a + ops->n_b <= g_small_max.load(std::memory_order_relaxed) && ops->n_sym <= 0xffffffffll;
@@ -3311,7 +3073,7 @@ extern "C" int smx_diag_small_stamps(uint64_t* host16) {
 
 extern "C" int64_t smx_set_small_limit(int64_t n) {
   const int64_t v = n < 0 ? 0 : n > SMALL_N ? SMALL_N : n;
-  return g_small_max.exchange(SMX_SMALL ? v : 0);
+  return g_small_max.exchange(v);
 }
 
 extern "C" int smx_set_profiling(int enabled) {

@@ -54,12 +54,6 @@ struct __attribute__((aligned(16))) R16 {  // one record (16-byte loads / stores
 #define RREC_TILE (RR_NT * RREC_ITEMS)    // 3072 records (120 KB) per block and pass
 #define RREC_SEG (RREC_TILE / RR_NW)      // contiguous records per wave
 #define RGA_NDIG 256                      // digits per pass
-#ifndef RR_HIST_OP
-#define RR_HIST_OP 0  // 1: the histogram pass also reads the op column (to count bad ops as list 0)
-#endif
-#ifndef RR_W16
-#define RR_W16 1  // runs written as 16-byte records (one store per record, not two)
-#endif
 static_assert(RREC_TILE % BLOCK == 0 && RREC_TILE <= 65535, "tile: k_rrec_hist blocks, u16 slots");
 
 template <bool FIRST>
@@ -81,7 +75,7 @@ __global__ void __launch_bounds__(BLOCK) k_rrec_hist(smx_rga_ops o, const u32* _
         const u32 l = o.list[i];
         // a list id out of range counts as list 0, where k_rrec_scatter places it (an op
         // > 2 fails the call there; its record still goes to its list)
-        const bool b = RR_HIST_OP ? l >= (u64)o.n_lists || o.op[i] > 2 : l >= (u64)o.n_lists;
+        const bool b = l >= (u64)o.n_lists;
         key[it] = b ? 0u : l;
         bad |= (u32)b;
       } else {
@@ -195,7 +189,7 @@ __global__ void __launch_bounds__(RR_NT) k_rrec_scatter(smx_rga_ops o, const u32
         const bool badl = key[it] >= (u64)o.n_lists, bado = T.op[it] > 2;
         if (valid && (badl || bado)) {
           *err = 1;
-          if (badl || RR_HIST_OP) key[it] = 0;
+          if (badl) key[it] = 0;
         }
       } else {
         key[it] = T.key[it];
@@ -274,7 +268,6 @@ __global__ void __launch_bounds__(RR_NT) k_rrec_scatter(smx_rga_ops o, const u32
     __syncthreads();
     // the next tile's loads fly while this tile's runs are written
     if (tile + gridDim.x < ntiles) rrec_load<FIRST>(T, o, kin, rin, (i64)(tile + gridDim.x) * RREC_TILE, t, w, lane);
-#if RR_W16
 #pragma unroll 1
     for (u32 p = t; p < cnt; p += RR_NT) {  // record-wise: consecutive lanes, consecutive 16-byte records
       const u32 key = skey[p];
@@ -283,19 +276,6 @@ __global__ void __launch_bounds__(RR_NT) k_rrec_scatter(smx_rga_ops o, const u32
       kout[dst] = (KO)key;  // (u8: the low byte, for k_rrec_local)
       *reinterpret_cast<R16*>(rout + (u64)dst * RGA_REC) = reinterpret_cast<const R16*>(srec)[p];
     }
-#else
-#pragma unroll 1
-    for (u32 p = t; p < cnt; p += RR_NT) {
-      const u32 d = (skey[p] >> shift) & 255u;
-      kout[gofs[d] + p - lstart[d]] = (KO)skey[p];  // (u8: the low byte, for k_rrec_local)
-    }
-#pragma unroll 1
-    for (u32 x = t; x < cnt * RGA_REC; x += RR_NT) {  // word-wise: consecutive lanes, consecutive words
-      const u32 p = x / RGA_REC, k = x - p * RGA_REC;
-      const u32 d = (skey[p] >> shift) & 255u;
-      rout[(u64)(gofs[d] + p - lstart[d]) * RGA_REC + k] = srec[x];
-    }
-#endif
     __syncthreads();  // LDS is rewritten by the next tile
   }
 }
@@ -317,45 +297,14 @@ __global__ void __launch_bounds__(RR_NT) k_rrec_scatter(smx_rga_ops o, const u32
 // RGA_E_UNGROUPED a call that said its events come grouped by list (SMX_RGA_GROUPED) has a
 // list id that decreases: every list kernel leaves at once and the call is redone with
 // the partition
-#ifndef RGA_DIRECT
-#define RGA_DIRECT 1  // grouped calls: the list kernels read the input columns (no record pass)
-#endif
 #define RGA_E_INPUT 1
 #define RGA_E_UNGROUPED 2
 
 // Events already grouped by list (non-decreasing list ids: what crdt.replay and RGA
-// hand over, stream after stream): the records are packed in place of the partition --
-// one coalesced pass, four consecutive events per thread -- and the list starts come
-// from the steps of the list id.  Also zeroes the survivor chunk sums (k_rga_bounds' duty).
-__global__ void __launch_bounds__(BLOCK) k_rga_pack(smx_rga_ops o, u64* __restrict__ rout, u32* __restrict__ lstart,
-                                                    u32* __restrict__ csum, i32* __restrict__ err) {
-  const i64 n = o.n_ops, nl = o.n_lists;
-  if (blockIdx.x == 0 && threadIdx.x < RGA_CS_MAX) csum[threadIdx.x] = 0u;
-  u32 bad = 0;
-  // consecutive lanes, consecutive events: coalesced column loads, one 16-byte record store
-  for (i64 i = (i64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (i64)gridDim.x * BLOCK) {
-    const u32 l = o.list[i], op = o.op[i], v = o.value[i], an = o.anchor[i];
-    const i64 t = o.t[i];
-    const u32 prev = i > 0 ? o.list[i - 1] : 0u;  // (the neighbour lane's load: an L1 hit)
-    bad |= (l >= (u64)nl || op > 2) ? (u32)(RGA_E_INPUT | RGA_E_UNGROUPED) : 0u;
-    bad |= i > 0 && l < prev ? (u32)RGA_E_UNGROUPED : 0u;
-    const u64 tt = (u64)t ^ 0x8000000000000000ull;
-    R16 r;
-    r.a = ((u64)an << 32) | (tt >> 32);
-    r.b = ((u64)v << 32) | ((op > 2 ? 0u : op) << 30) | (u32)i;
-    *reinterpret_cast<R16*>(rout + (u64)i * RGA_REC) = r;
-    // list starts: the lists in (prev, l] start here (from list 0 at the first event);
-    // after the last event the rest start at n (ids clamped: one out of range fails the call)
-    const u32 lo = i == 0 ? 0u : prev + 1u, hi = l < (u64)nl ? l : (u32)(nl - 1);
-    for (u32 L = lo; L <= hi; ++L) lstart[L] = (u32)i;
-    if (i == n - 1)
-      for (i64 L = (i64)hi + 1; L < nl; ++L) lstart[L] = (u32)n;
-  }
-  if (bad) atomicOr(err, (i32)bad);
-}
-
-// Grouped events read in place by the list kernels (ColSrc): only the list starts, the
-// checks and the chunk sums' zeroing of k_rga_pack, reading the list ids and ops.
+// hand over, stream after stream) are read in place by the list kernels (ColSrc), so no
+// partition runs: only the list starts, which come from the steps of the list id, and
+// the input checks, reading the list ids and ops.  Also zeroes the survivor chunk sums
+// (k_rga_bounds' duty).
 __global__ void __launch_bounds__(BLOCK) k_rga_gbounds(smx_rga_ops o, u32* __restrict__ lstart,
                                                        u32* __restrict__ csum, i32* __restrict__ err) {
   const i64 n = o.n_ops, nl = o.n_lists;
@@ -416,9 +365,6 @@ __global__ void k_rga_bounds(const u32* __restrict__ keys, i64 n, i64 nl, u32* _
 // stable scatter of tiles in stream order -- no global histogram, scan or bounds pass
 // (the bucket's list starts come from its scan), and no list ids written (the list
 // kernels read only the starts).  Bucket d is [dstart[d], dstart[d + 1]).
-#ifndef RGA_MSD
-#define RGA_MSD 1  // 0: LSD passes (k_rrec_hist / k_rrec_scatter twice, k_rga_bounds)
-#endif
 #define RL_NT 1024
 #define RL_NW (RL_NT / WAVE)
 #ifndef RL_ITEMS
@@ -429,9 +375,6 @@ __global__ void k_rga_bounds(const u32* __restrict__ keys, i64 n, i64 nl, u32* _
 #define RL_CU 8                   // count phase: keys in flight per lane
 #ifndef RL_S
 #define RL_S 2  // workgroups per bucket
-#endif
-#ifndef RL_PF
-#define RL_PF 0  // 1: the next tile's loads issued once this one is staged (measured slower: 0.58 -> 0.605 ms)
 #endif
 __global__ void __launch_bounds__(RL_NT) k_rrec_local(const u8* __restrict__ kin, const u64* __restrict__ rin,
                                                       u64* __restrict__ rout,
@@ -461,7 +404,6 @@ __global__ void __launch_bounds__(RL_NT) k_rrec_local(const u8* __restrict__ kin
       rv[it].b = valid ? rin[(u64)i * RGA_REC + 1] : 0ull;
     }
   };
-  if (RL_PF && sa < sb) load_tile(sa);  // (in flight during the count)
   if (t < RGA_NDIG) {
     cnt[t] = 0;
     tstart[t] = 0;  // (first: the counts of the parts before this workgroup's)
@@ -521,7 +463,7 @@ __global__ void __launch_bounds__(RL_NT) k_rrec_local(const u8* __restrict__ kin
   __shared__ R16 stg[RL_TILE];
   __shared__ u8 sdig[RL_TILE];
   for (u32 base = sa; base < sb; base += RL_TILE) {
-    if (!RL_PF) load_tile(base);
+    load_tile(base);
     for (u32 x = t; x < RL_NW * RGA_NDIG; x += RL_NT) (&wc[0][0])[x] = 0;
     __syncthreads();
 #pragma unroll
@@ -564,7 +506,6 @@ __global__ void __launch_bounds__(RL_NT) k_rrec_local(const u8* __restrict__ kin
       sdig[slot] = (u8)dd;
     }
     __syncthreads();
-    if (RL_PF && base + RL_TILE < sb) load_tile(base + RL_TILE);  // in flight while this tile is written
     const u32 nv = min((u32)RL_TILE, sb - base);
     for (u32 j = t; j < nv; j += RL_NT) {
       const u32 dd = sdig[j];
@@ -627,17 +568,7 @@ __device__ __forceinline__ bool rec_lt(const u64* a, const u64* b, const smx_rga
 #define RW_DEAD 0x400u
 #define RW_MOP 12       // member entries: event | op << RW_MOP
 #define RW_MEV 0xfffu
-#ifndef RW_HT1
-#define RW_HT1 1
-#endif
-#ifndef RW_H16
-#define RW_H16 1  // 16-bit group counts / bases (a list has at most 2 * RW_CAP events): less LDS per wave
-#endif
-#if RW_H16
-#define RW_HT u16
-#else
-#define RW_HT u32
-#endif
+#define RW_HT u16  // 16-bit group counts / bases (a list has at most 2 * RW_CAP events): less LDS per wave
 #ifndef RW_OCC_W
 #define RW_OCC_W 8  // k_rga_wave: registers for this many waves per SIMD (0: compiler's choice)
 #endif
@@ -646,24 +577,9 @@ __device__ __forceinline__ bool rec_lt(const u64* a, const u64* b, const smx_rga
 #else
 #define RW_OCC
 #endif
-#ifndef RW_LAUNDER
-#define RW_LAUNDER 1
-#endif
-#ifndef RW_RREG
-#define RW_RREG 0  // 1: groups of 2-4 events replayed in registers (list kernel 199 -> 204 us: off)
-#endif
 #ifndef RW_PINS_K
 #define RW_PINS_K 16  // lists of K >= this: a lane's K hash inserts probed together (off: for
                       // k_rga_wave's K = 4 0.563 -> 0.576 ms; k_rga_wave2's K = 8 26.9 us either way)
-#endif
-#ifndef RW_W0R
-#define RW_W0R 1  // word 0 of a lane's own events kept in registers for the survivors' keys
-#endif
-#ifndef RW_MGP_UNION
-#define RW_MGP_UNION 1  // mem / gp share LDS: 9.5 KB per two-list workgroup, 16 per CU
-#endif
-#ifndef RW_W0G
-#define RW_W0G 1  // key word 0 read from the list's records in L2, not held in LDS: 2 KB less per list, more lists per CU
 #endif
 #ifndef RW_ABL
 #define RW_ABL 0  // timing ablations (wrong results): bit0 no replay, bit1 no grouping / replay,
@@ -671,9 +587,6 @@ __device__ __forceinline__ bool rec_lt(const u64* a, const u64* b, const smx_rga
 #endif
 
 
-#ifndef RW_XV
-#define RW_XV 0  // 1: exchanges on the VALU only (DPP, permlane swaps): measured 0.560 -> 0.57 ms, off
-#endif
 // v from lane ^ lm (lm a constant after unrolling): DPP for 1, 2, 3, 7, 15, a swizzle
 // within 32 lanes for 4, 8, 16, 31, a permute otherwise.
 __device__ __forceinline__ u32 xor32_swap(u32 v) {  // lane ^ 32 (v_permlane32_swap: VALU)
@@ -686,25 +599,6 @@ __device__ __forceinline__ u32 xor16_swap(u32 v) {  // lane ^ 16 (v_permlane16_s
 }
 
 __device__ __forceinline__ u32 xshfl(u32 v, u32 lm) {
-#if RW_XV  // every exchange on the VALU (DPP, permlane swaps): no LDS-unit round trips
-  switch (lm) {
-    case 1: return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
-    case 2: return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);
-    case 3: return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x1B, 0xF, 0xF, false);
-    case 7: return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);
-    case 15: return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);
-    case 4: {  // ^7 (row half mirror) then ^3 (quad perm 3,2,1,0)
-      const u32 x = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);
-      return (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0x1B, 0xF, 0xF, false);
-    }
-    case 8: return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
-    case 16: return xor16_swap(v);
-    case 31: return (u32)__builtin_amdgcn_update_dpp(0, (int)xor16_swap(v), 0x140, 0xF, 0xF, false);
-    case 32: return xor32_swap(v);
-    case 63: return (u32)__builtin_amdgcn_update_dpp(0, (int)xor16_swap(xor32_swap(v)), 0x140, 0xF, 0xF, false);
-    default: return (u32)__shfl_xor((int)v, (int)lm);
-  }
-#endif
   switch (lm) {
     case 1: return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
     case 2: return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);
@@ -781,20 +675,13 @@ __device__ __forceinline__ void wave_bitonic32(u32 (&key)[8], u32 lane) {
   if constexpr (KK < 64u * K) wave_bitonic32<K, KK * 2>(key, lane);
 }
 
-#ifndef RW_PACK
-#define RW_PACK 1  // survivors' keys packed to 32 bits when the list's ranges allow (see rw_order)
-#endif
-
 template <int CAP>
 struct RwLds {
   static constexpr int cap = CAP;
-  // hash slots: one per event for k_rga_wave's lists (RW_HT1: 7.4 KB of LDS per list, five
+  // hash slots: one per event for k_rga_wave's lists (7.4 KB of LDS per list, five
   // waves per SIMD; a full table still terminates, every value finds its slot), two
   // per event otherwise
-  static constexpr int HT = (RW_HT1 && CAP == RW_CAP) ? CAP : 2 * CAP;
-#if !RW_W0G
-  u64 w0[CAP];          // key word 0 of each event (words 1-3 stay in global memory / L2)
-#endif
+  static constexpr int HT = CAP == RW_CAP ? CAP : 2 * CAP;
   u64 wv[CAP];          // value << 32 | op << 30 | index (record word RGA_WV)
   union {
     struct {
@@ -804,11 +691,7 @@ struct RwLds {
     } h;
     u64 gs[CAP];        // step 3: survivors' word 0, sorted
   };
-#if RW_MGP_UNION
   union {               // (mem is dead once the groups are replayed)
-#else
-  struct {
-#endif
     u16 mem[CAP];       // group members, group by group, each in event order (| op << RW_MOP)
     u16 gp[CAP];        // step 3: survivors' events, sorted
   };
@@ -846,11 +729,7 @@ struct ColSrc {
 template <class LDS, class SRC>
 __device__ __forceinline__ bool ev_lt(const LDS& S, const SRC& src, const smx_rga_ops& o, u32 a,
                                       u32 b) {
-#if RW_W0G
   const u64 wa = src.w0(a), wb = src.w0(b);  // (the list's records or columns, L2-resident)
-#else
-  const u64 wa = S.w0[a], wb = S.w0[b];
-#endif
   if (wa != wb) return wa < wb;
   return rga_key_lt(o, (u32)S.wv[a] & RGA_IDX_MASK, (u32)S.wv[b] & RGA_IDX_MASK);
 }
@@ -862,7 +741,6 @@ __device__ __forceinline__ void rw_order(LDS& S, const SRC& src, const smx_rga_o
                                          u32 s0, u32 lane, u32* __restrict__ tmp_v, u32* __restrict__ tmp_s) {
   constexpr u32 N = 64u * K2;
   bool packed = false;
-#if RW_PACK
   {  // word 0 = anchor << 32 | t's top half.  When the survivors' anchor and t ranges fit
      // beside the event bits in 31 bits, sort (anchor - min, t - min, event) as one u32:
      // one lane exchange and a min / max per step instead of three exchanges and selects.
@@ -902,7 +780,6 @@ __device__ __forceinline__ void rw_order(LDS& S, const SRC& src, const smx_rga_o
       }
     }
   }
-#endif
   if (!packed) wave_bitonic<K2>(key, pay, lane);
 #pragma unroll
   for (int k = 0; k < K2; ++k) {
@@ -948,8 +825,6 @@ __device__ __forceinline__ u32 rga_wave_list(const smx_rga_ops& o, const SRC src
                                               RwLds<CAP>& S, u32 lane, bool tomb,
                                               u32* __restrict__ tmp_v, u32* __restrict__ tmp_s,
                                               u32* __restrict__ scnt) {
-  static_assert(RW_W0R, "the record words come through src.w0 / src.w1");
-#if RW_W0R
   u64 w0r[K];  // word 0 of this lane's events k * 64 + lane, kept for step 3
   {  // every load in flight at once; word 1 of each event to LDS
     u64 wvr[K];
@@ -969,31 +844,6 @@ __device__ __forceinline__ u32 rga_wave_list(const smx_rga_ops& o, const SRC src
       if (e < cnt) S.wv[e] = wvr[k];
     }
   }
-#else
-  {  // every load in flight at once; words 0 and 4 of each event to LDS
-    u64 v[RGA_REC * K];
-#pragma unroll
-    for (int i = 0; i < RGA_REC * K; ++i) {
-      const u32 x = lane + (u32)i * WAVE;
-      v[i] = x < cnt * RGA_REC ? (x % RGA_REC ? src.w1(x / RGA_REC) : src.w0(x / RGA_REC)) : 0ull;
-    }
-    for (u32 t = lane; t < RwLds<CAP>::HT; t += WAVE) {
-      S.h.hkey[t] = RW_EMPTY;
-      S.h.hcnt[t] = 0;
-    }
-#pragma unroll
-    for (int i = 0; i < RGA_REC * K; ++i) {
-      const u32 x = lane + (u32)i * WAVE;
-      const u32 e = x / RGA_REC, wd = x - e * RGA_REC;
-      if (x < cnt * RGA_REC) {
-#if !RW_W0G
-        if (wd == 0) S.w0[e] = v[i];
-#endif
-        if (wd == RGA_WV) S.wv[e] = v[i];
-      }
-    }
-  }
-#endif
   wave_lds_sync();
   if (RW_ABL & 8) return (u32)__builtin_amdgcn_readfirstlane((int)((u32)S.wv[lane] & 1u));
   const u64 lt = lane ? ~0ull >> (WAVE - lane) : 0ull;  // (from `lane`: see k_rga_wave)
@@ -1107,46 +957,6 @@ __device__ __forceinline__ u32 rga_wave_list(const smx_rga_ops& o, const SRC src
         S.st[e] = opk[k] != 2;
         continue;
       }
-#if RW_RREG
-      if (c <= 4) {  // small groups (most of them) replayed in registers: the members'
-                     // entries read at once, no chain of dependent LDS reads.  A move
-                     // with two live candidates (their list order needs the keys) takes
-                     // the general loop below instead.
-        u32 xm[4], sv[4] = {0u, 0u, 0u, 0u};
-        bool hard = false;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xm[i] = (u32)i < c ? S.mem[b + i] : 0u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if ((u32)i >= c) break;
-          const u32 op = xm[i] >> RW_MOP;
-          if (op == 2) {  // delete: every present element is tombstoned
-#pragma unroll
-            for (int j = 0; j < i; ++j) sv[j] |= (sv[j] & 1u) << 1;
-            continue;
-          }
-          if (op == 1) {  // move: pops the live element (the only one here)
-            u32 cand = 0;
-#pragma unroll
-            for (int j = 0; j < i; ++j) cand |= (u32)(sv[j] == 1u) << j;
-            if (cand & (cand - 1)) {
-              hard = true;
-              break;
-            }
-#pragma unroll
-            for (int j = 0; j < i; ++j)
-              if ((cand >> j) & 1u) sv[j] = 0u;
-          }
-          sv[i] = 1u;
-        }
-        if (!hard) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            if ((u32)i < c) S.st[xm[i] & RW_MEV] = (u8)sv[i];
-          continue;
-        }
-      }
-#endif
       for (u32 i = 0; i < c; ++i) {
         const u32 xm = S.mem[b + i];
         const u32 x = xm & RW_MEV, op = xm >> RW_MOP;
@@ -1159,7 +969,6 @@ __device__ __forceinline__ u32 rga_wave_list(const smx_rga_ops& o, const SRC src
         }
         if (op == 1) {  // move: pops the live element first in list order
           u32 best = RW_NIL;
-#if RW_W0G
           u64 wb = 0;  // best's word 0: read when a second candidate shows up, then kept
           bool wbl = false;
           for (u32 j = 0; j < i; ++j) {
@@ -1180,12 +989,6 @@ __device__ __forceinline__ u32 rga_wave_list(const smx_rga_ops& o, const SRC src
               wb = wy;
             }
           }
-#else
-          for (u32 j = 0; j < i; ++j) {
-            const u32 y = S.mem[b + j] & RW_MEV;
-            if (S.st[y] == 1 && (best == RW_NIL || ev_lt(S, src, o, y, best))) best = y;
-          }
-#endif
           if (best != RW_NIL) S.st[best] = 0;
         }
         S.st[x] = 1;
@@ -1210,9 +1013,7 @@ __device__ __forceinline__ u32 rga_wave_list(const smx_rga_ops& o, const SRC src
     if (live) {
       const u32 q = m + (u32)__popcll(ball & lt);
       S.gp[q] = (u16)e;
-#if RW_W0R
       S.gs[q] = w0r[k];  // (the hash table under gs is dead after step 2)
-#endif
     }
     m += (u32)__popcll(ball);
   }
@@ -1222,13 +1023,7 @@ __device__ __forceinline__ u32 rga_wave_list(const smx_rga_ops& o, const SRC src
     const u32 a = (u32)k * 64u + lane;
     if (a < m) {
       pay[k] = S.gp[a];
-#if RW_W0R
       key[k] = S.gs[a];
-#elif RW_W0G
-      key[k] = src.w0(pay[k]);
-#else
-      key[k] = S.w0[pay[k]];
-#endif
     }
   }
   wave_lds_sync();  // gp / the hash table are rewritten below
@@ -1276,7 +1071,7 @@ __global__ void __launch_bounds__(WAVE * RW_WAVES) RW_OCC k_rga_wave(smx_rga_ops
       // the lane id laundered per list: otherwise the compiler hoists every lane-derived
       // constant of the list code out of the loop and keeps it live
       u32 ln = lane;
-      if (RW_LAUNDER) asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
+      asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
       u32 m;
       auto run = [&](auto src) {
         if (cnt <= 64) return rga_wave_list<1>(o, src, l, s0, cnt, lds[w], ln, tomb != 0, tmp_v, tmp_s, scnt);
@@ -1660,14 +1455,11 @@ static int rga_impl(const smx_rga_ops* ops, const smx_rga_out* out, void* ws, si
     g_cus = cus > 0 ? cus : 256;
     g_rr_grid = g_cus * RR_PER_CU;
   }
-  const bool direct = grouped && RGA_DIRECT;  // the list kernels read the columns in place
+  const bool direct = grouped;  // grouped calls: the list kernels read the input columns in place (no record pass)
   if (grouped) {  // the caller's events come list by list: no partition
     const int pgrid = (int)(SMX_CEIL_DIV(n, (i64)BLOCK) < 8192 ? SMX_CEIL_DIV(n, (i64)BLOCK) : 8192);
-    if (direct)
-      hipLaunchKernelGGL(k_rga_gbounds, dim3((int)SMX_CEIL_DIV((i64)pgrid, (i64)4)), dim3(BLOCK), 0, st, *ops, lstart,
-                         scnt - RGA_CS_MAX, err);
-    else
-      hipLaunchKernelGGL(k_rga_pack, dim3(pgrid), dim3(BLOCK), 0, st, *ops, rec, lstart, scnt - RGA_CS_MAX, err);
+    hipLaunchKernelGGL(k_rga_gbounds, dim3((int)SMX_CEIL_DIV((i64)pgrid, (i64)4)), dim3(BLOCK), 0, st, *ops, lstart,
+                       scnt - RGA_CS_MAX, err);
   } else {  // records grouped by list: LSD passes over the list id, ping-pong into rec
     int npass = 1;
     while (npass < 4 && ((u64)(nl - 1) >> (8 * npass)) != 0) ++npass;
@@ -1676,7 +1468,7 @@ static int rga_impl(const smx_rga_ops* ops, const smx_rga_out* out, void* ws, si
     u32* dstart = tsum + hscan_tsum_bytes(nblk, 256) / 4;
     u64* rbuf[2] = {npass % 2 ? rec : rec2, npass % 2 ? rec2 : rec};
     u32* kbuf[2] = {keys, keys2};
-    if (RGA_MSD && npass == 2) {  // high byte by the global pass, low byte per bucket
+    if (npass == 2) {  // high byte by the global pass, low byte per bucket
       hipLaunchKernelGGL(k_rrec_hist<true>, dim3(nblk), dim3(BLOCK), 0, st, o, nullptr, 8, rhist, err);
       // (one-launch column scan with the bucket starts from its last workgroup, on a
       // [digit][tile] histogram: 18.7 + 34.3 us against hscan's 22 + 28.8, profiles/r04_ac)

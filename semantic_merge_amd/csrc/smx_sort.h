@@ -12,9 +12,6 @@
 #ifndef RADIX_ITEMS
 #define RADIX_ITEMS 16
 #endif
-#ifndef RADIX_HIST_AGG
-#define RADIX_HIST_AGG 0
-#endif
 #define RADIX_TILE (BLOCK * RADIX_ITEMS)   // 4096 pairs per block and pass (16-pair digit runs)
 #define RADIX_SEG (RADIX_TILE / NWAVES)     // contiguous elements per wave
 
@@ -31,20 +28,9 @@ static __global__ void __launch_bounds__(BLOCK) k_radix_hist(const u64* __restri
     const i64 i = base + it * BLOCK + threadIdx.x;
     d[it] = i < n ? (u32)(keys[i] >> shift) & 255u : 256u;
   }
-#if RADIX_HIST_AGG
-  // one LDS atomic per distinct digit per wave (slow-varying digits, e.g. timestamp
-  // bytes, would otherwise serialise on one bin)
-  const u64 lt = lanemask_lt();
-#pragma unroll
-  for (int it = 0; it < RADIX_ITEMS; ++it) {
-    const u64 peers = wave_peers<8>(d[it] & 255u, d[it] < 256u);
-    if (d[it] < 256u && (peers & lt) == 0) atomicAdd(&h[d[it]], (u32)__popcll(peers));
-  }
-#else
 #pragma unroll
   for (int it = 0; it < RADIX_ITEMS; ++it)
     if (d[it] < 256u) atomicAdd(&h[d[it]], 1u);
-#endif
   __syncthreads();
   hist[(i64)blockIdx.x * 256 + threadIdx.x] = h[threadIdx.x];
 }

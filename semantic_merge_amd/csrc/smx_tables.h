@@ -228,18 +228,12 @@ __global__ void k_tb_unskip(TbArgs A0, const u32* __restrict__ lst, u32* __restr
 }
 
 #define TBR_NT 1024
-#ifndef SMX_XCD_TB
-#define SMX_XCD_TB 1
-#endif
 #ifndef TBR_TK
 #define TBR_TK 16
 #endif
 // TBR_TK: tiles per wave step in k_tb_reduce
 #ifndef TBR_U
 #define TBR_U 2         // records per lane and tile in a k_tb_reduce step (longer runs: the tail loop)
-#endif
-#ifndef TBR_PREFETCH
-#define TBR_PREFETCH 1  // k_tb_reduce loads the next step's run bounds before this step's records are used
 #endif
 
 // One workgroup per bucket: LDS max over record indices, then each symbol's
@@ -280,7 +274,7 @@ __global__ void __launch_bounds__(TBR_NT) k_tb_reduce(TbArgs A0, const u32* __re
   const TbArgs A = tb_load(A0);
   // neighbouring buckets on one XCD: a tile's runs of buckets b and b + 1 share their
   // boundary lines, which are then fetched into one L2 only
-  const u32 b = SMX_XCD_TB ? (u32)xcd_item(blockIdx.x, gridDim.x) : blockIdx.x;
+  const u32 b = (u32)xcd_item(blockIdx.x, gridDim.x);
   for (u32 i = threadIdx.x; i < A.width; i += TBR_NT) tA[i] = tF[i] = tC[i] = 0;
   __syncthreads();
   auto put = [&](u32 q, u64 rb) {
@@ -311,10 +305,9 @@ __global__ void __launch_bounds__(TBR_NT) k_tb_reduce(TbArgs A0, const u32* __re
     }
   };
   u32 lo_n = 0, hi_n = 0;
-  if (TBR_PREFETCH) bounds(wv * TBR_TK, &lo_n, &hi_n);
+  bounds(wv * TBR_TK, &lo_n, &hi_n);
   for (int t0 = wv * TBR_TK; t0 < nt; t0 += NW * TBR_TK) {
-    u32 lo = lo_n, hi = hi_n;
-    if (!TBR_PREFETCH) bounds(t0, &lo, &hi);
+    const u32 lo = lo_n, hi = hi_n;
     u32 q[TBR_TK][TBR_U];
 #pragma unroll
     for (int k = 0; k < TBR_TK; ++k) {
@@ -326,7 +319,7 @@ __global__ void __launch_bounds__(TBR_NT) k_tb_reduce(TbArgs A0, const u32* __re
         q[k][u] = i < hk ? __builtin_nontemporal_load(&rec[rb + i]) : ~0u;
       }
     }
-    if (TBR_PREFETCH) bounds(t0 + NW * TBR_TK, &lo_n, &hi_n);
+    bounds(t0 + NW * TBR_TK, &lo_n, &hi_n);
 #pragma unroll
     for (int k = 0; k < TBR_TK; ++k)
 #pragma unroll

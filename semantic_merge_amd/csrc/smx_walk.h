@@ -268,8 +268,6 @@ __device__ u32 replay_region(const WalkArgs& W, u32 p, ReplayState& st, u32* nco
 // window's in-window candidates in its slots; wtot[w] = all of the window's
 // candidates.  Re-running it (sharded walk rounds) rewrites the same slots.  Block
 // 0 also resets the walk's counters in meta.
-// (cslot and wtot carry no __restrict__: k_boundary_cc's last block reads what the
-// other blocks wrote there)
 __device__ __forceinline__ void boundary_body(WalkArgs W0, ComposeMeta* meta, u32* cslot,
                                               const u32* __restrict__ wcand, u32* wtot,
                                               u64* __restrict__ skipbits, u64 nskipw) {
@@ -316,22 +314,6 @@ __global__ void __launch_bounds__(BLOCK) k_boundary(WalkArgs W0, ComposeMeta* me
                                                     const u32* __restrict__ wcand, u32* wtot,
                                                     u64* __restrict__ skipbits, u64 nskipw) {
   boundary_body(W0, meta, cslot, wcand, wtot, skipbits, nskipw);
-}
-
-// Fused steps of small merges (launch-bound): every block counts itself done and the
-// last one runs the next single-block step, after a device-scope fence each side (the
-// other blocks' writes are then visible to it); it also resets the counter, which the
-// plan's meta zero-fill started at 0.
-__device__ __forceinline__ bool walk_last_block(u32* ctr) {
-  __shared__ u32 last;
-  __threadfence();
-  __syncthreads();
-  if (threadIdx.x == 0) last = atomicAdd(ctr, 1u) == gridDim.x - 1 ? 1u : 0u;
-  __syncthreads();
-  if (!last) return false;
-  __threadfence();
-  if (threadIdx.x == 0) *ctr = 0u;
-  return true;
 }
 
 // One thread per window: its candidate slots -> cand[] at the window's offset
@@ -415,16 +397,6 @@ __global__ void __launch_bounds__(S1_NT) k_cand_scan_compact(WalkArgs W0, const 
                                                              const u32* __restrict__ cslot, u32* __restrict__ out) {
   __shared__ u32 s[S1_NT / WAVE + 1];
   cand_scan_compact_body<S1_NT>(walk_load(W0), wtot, woff, cap, total_lo, cslot, out, s);
-}
-// k_boundary, then (its last block) k_cand_scan_compact: one launch
-__global__ void __launch_bounds__(BLOCK) k_boundary_cc(WalkArgs W0, ComposeMeta* meta, u32* cslot,
-                                                       const u32* __restrict__ wcand, u32* wtot,
-                                                       u64* __restrict__ skipbits, u64 nskipw, u32* woff, u64 cap,
-                                                       u32* total_lo, u32* cand) {
-  boundary_body(W0, meta, cslot, wcand, wtot, skipbits, nskipw);
-  if (!walk_last_block(&meta->wk_done[0])) return;
-  __shared__ u32 s[NWAVES + 1];
-  cand_scan_compact_body<BLOCK>(walk_load(W0), wtot, woff, cap, total_lo, cslot, cand, s);
 }
 
 // Incoming open region (sharded merge): the previous shards' walk ended with
@@ -541,15 +513,6 @@ __global__ void __launch_bounds__(S1_NT) k_cluster_fused(WalkArgs W0, const u32*
                                                          u32* total_lo) {
   __shared__ u32 s[S1_NT / WAVE + 1];
   cluster_fused_body<S1_NT>(W0, cand, q, pm, nconf, meta, nreal, coff, cap, total_lo, s);
-}
-// k_replay_q, then (its last block) k_cluster_fused: one launch
-__global__ void __launch_bounds__(BLOCK) k_replay_q_cl(WalkArgs W0, const u32* __restrict__ cand, ComposeMeta* meta,
-                                                       u32* q, u32* nconf, u32* pm, u32* nreal, u32* coff, u64 cap,
-                                                       u32* total_lo) {
-  replay_q_body(W0, cand, meta, q, nconf);
-  if (!walk_last_block(&meta->wk_done[1])) return;
-  __shared__ u32 s[NWAVES + 1];
-  cluster_fused_body<BLOCK>(W0, cand, q, pm, nconf, meta, nreal, coff, cap, total_lo, s);
 }
 
 // Writes the conflict pairs, skip-list entries and skip bits of every real

@@ -36,9 +36,6 @@
 #include "smx_common.h"
 
 #define WIN_CAP 2048               // max ops per window held in LDS
-#ifndef SMX_XCD_WIN
-#define SMX_XCD_WIN 1              // generic-plan windows dealt to XCDs in consecutive runs
-#endif
 #ifndef WIN_TGT
 #define WIN_TGT 1792               // default target window size, presorted path (SMX_WIN_TGT)
 #endif
@@ -54,14 +51,6 @@
 #define SYM_MASK 0x3fffffffu       // msym: symbol bits (n_sym <= 2^30)
 #define MS_HAS_A (1u << 30)
 #define MS_HAS_F (1u << 31)
-
-// Keys < kp among the four (or the first m) of a 16-byte LDS read.
-__device__ __forceinline__ int rk4(const uint4 x, u32 kp) {
-  return (x.x < kp) + (x.y < kp) + (x.z < kp) + (x.w < kp);
-}
-__device__ __forceinline__ int rk4(const uint4 x, u32 kp, int m) {
-  return (m > 0 && x.x < kp) + (m > 1 && x.y < kp) + (m > 2 && x.z < kp) + (m > 3 && x.w < kp);
-}
 
 // Four consecutive i32 stores as one 16-byte store (4-byte aligned address).
 typedef i32 __attribute__((ext_vector_type(4))) win_v4i;
@@ -259,77 +248,6 @@ __device__ __forceinline__ void win_rename_flags(const WinArgs& P, i64 w, u64 Mb
 #ifndef WF_MINB
 #define WF_MINB 8
 #endif
-#ifndef WF_DENSE_KINDS
-#define WF_DENSE_KINDS 1  // step 3's ballots over the dense index of the present kinds
-#endif
-#ifndef WF_BUCKET
-#define WF_BUCKET 1  // step 5 by interpolation buckets (0: counting rank over each group)
-#endif
-#ifndef WF_BF
-#define WF_BF 1      // branch-free per-item code in the load and merge phases
-#endif
-#ifndef WF_ONEATOM
-#define WF_ONEATOM 1 // step 5 places each slot at start + arrival rank (one LDS atomic per element, not two)
-#endif
-#ifndef WF_TIEFIX
-#define WF_TIEFIX 1  // wide windows: equal 32-bit keys in a bucket ranked on the full ids right there (no window re-rank)
-#endif
-#ifndef WF_LATEARGS
-#define WF_LATEARGS 0  // step 9 re-reads its kernel arguments: 63 -> 17 SGPR spills, but 28 B/lane of VGPR scratch spills (off)
-#endif
-#ifndef WF_RUNMERGE
-#define WF_RUNMERGE 0  // step 2 by timestamp-run heads (a search per run, not a merge path per thread):
-                       // config 3 window 1.225 -> 1.230 ms, config 5 wide 0.907 -> 0.960 ms; off (profiles/r04_e, r04_f)
-#endif
-#ifndef WF_KPBAL
-#define WF_KPBAL 0   // partial-chunk kinds counted by peers ballots (one LDS atomic per (wave, kind)): 1.225 -> 1.235 ms,
-                     // and 1.395 ms together with WF_RUNMERGE (+21% VALU in that build); off (profiles/r04_f)
-#endif
-#ifndef WF_RANK8
-#define WF_RANK8 0   // step 5's bucket rank by 8 predicated compares (the loop only for larger buckets): window 1.223 -> 1.260 ms, off (profiles/r04_d)
-#endif
-#ifndef WF_BK16
-#define WF_BK16 1    // bucket-ordered 16-bit key prefixes for the rank loop (window 1.329 -> 1.286 ms, profiles/r03_e/ab.txt)
-#endif
-#ifndef WF_FUSEFIN
-#define WF_FUSEFIN 1  // step 5's final order written by the rank loop itself: window 1.248 -> 1.227 ms (profiles/r03_q)
-#endif
-#ifndef WF_BZ4
-#define WF_BZ4 1     // step 5's bucket counters zeroed in step 4's last phase (one barrier fewer)
-#endif
-#ifndef WF_OUT2
-#define WF_OUT2 1    // steps 7-9 staged by final slot (inv), four slots per thread, 16-byte stores: window 1.271 -> 1.233 ms (profiles/r03_m/ab.txt)
-#endif
-#ifndef WF_RUNS
-#define WF_RUNS 1    // the normal presorted windows order by runs and (kind, run) groups (no merge / multisplit)
-#endif
-#ifndef WF_HBATCH
-#define WF_HBATCH 0  // run-grouped step h, 1: the ITEMS buckets' ends and first members read together:
-                     // window 1.181 -> 1.439 ms on config 3 (more live registers), off
-#endif
-#ifndef WF_LOREG
-#define WF_LOREG 1  // run-grouped step h: a bucket's start from the op's slot and arrival rank (no LDS read)
-#endif
-#ifndef WF_HEADLIST
-#define WF_HEADLIST 0  // run-grouped step a, 1: every head binary-searches a list of the other part's
-                       // heads at once (three more barriers): window 1.196 -> 1.241 ms on config 3,
-                       // wide 0.409 -> 0.416 on config 5 (profiles/r05_x), off; 0: one head at a time
-                       // with the whole wave, a 64-way search of the other part's timestamps
-#endif
-#ifndef WF_GAGG
-#define WF_GAGG 1  // step c's group counts aggregated per wave: 1 the wide windows, 2 every window
-#endif
-#ifndef WF_RUNS_WIDE
-#define WF_RUNS_WIDE 1  // ... and the wide ones (config 5: one run per window)
-#endif
-#ifndef WF_STB_KIND
-#define WF_STB_KIND 1  // v0 / v1 staged for moves and renames only (the other kinds output neither)
-#endif
-#ifdef WF_WPE
-#define WF_BOUNDS __launch_bounds__(WF_NT) __attribute__((amdgpu_waves_per_eu(WF_WPE, WF_WPE)))
-#else
-#define WF_BOUNDS __launch_bounds__(WF_NT, WF_MINB)
-#endif
 template <int CAP, int NT, bool DBG, bool MAP, bool RUNS = false>
 __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(WinArgs P) {
   // CAP ops per window on NT threads: (2048, 512) four windows per CU; (8192, 1024) one
@@ -338,18 +256,16 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
   // equal 32-bit rank keys resolved in the rank loop itself (the wide window, whose
   // 8192-op groups see ~1 such pair in 128 and whose exact re-rank would be quadratic);
   // the small windows flag them for the window re-rank (fewer registers in the loop)
-  constexpr bool TIEFIX = WF_TIEFIX && CAP > WF_CAP;
+  constexpr bool TIEFIX = CAP > WF_CAP;
   static_assert(CAP % NT == 0 && NCH <= 2 * WAVE && CAP <= 65536, "window geometry");
   __shared__ __attribute__((aligned(16))) u64 sts[CAP];  // element space: timestamps; later slot-space rank keys
   __shared__ __attribute__((aligned(16))) u16 sord[CAP];  // S order (merge), later the final order
   __shared__ u16 fin[CAP];        // slot -> element, later rename ranks
   __shared__ u16 sl[CAP];         // element -> slot, later rank -> slot, later posl
   __shared__ u8 skind[CAP];
-  __shared__ __attribute__((aligned(16))) u8 skS[CAP];  // kinds in S order, later by slot (WF_OUT2)
-#if WF_OUT2
+  __shared__ __attribute__((aligned(16))) u8 skS[CAP];  // kinds in S order, later by slot (steps 7-9)
   __shared__ u16 inv[CAP];        // element -> final slot
   __shared__ u64 tbase[SMX_N_KINDS]; // T of a kind's slot x = tbase[kind] + x
-#endif
   __shared__ u64 gbits[NCH];       // group-start bits over slots, later candidate ballots
   __shared__ u16 ccnt[NCH][SMX_N_KINDS];
   __shared__ u16 rc[NCH][2];
@@ -422,9 +338,7 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
   // T-order segment starts; window offsets = chunk prefix at the window start + kinds
   // of the <= 255 ops between that chunk start and the window start (per branch)
   const u64 base_v = t <= SMX_N_KINDS ? P.meta->base[t] : 0ull;
-#if WF_DENSE_KINDS
   const u32 kmask_r = P.meta->kmask[0] | P.meta->kmask[1];
-#endif
   // a window that already failed the plan (dense groups: every window does) makes the
   // rest of the launch pointless: checked after the load phase, no extra round trip
   const u64 failed = t == 0 ? P.meta->f_fail : 0ull;
@@ -462,7 +376,6 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
   }
   u32 none_mv = 0;  // moves with a None value (prefix fix-up)
   u32 vb_a = 0, vb_f = 0, vb_c = 0;  // OR of (value + 1): widths of the packed final-state table
-#if WF_BF
   // branch-free: the LDS slots past sz take harmless values (every later phase reads
   // slots < sz only), the rest is selects -- no exec-mask bookkeeping per item
   static_assert(NT * ITEMS <= CAP, "item slots inside the LDS arrays");
@@ -483,28 +396,6 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     vb_f |= mv ? (u32)(v1_r[i] + 1) : 0u;
     vb_c |= rn ? (u32)(v1_r[i] + 1) : 0u;
   }
-#else
-#pragma unroll
-  for (int i = 0; i < ITEMS; ++i) {
-    const int e = t + NT * i;
-    if (e < sz) {
-      bad |= k_r[i] >= SMX_N_KINDS || sym_r[i] >= (u64)P.n_sym;
-      const u32 k = k_r[i] < SMX_N_KINDS ? k_r[i] : SMX_N_KINDS - 1;
-      sts[e] = ts_r[i];
-      skind[e] = (u8)k;
-      // the payload's first word: sym | the move's has-value bits (msym)
-      if (k == KMOVE) {
-        sym_r[i] = (sym_r[i] & SYM_MASK) | (v0_r[i] >= 0 ? MS_HAS_A : 0u) | (v1_r[i] >= 0 ? MS_HAS_F : 0u);
-        none_mv += v0_r[i] < 0 || v1_r[i] < 0;
-        vb_a |= (u32)(v0_r[i] + 1);
-        vb_f |= (u32)(v1_r[i] + 1);
-      } else {
-        sym_r[i] &= SYM_MASK;
-        if (k == KREN) vb_c |= (u32)(v1_r[i] + 1);
-      }
-    }
-  }
-#endif
   vb_a = wave_or_to_last(vb_a);
   vb_f = wave_or_to_last(vb_f);
   vb_c = wave_or_to_last(vb_c);
@@ -532,25 +423,6 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     return;
   }
   // window offsets: the partial-chunk kinds
-#if WF_KPBAL && WF_DENSE_KINDS
-  {
-    // one LDS atomic per (wave, kind) from the peers ballots over the dense index of the
-    // present kinds (per-lane atomics on a few hot counters serialise in the LDS);
-    // a wave's slots x = t + NT * u lie on one side of CH (WAVE divides CH)
-    static_assert(CH % WAVE == 0, "one side per wave");
-    const u32 kp0 = __builtin_amdgcn_readfirstlane(kmask_r);
-    const int kb0 = 32 - __clz((int)(max(__popc(kp0), 1u) - 1u));
-#pragma unroll
-    for (int u = 0; u < KP; ++u) {
-      const bool v = kpart[u] != 0xffffffffu;
-      const u32 k = v ? (kpart[u] < SMX_N_KINDS ? kpart[u] : SMX_N_KINDS - 1) : 0u;
-      const u64 peers = wave_peers_n((u32)__popc(kp0 & ((1u << k) - 1u)), v, kb0);
-      if (v && (peers & lanemask_lt()) == 0) atomicAdd(&woffk[k], (u32)__popcll(peers));
-      const u64 rb = __ballot(v && k == KREN);
-      if (lane == 0 && rb) atomicAdd(&woffk[SMX_N_KINDS + (t + NT * u >= CH)], (u32)__popcll(rb));
-    }
-  }
-#else
 #pragma unroll
   for (int u = 0; u < KP; ++u) {
     if (kpart[u] != 0xffffffffu) {
@@ -559,7 +431,6 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       if (k == KREN) atomicAdd(&woffk[SMX_N_KINDS + (t + NT * u >= CH)], 1u);
     }
   }
-#endif
 
   const int nch = (sz + WAVE - 1) / WAVE;
   auto group_of = [&](int p, int* gs_o, int* ge_o) {
@@ -596,10 +467,6 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     __shared__ u16 occpre[OW];
     __shared__ u16 lasth[NCH];       // last head at or before the end of each 64-op chunk
     __shared__ u32 rinfo[2];         // groups fit, R
-#if WF_HEADLIST
-    __shared__ u16 hpre[NCH + 1];    // heads before each chunk (and in all)
-    __shared__ u32 hna;              // the A part's heads (index of B's first head)
-#endif
     u16* sp = sl;                    // S position of each head's run (element space)
     u32* gcnt = reinterpret_cast<u32*>(sts);             // group counters, two u16 per word
     static_assert(GMAX / 2 * sizeof(u32) <= sizeof(sts), "group counters inside sts");
@@ -626,7 +493,6 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       // compiler, which would then run the head searches below as lane-divergent loops)
       const int c = __builtin_amdgcn_readfirstlane((NT * i) / WAVE + wv);
       if (lane == 0 && c < NCH) gbits[c] = hbr[i];
-#if !WF_HEADLIST
       // the heads of this chunk, one at a time with the whole wave: a 64-way search of
       // the other part for #{ops < v} (two or three rounds of one LDS read per lane)
       u64 hb = hbr[i];
@@ -656,69 +522,11 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
           atomicOr(&occ[spos >> 5], 1u << (spos & 31));
         }
       }
-#endif
     }
-#if WF_HEADLIST
-    if (t == 0) hna = 0xffffu;  // (no B part: every head is A's)
-#endif
     if (__syncthreads_or(dec)) {
       if (t == 0) atomicOr((unsigned long long*)&P.meta->f_fail, 1ull);
       return;
     }
-#if WF_HEADLIST
-    // the heads of both parts in one list, element order (A's first): hel[j], with the
-    // heads before each chunk from one wave's scan of the chunk ballots
-    u16* hel = sord;  // (free until step h)
-    if (wv == 0) {
-      const u32 h0 = lane < NCH ? (u32)__popcll(gbits[lane]) : 0u;
-      const u32 h1 = lane + WAVE < NCH ? (u32)__popcll(gbits[lane + WAVE]) : 0u;
-      const u32 i0 = wave_incl_sum_u32(h0), i1 = wave_incl_sum_u32(h1);
-      const u32 t0 = (u32)__builtin_amdgcn_readlane((int)i0, WAVE - 1);
-      if (lane < NCH) hpre[lane] = (u16)(i0 - h0);
-      if (lane + WAVE < NCH) hpre[lane + WAVE] = (u16)(t0 + i1 - h1);
-      if (lane == WAVE - 1) hpre[NCH] = (u16)(t0 + i1);
-    }
-    __syncthreads();
-    {
-      const u64 lt = lanemask_lt();
-#pragma unroll
-      for (int i = 0; i < ITEMS; ++i) {
-        const int e = t + NT * i;
-        const int c = __builtin_amdgcn_readfirstlane((NT * i) / WAVE + wv);
-        if ((hbr[i] >> lane) & 1ull) {
-          const u32 j = (u32)hpre[c] + (u32)__popcll(hbr[i] & lt);
-          hel[j] = (u16)e;
-          if (e == na) hna = j;
-        }
-      }
-    }
-    __syncthreads();
-    {
-      // each head: #{other part's ops < v} = the index of the other part's first head
-      // whose timestamp is >= v (that op starts a run), by a binary search of the head list
-      const u32 nH = hpre[NCH], nHA = hna == 0xffffu ? nH : hna;
-#pragma unroll
-      for (int i = 0; i < ITEMS; ++i) {
-        const int e = t + NT * i;
-        if (!((hbr[i] >> lane) & 1ull)) continue;
-        const u64 v = ts_r[i];
-        const bool sa = e < na;
-        const u32 end = sa ? nH : nHA;
-        u32 lo = sa ? nHA : 0u, hi = end;
-        while (lo < hi) {
-          const u32 mid = (lo + hi) >> 1;
-          if (sts[hel[mid]] < v) lo = mid + 1;
-          else hi = mid;
-        }
-        const int o0 = sa ? na : 0, no = sa ? nb : na;
-        const int cnt = lo < end ? (int)hel[lo] - o0 : no;
-        const int spos = (sa ? e : e - na) + cnt;
-        sp[e] = (u16)spos;
-        atomicOr(&occ[spos >> 5], 1u << (spos & 31));
-      }
-    }
-    __syncthreads();
-#endif
     RX_EXIT(1);
     // b. (wave 0) the last head of each chunk, the runs' dense index, the group count
     const u32 kpres = __builtin_amdgcn_readfirstlane(kmask_r);
@@ -788,15 +596,13 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
         // saves), one atomic per op
         bool agg = false;
         u32 r0 = 0;
-        if constexpr (WF_GAGG >= 2 || (WF_GAGG == 1 && CAP > WF_CAP)) {
+        if constexpr (CAP > WF_CAP) {
           const u64 vm = __ballot(e < sz);
           r0 = (u32)__builtin_amdgcn_readfirstlane((int)r);
-          // (WF_GAGG 2: also a wave over two runs, one more ballot)
-          agg = vm && __ballot(e < sz && r - r0 > (WF_GAGG >= 2 ? 1u : 0u)) == 0;
+          agg = vm && __ballot(e < sz && r - r0 > 0u) == 0;
         }
         if (agg) {
-          const u64 peers = WF_GAGG >= 2 ? wave_peers_n(dk << 1 | (r - r0), e < sz, kbits_r + 1)
-                                         : wave_peers_n(dk, e < sz, kbits_r);
+          const u64 peers = wave_peers_n(dk, e < sz, kbits_r);
           if (e < sz && (peers & lanemask_lt()) == 0)
             atomicAdd(&gcnt[g_r[i] >> 1], (u32)__popcll(peers) << (16 * (g_r[i] & 1)));
         } else if (e < sz) {
@@ -890,50 +696,19 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       // h. rank inside the bucket on (key, full id, side, index); the final order
       //    (per-lane loops: one op per bucket on average; a wave-uniform loop over the
       //    ITEMS buckets together spilled registers)
-#if WF_HBATCH
-      // every item's bucket end and first member read together (independent LDS reads:
-      // one round trip for the ITEMS buckets; a bucket holds one op on average), the
-      // rest of a bucket by the loop below
-      u32 hw_r[ITEMS], x0_r[ITEMS];
-#pragma unroll
-      for (int i = 0; i < ITEMS; ++i) {
-        const u32 b = b_r[i] == 0xffffffffu ? 0u : b_r[i];
-        const u32 b1 = b + 1 < (u32)CAP ? b + 1 : (u32)CAP - 1;
-        hw_r[i] = bcnt[b1 >> 1];
-        x0_r[i] = mkey[slot_r[i] - ar_r[i]];
-      }
-#endif
 #pragma unroll
       for (int i = 0; i < ITEMS; ++i) {
         const u32 b = b_r[i];
         if (b == 0xffffffffu) continue;
         const int e = t + NT * i;
         const u32 b1 = b + 1 < (u32)CAP ? b + 1 : (u32)CAP - 1;  // (branch-free bucket bounds)
-#if WF_LOREG
         const u32 lo = slot_r[i] - ar_r[i];  // (the bucket's start: this op's slot less its arrival rank)
-#else
-        const u32 lo = (bcnt[b >> 1] >> (16 * (b & 1))) & 0xffffu;
-#endif
-#if WF_HBATCH
-        const u32 hw = (hw_r[i] >> (16 * (b1 & 1))) & 0xffffu;
-#else
         const u32 hw = (bcnt[b1 >> 1] >> (16 * (b1 & 1))) & 0xffffu;
-#endif
         const u32 hi = b + 1 < (u32)CAP ? hw : (u32)sz, kp = hi_r[i];
         u32 c = 0;
         bool tie = false;
-#if WF_HBATCH
-        {  // the first member (lo < hi: this op is in the bucket)
-          const u32 x = x0_r[i];
-          c += x < kp;
-          tie |= (x == kp) & (lo != slot_r[i]);
-        }
-#pragma unroll 1
-        for (u32 q = lo + 1; q < hi; ++q) {
-#else
 #pragma unroll 1
         for (u32 q = lo; q < hi; ++q) {  // (own slot: x == kp, not a tie)
-#endif
           const u32 x = mkey[q];
           c += x < kp;
           tie |= (x == kp) & (q != slot_r[i]);
@@ -976,54 +751,6 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     dec = (a0 > 0 && na > 0 && prev_a > sts[0]) || (b0 > 0 && nb > 0 && prev_b > sts[na]);
     win_publish_widths(P.meta, &vbw[0][0], WAVES, vcur);
   }
-#if WF_RUNMERGE
-  // Run-head merge.  Inside a branch the timestamps never decrease, so an op's merged
-  // position is its branch index plus the other branch's ops before its timestamp run
-  // (A first on ties: for an A op the B ops with a smaller timestamp, for a B op the A
-  // ops with a smaller or equal one).  Only the first op of each run (a head) searches
-  // the other branch; the rest read their head's count.  (Config 2 / 3 windows hold ~14
-  // runs per branch, config 5's wide windows one: a few searches instead of a merge-path
-  // search and a merge step chain per thread.)
-  u64* rbits = gbits;  // [NCH] head bits over elements (gbits is next written in step 4)
-  u16* hl = fin;       // per wave: its heads' elements (fin is next written in step 3)
-  u16* roff = sl;      // per head element: the other branch's ops before its run (sl: step 3)
-  u64 hb[ITEMS];
-  int nh = 0;  // this wave's heads (wave-uniform)
-#pragma unroll
-  for (int i = 0; i < ITEMS; ++i) {
-    const int e = t + NT * i;
-    const bool valid = e < sz;
-    const u64 pv = sts[valid && e > 0 ? e - 1 : 0];
-    const bool head = valid && (e == 0 || e == na || pv != ts_r[i]);
-    if (!(SMX_DIAG && (P.ablate & 1))) dec |= valid && e != 0 && e != na && pv > ts_r[i];
-    hb[i] = __ballot(head);
-    if (lane == 0) rbits[(NT * i) / WAVE + wv] = hb[i];
-    if (head) hl[wv * (ITEMS * WAVE) + nh + (int)__popcll(hb[i] & lanemask_lt())] = (u16)e;
-    nh += (int)__popcll(hb[i]);
-  }
-  wave_lds_sync();  // this wave's head list, for its own lanes
-  for (int r = 0; r < nh; r += WAVE) {
-    if (r + lane < nh) {
-      const int e = hl[wv * (ITEMS * WAVE) + r + lane];
-      const u64 x = sts[e];
-      int lo = 0, hi = e < na ? nb : na;
-      if (e < na) {  // B ops with a smaller timestamp
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (sts[na + mid] < x) lo = mid + 1;
-          else hi = mid;
-        }
-      } else {  // A ops with a smaller or equal timestamp
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (sts[mid] <= x) lo = mid + 1;
-          else hi = mid;
-        }
-      }
-      roff[e] = (u16)lo;
-    }
-  }
-#else
 #pragma unroll
   for (int i = 0; i < ITEMS; ++i) {
     const int e = t + NT * i;
@@ -1042,7 +769,6 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       else hi = mid;
     }
     int ia = lo, ib = d0 - lo;
-#if WF_BF
     // ITEMS outputs, predicated (a thread past sz stores nothing)
 #pragma unroll
     for (int u = 0; u < ITEMS; ++u) {
@@ -1057,59 +783,11 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
         skS[d] = skind[e];
       }
     }
-#else
-    for (int d = d0; d < d1; ++d) {
-      const bool take_a = ia < na && (ib >= nb || sts[ia] <= sts[na + ib]);
-      const int e = take_a ? ia++ : na + ib++;
-      sord[d] = (u16)e;
-      skS[d] = skind[e];
-    }
-#endif
   }
-#endif
   if (__syncthreads_or(dec)) {
     if (t == 0) atomicOr((unsigned long long*)&P.meta->f_fail, 1ull);
     return;
   }
-#if WF_RUNMERGE
-  {
-    // each op's head: the last head at or before it -- in its own 64-op chunk (the
-    // ballot), else the last head of the nearest earlier chunk that has one (every
-    // chunk's head word read once per wave; lane broadcasts with the whole wave active)
-    const int nchw = (sz + WAVE - 1) / WAVE;
-    const u64 rw0 = lane < nchw ? rbits[lane] : 0ull;
-    const u64 rnz0 = __ballot(rw0 != 0);
-    const u64 rw1 = NCH > WAVE && WAVE + lane < nchw ? rbits[(WAVE + lane) % NCH] : 0ull;
-    const u64 rnz1 = NCH > WAVE ? __ballot(rw1 != 0) : 0ull;
-    auto bc64 = [](u64 v, int l) -> u64 {
-      return (u64)(u32)__builtin_amdgcn_readlane((int)(u32)v, l) |
-             ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), l) << 32);
-    };
-    const u64 lem = lanemask_lt() | (1ull << lane);
-#pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
-      const int c = (NT * i) / WAVE + wv;  // this wave's chunk (uniform)
-      if (c * WAVE >= sz) break;          // (uniform)
-      // the last non-empty chunk before c (chunk 0 starts with a head, so c > 0 has one)
-      const int cl = c & (WAVE - 1);
-      const u64 b0 = c < WAVE ? rnz0 & ((1ull << cl) - 1) : rnz0;
-      const u64 b1 = c < WAVE ? 0ull : rnz1 & ((1ull << cl) - 1);
-      const int wp = b1 ? WAVE + 63 - __clzll(b1) : (b0 ? 63 - __clzll(b0) : 0);
-      const u64 wpw = wp < WAVE ? bc64(rw0, wp & (WAVE - 1)) : bc64(rw1, wp & (WAVE - 1));
-      const int hprev = wp * WAVE + 63 - __clzll(wpw | 1ull);
-      const u64 below = hb[i] & lem;
-      const int e = t + NT * i;
-      if (e < sz) {
-        const int h = below ? c * WAVE + 63 - __clzll(below) : hprev;
-        const int pos = (e < na ? e : e - na) + (int)roff[h];
-        const u32 kr = k_r[i] < SMX_N_KINDS ? k_r[i] : SMX_N_KINDS - 1;
-        sord[pos] = (u16)e;
-        skS[pos] = (u8)kr;
-      }
-    }
-  }
-  __syncthreads();
-#endif
   WSTAMP(3);
   WF_EXIT(2);
 
@@ -1124,23 +802,17 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     mkr[j] = m < sz ? skS[m] : 0u;
   }
   const u64 ltm = lanemask_lt();
-#if WF_DENSE_KINDS
   // the ballots run over the dense index of the kinds present in the merge (k_khist's
   // kind masks): 6 kinds take 3 ballots instead of 5
   const u32 kpres = __builtin_amdgcn_readfirstlane(kmask_r);
   const int kbits = 32 - __clz((int)(max(__popc(kpres), 1u) - 1u));
-#endif
 #pragma unroll
   for (int j = 0; j < ITEMS; ++j) {
     const int m = t + NT * j;
     const int c = wv + WAVES * j;
     const bool valid = m < sz;
     const u32 k = mkr[j];
-#if WF_DENSE_KINDS
     const u64 peers = wave_peers_n((u32)__popc(kpres & ((1u << k) - 1u)), valid, kbits);
-#else
-    const u64 peers = wave_peers<5>(k, valid);
-#endif
     const u32 r = __popcll(peers & ltm);
     mkr[j] = k | (r << 8);
     if (valid && r == 0) {
@@ -1179,7 +851,7 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       const int p = kbase[k] + ccnt[wv + WAVES * j][k] + (mkr[j] >> 8);
       fin[p] = (u16)me[j];
       sl[me[j]] = (u16)p;
-      if (WF_OUT2) skS[p] = (u8)k;  // (skS was read in the prologue, before two barriers)
+      skS[p] = (u8)k;  // (skS was read in the prologue, before two barriers)
     }
   }
   __syncthreads();
@@ -1194,11 +866,7 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     bool f = false;
     if (p < sz) {
       const int e = fin[p];
-#if WF_OUT2
       f = (p == (int)kbase[skS[p]]) || (sts[fin[p - 1]] != sts[e]);  // (skS: kinds by slot)
-#else
-      f = (p == (int)kbase[skind[e]]) || (sts[fin[p - 1]] != sts[e]);
-#endif
     }
     const u64 b = __ballot(f);
     if (lane == 0 && (p >> 6) < NCH) gbits[p >> 6] = b;
@@ -1218,19 +886,18 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       sl[e] = 0xffffu;
     }
   }
-#if WF_BUCKET && WF_BZ4
   // step 5's bucket counters (the upper half of sts: the timestamps are dead)
   for (int i = t; i < CAP / 2; i += NT) reinterpret_cast<u32*>(sts)[CAP + i] = 0u;
-#endif
   __syncthreads();
   WSTAMP(9);
   WF_EXIT(7);
 
-  // 5. order each group by (oid, side, index): counting rank over the group on the
-  //    32-bit keys, four per LDS read.  Two keys of a group that are equal (about one
-  //    window in 10^4 on random ids; every duplicate id) get the same rank and leave
-  //    a rank without a slot: such a window is re-ranked exactly on (oid_hi, oid_lo,
-  //    slot) -- slot order is (side, index) order inside a group.
+  // 5. order each group by (oid, side, index): interpolation buckets over the group on
+  //    the 32-bit keys, then a rank inside each bucket.  Two keys of a group that are
+  //    equal (about one window in 10^4 on random ids; every duplicate id) are flagged
+  //    (btie): such a window is re-ranked exactly on (oid_hi, oid_lo, slot) -- slot
+  //    order is (side, index) order inside a group (the wide window resolves them in
+  //    the rank loop itself: TIEFIX).
   // the group bounds of a wave's 64 consecutive slots from one read of every
   // group-start word (nch <= 32) and lane broadcasts: no dependent LDS chain
   // (NCH > 64: a second word per lane, gw1 / gnz1 for chunks 64..127)
@@ -1249,31 +916,19 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     return i < WAVE ? a : b;
   };
   const u64 le_mask = lanemask_lt() | (1ull << lane);
-#if WF_BUCKET
-#endif
-#if WF_BUCKET
   // interpolation buckets over slot space: slot p of group [gs, ge) goes to bucket
   // gs + (ge - gs) * key / 2^32 (one op per bucket on random ids); 16-bit counters,
   // two per word, in the upper half of sts (free until step 7)
   u32* bcnt = reinterpret_cast<u32*>(sts) + CAP;
-#if WF_BK16
   // the top 16 bits of each key in bucket order (the last quarter of sts): the rank
   // loop compares them without the slot -> key chain, the full key only on a tie
   u16* bk16 = reinterpret_cast<u16*>(reinterpret_cast<u32*>(sts) + CAP + CAP / 2);
   u32 own_r[ITEMS];
-#endif
-#if !WF_BZ4
-  for (int i = t; i < CAP / 2; i += NT) bcnt[i] = 0u;
-  __syncthreads();
-#endif
   u32 bk_r[ITEMS];
   u32 kp_r[ITEMS];
-#if WF_ONEATOM
   u32 ar_r[ITEMS];  // arrival rank inside the bucket (the count atomic's return value)
-#endif
 #pragma unroll
   for (int j = 0; j < ITEMS; ++j) bk_r[j] = 0xffffffffu, kp_r[j] = 0u;
-#endif
 #pragma unroll
   for (int j = 0; j < ITEMS; ++j) {
     const int wi = __builtin_amdgcn_readfirstlane((NT * j) / WAVE + wv);  // this wave's slot chunk
@@ -1311,47 +966,14 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     const int gs = below ? wi * WAVE + 63 - __clzll(below | 1ull) : prevS;
     int ge = above ? wi * WAVE + __ffsll((unsigned long long)(above | (1ull << 63))) - 1 : nextS;
     ge = ge < sz ? ge : sz;
-    if (p >= sz) continue;
-#if WF_BUCKET
-    {
+    if (p < sz) {
       const u32 kp = pkey[p];
       const u32 b = (u32)gs + (u32)(((u64)(u32)(ge - gs) * kp) >> 32);
       kp_r[j] = kp;
       bk_r[j] = b;
-#if WF_ONEATOM
       ar_r[j] = (atomicAdd(&bcnt[b >> 1], 1u << (16 * (b & 1))) >> (16 * (b & 1))) & 0xffffu;
-#else
-      atomicAdd(&bcnt[b >> 1], 1u << (16 * (b & 1)));
-#endif
-      continue;
     }
-#endif
-    int r = p;
-    if (ge - gs > 1 && !(SMX_DIAG && (P.ablate & 2))) {
-      const u32 kp = pkey[p];
-      const uint4* pv = reinterpret_cast<const uint4*>(pkey);
-      const int q0 = gs & ~3;
-      int c = 0;
-      int q = q0;
-      for (; q + 8 <= ge; q += 8) {  // 2 x 16 bytes of keys per step in flight
-        const uint4 x0 = pv[q / 4], x1 = pv[q / 4 + 1];
-        c += rk4(x0, kp) + rk4(x1, kp);
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {  // fewer left: up to 2 more reads, masked
-        const int qq = q + 4 * u;
-        if (qq < ge) c += rk4(pv[qq / 4], kp, ge - qq);
-      }
-      if (q0 < gs) c -= rk4(pv[q0 / 4], kp, gs - q0);  // slots before the group
-      r = gs + c;
-    }
-    sord[r] = fin[p];
-    sl[r] = (u16)p;  // sl now maps rank -> slot
-#if WF_OUT2
-    inv[fin[p]] = (u16)r;
-#endif
   }
-#if WF_BUCKET
   {
     __syncthreads();
     // exclusive scan of the CAP counters: CAP / NT per thread (two 16-bit ones per word)
@@ -1372,8 +994,7 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     }
     __syncthreads();
     // scatter the slots into their buckets (sl: bucket position -> slot); the counters
-    // become the bucket ends (WF_ONEATOM: they stay the starts; position = start +
-    // arrival rank, no second atomic)
+    // stay the bucket starts (position = start + arrival rank, no second atomic)
     u32 lo_r[ITEMS];
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
@@ -1381,18 +1002,11 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       lo_r[j] = 0;
       if (b == 0xffffffffu) continue;
       const u32 sh = 16 * (b & 1);
-#if WF_ONEATOM
       lo_r[j] = (bcnt[b >> 1] >> sh) & 0xffffu;
       const u32 pos = lo_r[j] + ar_r[j];
-#else
-      const u32 old = atomicAdd(&bcnt[b >> 1], 1u << sh);
-      const u32 pos = (old >> sh) & 0xffffu;
-#endif
       sl[pos] = (u16)((NT * j) / WAVE * WAVE + wv * WAVE + lane);
-#if WF_BK16
       own_r[j] = pos;
       bk16[pos] = (u16)(kp_r[j] >> 16);
-#endif
     }
     __syncthreads();
     // rank inside the bucket on the 32-bit key
@@ -1402,42 +1016,14 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       const u32 b = bk_r[j];
       rr[j] = -1;
       if (b == 0xffffffffu) continue;
-#if WF_ONEATOM
       // bucket [start(b), start(b + 1)); the starts are an exclusive scan over every
       // bucket of the window (buckets past the last slot start at the total)
       const u32 lo = lo_r[j];
       const u32 e = b + 1 < (u32)CAP ? (bcnt[(b + 1) >> 1] >> (16 * ((b + 1) & 1))) & 0xffffu : (u32)sz;
-#else
-      const u32 e = (bcnt[b >> 1] >> (16 * (b & 1))) & 0xffffu;
-      const u32 lo = b ? (bcnt[(b - 1) >> 1] >> (16 * ((b - 1) & 1))) & 0xffffu : 0u;
-#endif
       const u32 kp = kp_r[j];
-      u32 c = 0, eq = 0;
-#if WF_BK16
+      u32 c = 0, eq = 1;
       const u32 k16 = kp >> 16, own = own_r[j];
-      eq = 1;
-#if WF_RANK8
-      // buckets of at most 8 (all but ~1e-5 of the elements on random ids): eight
-      // predicated compares, no lane-divergent loop (whose exec-mask bookkeeping is
-      // scalar work, the window's scarcest issue slot); larger buckets and equal top
-      // halves take the general loop below
-      {
-        const u32 nb = e - lo;
-        bool gen = nb > 8;
-#pragma unroll
-        for (u32 i = 0; i < 8; ++i) {
-          const u32 q = lo + i;
-          const u32 x = bk16[q];  // (past the bucket: masked; LDS reads never fault)
-          const bool in = i < nb && q != own;
-          c += (in && x < k16) ? 1u : 0u;
-          gen |= in && x == k16;
-        }
-        if (gen) c = 0;
-        for (u32 q = gen ? lo : e; q < e; ++q) {
-#else
-      {
       for (u32 q = lo; q < e; ++q) {
-#endif
         const u32 x = bk16[q];
         if (q == own) continue;
         if (x != k16) {
@@ -1458,27 +1044,17 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
           }
         }
       }
-      }
-#else
-      for (u32 q = lo; q < e; ++q) {
-        const u32 k = pkey[sl[q]];
-        c += k < kp;
-        eq += k == kp;
-      }
-#endif
       btie |= eq > 1;
       rr[j] = (int)(lo + c);
-      if (WF_FUSEFIN && !DBG) {
+      if (!DBG) {
         // the final order at once: nothing in this loop reads sord or inv, and the
         // rank -> slot map is not needed after step 5 (the exact re-rank rebuilds it)
         const int e = fin[(NT * j) / WAVE * WAVE + wv * WAVE + lane];
         sord[rr[j]] = (u16)e;
-#if WF_OUT2
         inv[e] = (u16)rr[j];
-#endif
       }
     }
-    if (!(WF_FUSEFIN && !DBG)) {
+    if (DBG) {
       __syncthreads();
 #pragma unroll
       for (int j = 0; j < ITEMS; ++j) {
@@ -1487,13 +1063,10 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
         const int e = fin[p];
         sord[rr[j]] = (u16)e;
         sl[rr[j]] = (u16)p;  // sl maps rank -> slot (the diagnostic order check)
-#if WF_OUT2
         inv[e] = (u16)rr[j];
-#endif
       }
     }
   }
-#endif
   __syncthreads();
   if (DBG) {  // diagnostics: the group order against the slot-space keys (dbg words 5, 17, 18)
     for (int r = t + 1; r < sz; r += NT) {
@@ -1538,18 +1111,8 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       }
     }
   };
-  bool tie = false;
-#if WF_BUCKET
-  tie = btie;
-#else
-#pragma unroll
-  for (int j = 0; j < ITEMS; ++j) {
-    const int r = t + NT * j;
-    if (r < sz) tie |= sl[r] == 0xffffu;
-  }
-#endif
   rename_ranks(false);
-  const bool any_tie = __syncthreads_or(tie);
+  const bool any_tie = __syncthreads_or(btie);
   WSTAMP(21);
   if (any_tie) {
     // exact ranks from the full ids (global memory; rare)
@@ -1573,9 +1136,7 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     for (int r = t; r < sz; r += NT) {
       const int e = fin[sl[r]];
       sord[r] = (u16)e;
-#if WF_OUT2
       inv[e] = (u16)r;
-#endif
     }
     __syncthreads();
     rename_ranks(true);
@@ -1619,7 +1180,6 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
   u32* st_a = (u32*)sts;             // [CAP] sym | flags
   i32* st_b = (i32*)sts + CAP;   // [CAP] v0, then v1
   u16* posl = sl;
-#if WF_OUT2
   // by final slot: each element's owner stores its payload at inv[element]
   int xi[ITEMS];
 #pragma unroll
@@ -1628,20 +1188,10 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     xi[i] = e < sz ? inv[e] : CAP;
     if (e < sz) {
       st_a[xi[i]] = sym_r[i];
-      if (!WF_STB_KIND || k_r[i] <= KREN) st_b[xi[i]] = v0_r[i];
+      if (k_r[i] <= KREN) st_b[xi[i]] = v0_r[i];  // (moves and renames only: the other kinds output neither v0 nor v1)
     }
   }
   if (t < SMX_N_KINDS) tbase[t] = base[t] + woffk[t] - kbase[t];
-#else
-#pragma unroll
-  for (int i = 0; i < ITEMS; ++i) {
-    const int e = t + NT * i;
-    if (e < sz) {
-      st_a[e] = sym_r[i];
-      st_b[e] = v0_r[i];
-    }
-  }
-#endif
   const int cntA = wtot[0], cntB = wtot[1];
   for (int x = t; x < RN; x += NT) {
     const int e = sord[R0 + x];
@@ -1665,42 +1215,16 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
         *own = rc[x >> 6][*s] + rown[x];
       },
       [&](int x) -> uint2 {
-#if WF_OUT2
         return make_uint2(st_a[R0 + x] & SYM_MASK, (u32)st_b[R0 + x]);
-#else
-        const int e = sord[R0 + x];
-        return make_uint2(st_a[e] & SYM_MASK, (u32)st_b[e]);
-#endif
       });
   WSTAMP(14);
   WF_EXIT(11);
   RX_EXIT(10);
 
-  // The output phases' kernel arguments are read again here from the kernarg segment
-  // (scalar loads through an opaque pointer): held from the kernel's start they were
-  // spilled to VGPR lanes and reloaded one v_readlane each in these phases.
-#if WF_LATEARGS == 2
-  // only the eight output pointers re-read here (the rest of the arguments as loaded)
-  WinArgs Q = P;
-  {
-    const WinArgs* K = kernarg_late<WinArgs>();
-    Q.out_order = K->out_order;
-    Q.out_addr = K->out_addr;
-    Q.out_file = K->out_file;
-    Q.out_ctx = K->out_ctx;
-    Q.msym = K->msym;
-    Q.tsrc = K->tsrc;
-    Q.tsym = K->tsym;
-    Q.Rstr = K->Rstr;
-  }
-#else
-  const WinArgs& Q = WF_LATEARGS ? *kernarg_late<WinArgs>() : P;
-#endif
   // 9. T-ordered records in final order (consecutive lanes -> consecutive T inside
   //    each kind: coalesced)
-  const u64 nall = (u64)(Q.na + Q.nb);
+  const u64 nall = (u64)(P.na + P.nb);
   const u64 nmv = base[KREN];
-#if WF_OUT2
   // four consecutive slots per thread (CAP = 4 * NT): one LDS read of each array,
   // and when the four share a kind (kinds are contiguous slot ranges) one 16-byte
   // store per output array
@@ -1708,7 +1232,7 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
   constexpr int OP = CAP / (4 * NT);
   static_assert(CAP == 4 * NT * OP, "four slots per thread and pass");
   auto gsrc = [&](i32 j) -> i32 {
-    return MAP ? Q.src_map[j] : (j < Q.na ? (i32)(Q.src_a + j) : (i32)(Q.src_b + (j - Q.na)));
+    return MAP ? P.src_map[j] : (j < P.na ? (i32)(P.src_a + j) : (i32)(P.src_b + (j - P.na)));
   };
   u32 k4[OP][4];
   u64 T4[OP][4];
@@ -1739,13 +1263,13 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     if (uni[ps]) {
       const u64 T = T4[ps][0];
       if (k4[ps][0] == KMOVE) {
-        st4(Q.out_order + T, gsrc(j4[0]), gsrc(j4[1]), gsrc(j4[2]), gsrc(j4[3]));
-        st4(Q.out_addr + T, bb[0], bb[1], bb[2], bb[3]);
-        st4(Q.out_ctx + T, -1, -1, -1, -1);
-        st4((i32*)Q.msym + T, (i32)aa[0], (i32)aa[1], (i32)aa[2], (i32)aa[3]);
+        st4(P.out_order + T, gsrc(j4[0]), gsrc(j4[1]), gsrc(j4[2]), gsrc(j4[3]));
+        st4(P.out_addr + T, bb[0], bb[1], bb[2], bb[3]);
+        st4(P.out_ctx + T, -1, -1, -1, -1);
+        st4((i32*)P.msym + T, (i32)aa[0], (i32)aa[1], (i32)aa[2], (i32)aa[3]);
       } else {
-        st4(Q.tsrc + (T - nmv), j4[0], j4[1], j4[2], j4[3]);
-        st4((i32*)Q.tsym + (T - nmv), (i32)(aa[0] & SYM_MASK), (i32)(aa[1] & SYM_MASK), (i32)(aa[2] & SYM_MASK),
+        st4(P.tsrc + (T - nmv), j4[0], j4[1], j4[2], j4[3]);
+        st4((i32*)P.tsym + (T - nmv), (i32)(aa[0] & SYM_MASK), (i32)(aa[1] & SYM_MASK), (i32)(aa[2] & SYM_MASK),
             (i32)(aa[3] & SYM_MASK));
       }
     } else {
@@ -1754,13 +1278,13 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
         const u64 T = T4[ps][u];
         if (u >= m4 || T >= nall) continue;  // (T >= nall: only a failed, discarded plan)
         if (k4[ps][u] == KMOVE) {
-          Q.out_order[T] = gsrc(j4[u]);
-          Q.out_addr[T] = bb[u];
-          Q.out_ctx[T] = -1;
-          Q.msym[T] = aa[u];
+          P.out_order[T] = gsrc(j4[u]);
+          P.out_addr[T] = bb[u];
+          P.out_ctx[T] = -1;
+          P.msym[T] = aa[u];
         } else {
-          Q.tsrc[T - nmv] = j4[u];
-          Q.tsym[T - nmv] = aa[u] & SYM_MASK;
+          P.tsrc[T - nmv] = j4[u];
+          P.tsym[T - nmv] = aa[u] & SYM_MASK;
         }
       }
     }
@@ -1771,7 +1295,7 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
   // round 2: v1 -> the move's newFile, the rename's chain value
 #pragma unroll
   for (int i = 0; i < ITEMS; ++i)
-    if (xi[i] < CAP && (!WF_STB_KIND || k_r[i] <= KREN)) st_b[xi[i]] = v1_r[i];
+    if (xi[i] < CAP && k_r[i] <= KREN) st_b[xi[i]] = v1_r[i];
   __syncthreads();
 #pragma unroll
   for (int ps = 0; ps < OP; ++ps) {
@@ -1782,57 +1306,17 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     const i32 bb[4] = {(i32)bv.x, (i32)bv.y, (i32)bv.z, (i32)bv.w};
     if (uni[ps]) {
       const u64 T = T4[ps][0];
-      st4(k4[ps][0] == KMOVE ? Q.out_file + T : Q.Rstr + (T - nmv), bb[0], bb[1], bb[2], bb[3]);
+      st4(k4[ps][0] == KMOVE ? P.out_file + T : P.Rstr + (T - nmv), bb[0], bb[1], bb[2], bb[3]);
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const u64 T = T4[ps][u];
         if (u >= m4 || T >= nall || k4[ps][u] > KREN) continue;
-        if (k4[ps][u] == KMOVE) Q.out_file[T] = bb[u];
-        else Q.Rstr[T - nmv] = bb[u];
+        if (k4[ps][u] == KMOVE) P.out_file[T] = bb[u];
+        else P.Rstr[T - nmv] = bb[u];
       }
     }
   }
-#else
-  // 9. T-ordered records in final order (consecutive lanes -> consecutive T inside
-  //    each kind: coalesced)
-  for (int x = t; x < sz; x += NT) {
-    const int e = sord[x];
-    const u32 k = skind[e];
-    const u64 T = base[k] + woffk[k] + (u32)(x - kbase[k]);
-    if (T >= nall) continue;  // only a failed (discarded) presorted plan can trip this
-    const i64 j = e < na ? a0 + e : bpos + e;
-    const u32 sa = st_a[e];
-    if (k == KMOVE) {
-      Q.out_order[T] = MAP ? Q.src_map[j] : (j < Q.na ? (i32)(Q.src_a + j) : (i32)(Q.src_b + (j - Q.na)));
-      Q.out_addr[T] = st_b[e];
-      Q.out_ctx[T] = -1;
-      Q.msym[T] = sa;
-    } else {
-      Q.tsrc[T - nmv] = (i32)j;
-      Q.tsym[T - nmv] = sa & SYM_MASK;
-    }
-  }
-  __syncthreads();
-  WSTAMP(15);
-  WF_EXIT(12);
-  // round 2: v1 -> the move's newFile, the rename's chain value
-#pragma unroll
-  for (int i = 0; i < ITEMS; ++i) {
-    const int e = t + NT * i;
-    if (e < sz) st_b[e] = v1_r[i];
-  }
-  __syncthreads();
-  for (int x = t; x < sz; x += NT) {
-    const int e = sord[x];
-    const u32 k = skind[e];
-    if (k != KMOVE && k != KREN) continue;
-    const u64 T = base[k] + woffk[k] + (u32)(x - kbase[k]);
-    if (T >= nall) continue;
-    if (k == KMOVE) Q.out_file[T] = st_b[e];
-    else Q.Rstr[T - nmv] = st_b[e];
-  }
-#endif
   if (DBG) {
     __syncthreads();
     WSTAMP(16);
@@ -1888,7 +1372,7 @@ __global__ void __launch_bounds__(WG_NT) k_window_g(WinArgs P) {
   const int wv = t / WAVE;
   // consecutive windows on one XCD: a timestamp group spans several windows, whose
   // gathers through the permutation then hit the same L2
-  const i64 w = SMX_XCD_WIN ? xcd_item(blockIdx.x, P.W) : (i64)blockIdx.x;
+  const i64 w = xcd_item(blockIdx.x, P.W);
   if (P.meta->f_fail) return;  // the segmented sort failed: no permutation to gather through
   const i64 a0 = P.bnd[2 * w], b0 = P.bnd[2 * w + 1];
   const int na = (int)(P.bnd[2 * w + 2] - a0);
