@@ -309,6 +309,70 @@ int smx_screen_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs,
 int smx_screen(const struct smx_screen* s, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Candidate pairs for the screen: which pairs (i, j), i < j, of n_logs logs stored once can
+ * have DivergentRename conflicts at all -- so that "which of these N pull requests conflict
+ * with each other" does not start from all N (N - 1) / 2 pairs.  A DivergentRename needs a
+ * rename in each log on the same symbolId with different newName (compose.py:60-70, 88-98):
+ * in the columns, the same sym with a different v0.  That is a necessary condition, not the
+ * answer: a candidate may turn out to have no conflict; a pair of valid logs that is not a
+ * candidate has none, in either orientation -- smx_compose, and so smx_screen, reports zero
+ * conflicts for (i, j) and for (j, i).
+ *
+ * Log l's ops are [log_off[l], log_off[l+1]) of the columns, and a log is valid under exactly
+ * smx_screen's rules: log_off[l] is not negative and not below any earlier offset,
+ * log_off[l+1] is not below log_off[l] and not above n_total, and no op of the log has
+ * kind >= 18.  Entries that no log covers are never read.  Only kind, sym and v0 are read (sym
+ * and v0 for renames only); ts, the ids and v1 are not part of the call.  sym has no bound and
+ * is only compared for equality; v0 is compared as a 32-bit pattern, as smx_screen does.
+ *
+ * Pair (i, j) with i < j is a candidate when both logs are valid and some symbol s has a
+ * rename in log i and a rename in log j whose v0 differ.  Self pairs (i, i) are not produced
+ * (a log can conflict with itself; screen (i, i) directly if that is asked).  A log takes
+ * part whatever its number of renames: the 2048-rename limit belongs to the later smx_screen.
+ *
+ *   pair_a, pair_b  the candidates in ascending (i, j) order, lexicographic and deterministic,
+ *                   each pair once however many symbols produce it: the first pair_cap of them
+ *                   are written and nothing at or past pair_cap.  pair_cap = 0 with both
+ *                   arrays NULL asks for the count alone.
+ *   counts[0]       the full number of candidates, whatever pair_cap is
+ *   counts[1]       the number of invalid logs; an invalid log appears in no pair and does not
+ *                   affect its neighbours
+ *   log_info        (or NULL) every log's entry is written: -1 for an invalid log, else its
+ *                   number of renames
+ *
+ * Stream-ordered as smx_screen: the call only enqueues -- no host synchronisation, no
+ * allocation, no read-back -- and the number of launches depends on n_logs alone (through the
+ * width of the sort key), never on the data.  It clears the workspace state it needs itself,
+ * so one workspace serves any sequence of calls.  Cost beyond the sort of the renames: a symbol
+ * renamed in g logs sets g (g - 1) / 2 bits of an n_logs x n_logs bit matrix, and one
+ * workgroup walks a log's kind bytes.
+ *
+ * To chain into smx_screen with no synchronisation at all: pre-fill pair_a / pair_b with -1,
+ * then call smx_screen on the same columns with these arrays as its pair_a / pair_b,
+ * n_pairs = pair_cap and conflicts = conf_off = NULL.  The entries past counts[0] still hold
+ * -1 and report counts -1 by smx_screen's rule for a pair index outside [0, n_logs).
+ */
+#define SMX_CAND_MAX_LOGS 16384
+struct smx_candidates {
+  int64_t n_logs, n_total;
+  const int64_t* log_off;                 /* device [n_logs+1], as smx_screen */
+  const uint8_t* kind; const uint32_t* sym; const int32_t* v0;   /* n_total entries; ts, ids, v1 are not read */
+  int32_t* pair_a, *pair_b;               /* device [pair_cap], out; both NULL only with pair_cap = 0 */
+  int64_t pair_cap;
+  int64_t* counts;                        /* device [2]: candidates (full number), invalid logs */
+  int32_t* log_info;                      /* device [n_logs] or NULL: -1 invalid log, else its number of renames */
+  int32_t grid_cap;                       /* as smx_batch: caps the call's own per-log, per-entry and matrix launches */
+};
+/* Workspace (8-byte aligned) for n_logs in 0 .. SMX_CAND_MAX_LOGS and n_total in 0 .. 2^31 - 1:
+ * about 48 bytes per op and 3 * n_logs^2 / 8 bytes (96 MB at the limit). */
+int smx_screen_candidates_workspace_bytes(int64_t n_logs, int64_t n_total, size_t* bytes);
+/* SMX_E_ARG (negative sizes, n_logs > SMX_CAND_MAX_LOGS, n_total > 2^31 - 1, pair_cap < 0,
+ * grid_cap < 0, a null log_off or counts, a null column with n_total > 0, a null pair array
+ * with pair_cap > 0) and SMX_E_WORKSPACE (too small or not 8-byte aligned) are reported before
+ * any HIP call; n_logs = 0 returns SMX_OK and launches nothing (counts is not written). */
+int smx_screen_candidates(const struct smx_candidates* c, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Sharded single merge: one process per GPU, shard r of G.
  * Replaces the same reference loop as smx_compose (compose.py:11-114) for a merge
  * too large for one GPU.  Shard r holds, for both branches, the ops whose

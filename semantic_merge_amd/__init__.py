@@ -3,7 +3,7 @@ from .ops import Op, Target  # noqa: F401
 from .conflict import Conflict  # noqa: F401
 
 __all__ = ["Op", "Target", "Conflict", "compose_oplogs", "compose_many", "compose_against",
-           "screen_conflicts"]
+           "screen_conflicts", "screen_all"]
 
 
 def __getattr__(name):
@@ -20,4 +20,7 @@ def __getattr__(name):
     if name == "screen_conflicts":
         from .compose import screen_conflicts
         return screen_conflicts
+    if name == "screen_all":
+        from .compose import screen_all
+        return screen_all
     raise AttributeError(name)

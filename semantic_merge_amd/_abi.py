@@ -110,6 +110,24 @@ class SmxScreen(C.Structure):
     ]
 
 
+class SmxCandidates(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_int64),
+        ("n_total", C.c_int64),
+        ("log_off", C.c_void_p),
+        ("kind", C.c_void_p),
+        ("sym", C.c_void_p),
+        ("v0", C.c_void_p),
+        ("pair_a", C.c_void_p),
+        ("pair_b", C.c_void_p),
+        ("pair_cap", C.c_int64),
+        ("counts", C.c_void_p),
+        ("log_info", C.c_void_p),
+        ("grid_cap", C.c_int32),
+    ]
+
+
+CAND_MAX_LOGS = 16384         # logs per smx_screen_candidates call (include/smx.h SMX_CAND_MAX_LOGS)
 SCREEN_MAX_RENAMES = 2048     # renames per pair of smx_screen, both logs together (more: counts -2)
 SCREEN_CLASSES = (128, 512, 2048)  # its size classes, in renames (csrc/smx_screen.h)
 BATCH_MAX_OPS = 2048          # ops per merge of smx_compose_batch (larger: counts -2)
@@ -196,6 +214,8 @@ EXPORTS = (
     "smx_compose_batch_shared",
     "smx_screen_workspace_bytes",
     "smx_screen",
+    "smx_screen_candidates_workspace_bytes",
+    "smx_screen_candidates",
     "smx_shard_step",
     "smx_shard_range_info",
     "smx_set_profiling",
@@ -243,6 +263,11 @@ def declare(lib: C.CDLL) -> C.CDLL:
         lib.smx_screen_workspace_bytes.restype = C.c_int
         lib.smx_screen.argtypes = [C.POINTER(SmxScreen), C.c_void_p, C.c_size_t, C.c_void_p]
         lib.smx_screen.restype = C.c_int
+    if hasattr(lib, "smx_screen_candidates"):  # (older builds, e.g. A/B baselines, lack it)
+        lib.smx_screen_candidates_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]
+        lib.smx_screen_candidates_workspace_bytes.restype = C.c_int
+        lib.smx_screen_candidates.argtypes = [C.POINTER(SmxCandidates), C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.smx_screen_candidates.restype = C.c_int
     lib.smx_shard_step.argtypes = [C.POINTER(SmxOps), C.POINTER(SmxShard), C.POINTER(SmxComposeOut),
                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
     lib.smx_shard_step.restype = C.c_int

@@ -403,6 +403,57 @@ class DeviceScreen(_DeviceMany):
                                    0 if self.null_conf else self._idx[3].data_ptr(), self.counts.data_ptr(), grid_cap)
 
 
+class DeviceCandidates(_DeviceMany):
+    """Device-resident inputs, outputs and workspace for repeated smx_screen_candidates calls
+    on a LogsSoA (tests, tools/cand_probe.py).  The optional arguments reach the corners of
+    the C ABI (include/smx.h smx_candidates):
+    pair_cap      capacity of pair_a / pair_b (default: all n (n - 1) / 2 pairs); 0: both NULL;
+    grid_cap      smx_candidates.grid_cap;
+    log_off       the offsets passed instead of the LogsSoA's own;
+    n_total       smx_candidates.n_total passed instead of the columns' real length;
+    fill          every output word (pairs, counts, log_info) starts as this value, and
+                  CONF_GUARD such words follow pair_cap and the logs' entries;
+    with_log_info False: smx_candidates.log_info is NULL."""
+
+    _OUT = ("pair_a", "pair_b", "counts", "log_info")
+
+    def __init__(self, lsoa, device: str = "cuda", pair_cap: Optional[int] = None, grid_cap: int = 0, log_off=None,
+                 n_total: Optional[int] = None, fill: Optional[int] = None, with_log_info: bool = True) -> None:
+        self._open(device)
+        torch, dev = self.torch, self.device
+        self.lsoa = lsoa
+        L = self.n_logs = lsoa.n_logs
+        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
+        tot = self.n_total = int(lsoa.n_total)
+        self.pair_cap = L * (L - 1) // 2 if pair_cap is None else pair_cap
+        f = 0 if fill is None else fill
+        self._in = [self._up(np.ascontiguousarray(getattr(lsoa, name)).astype(dt, copy=False), view)
+                    for name, dt, view in (_COLS[0], _COLS[4], _COLS[5])]  # kind, sym, v0
+        self.pair_a = torch.full((self.pair_cap + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        self.pair_b = torch.full((self.pair_cap + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        self.counts = torch.full((2 + self.CONF_GUARD,), f, dtype=torch.int64, device=dev)
+        self.log_info = torch.full((L + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        ws = C.c_size_t(0)
+        check(lib().smx_screen_candidates_workspace_bytes(L, tot, C.byref(ws)))
+        self.ws_bytes = ws.value
+        self.ws = torch.empty(max(ws.value, 1), dtype=torch.uint8, device=dev)
+        self._idx = [self._up(self.log_off)]
+        self._call = lib().smx_screen_candidates
+        self._arg = _abi.SmxCandidates(L, tot if n_total is None else n_total, self._idx[0].data_ptr(),
+                                       *[_ptr(t) for t in self._in],
+                                       self.pair_a.data_ptr() if self.pair_cap else 0,
+                                       self.pair_b.data_ptr() if self.pair_cap else 0, self.pair_cap,
+                                       self.counts.data_ptr(), self.log_info.data_ptr() if with_log_info else 0, grid_cap)
+
+    def results(self, raw: Optional[dict] = None):
+        """(pairs, n_candidates, n_invalid, log_info): the written candidates as an (n, 2)
+        array (the first pair_cap of them), the full count, the invalid logs, every log's entry."""
+        r = self.raw() if raw is None else raw
+        n, bad = int(r["counts"][0]), int(r["counts"][1])
+        k = min(n, self.pair_cap)
+        return np.stack([r["pair_a"][:k], r["pair_b"][:k]], axis=1), n, bad, r["log_info"][: self.n_logs]
+
+
 def _al(x: int) -> int:
     return (x + 255) & ~255
 
@@ -854,6 +905,171 @@ class ComposeSession:
                 res[p] = res[p][4]
         return res
 
+    # -- candidate pairs (smx_screen_candidates) and the screen of all of them ----------------
+
+    _CAND_IN = (_IN[0], _IN[4], _IN[5])  # kind, sym, v0
+
+    @staticmethod
+    def _cand_layout(n_total: int, n_logs: int, cap: int, cols):
+        """Byte offsets of a candidates call in the staging areas.  In: the columns `cols`
+        for n_total ops, then log_off (the six columns lie as _screen_layout has them).  Out:
+        the two counts, log_info, then pair_a and pair_b of `cap` entries."""
+        lay = ComposeSession._layout(n_total, [(name, n_total * w) for name, w in cols]
+                                     + [("log_off", (n_logs + 1) * 8)], 0, 0, 0)
+        lay["counts"] = 0
+        lay["log_info"] = 256
+        lay["pair_a"] = 256 + _al(4 * n_logs)
+        lay["pair_b"] = lay["pair_a"] + _al(4 * cap)
+        lay["out_bytes"] = lay["pair_b"] + _al(4 * cap)
+        return lay
+
+    def _ensure_aux(self, in_bytes: int, out_bytes: int) -> None:
+        """A second, small pair of staging areas (screen_all's second call), so that the
+        first call's columns and pairs stay where they are on the device."""
+        torch = self.torch
+        if in_bytes > getattr(self, "cap_aux_in", -1) or out_bytes > getattr(self, "cap_aux_out", -1):
+            self.cap_aux_in = max(in_bytes + in_bytes // 4, 4096)
+            self.cap_aux_out = max(out_bytes + out_bytes // 4, 4096)
+            self.h_aux_in = torch.empty(self.cap_aux_in, dtype=torch.uint8, pin_memory=True)
+            self.d_aux_in = torch.empty(self.cap_aux_in, dtype=torch.uint8, device=self.device)
+            self.h_aux_out = torch.empty(self.cap_aux_out, dtype=torch.uint8, pin_memory=True)
+            self.d_aux_out = torch.empty(self.cap_aux_out, dtype=torch.uint8, device=self.device)
+            torch.cuda.synchronize(self.device)  # (as _ensure: ready before the session's stream uses them)
+
+    def _candidates(self, lsoa, cols, start_cap: Optional[int]):
+        """smx_screen_candidates on the columns `cols` of a LogsSoA, staged once: one copy in,
+        one call, one copy back, one sync; once more with the exact count when the
+        candidates exceed the starting capacity (the columns are copied again only if the
+        staging areas had to grow for it).  Returns the (n, 2) pairs (a view of the output
+        staging area), every log's rename count and the layout; `last` is set."""
+        import time
+        t0 = time.perf_counter()
+        L, tot = lsoa.n_logs, int(lsoa.n_total)
+        if L > _abi.CAND_MAX_LOGS:
+            raise SmxError(-1, f"{L} logs exceed the {_abi.CAND_MAX_LOGS} of one candidates call")
+        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
+        full = L * (L - 1) // 2
+        cap = max(min(full, max(8 * L, 1024) if start_cap is None else start_cap), 1)
+        ws = C.c_size_t(0)
+        check(lib().smx_screen_candidates_workspace_bytes(L, tot, C.byref(ws)))
+        st = self.stream.cuda_stream
+        retries, in_bytes, out_bytes, staged = 0, 0, 0, None
+        t1 = t0
+        while True:
+            lay = self._cand_layout(tot, L, cap, cols)
+            self._ensure_batch(lay, ws.value)
+            if staged != self.d_in.data_ptr():  # (not yet, or the areas grew)
+                hin = self.h_in.numpy()
+                h0 = hin.ctypes.data
+                for name, w in cols:
+                    _pack(hin, h0, getattr(lsoa, name), lay[name], tot * w)
+                _pack(hin, h0, log_off, lay["log_off"], log_off.nbytes)
+                t1 = time.perf_counter()
+                self._copy_in(st, lay["in_bytes"])
+                staged = self.d_in.data_ptr()
+                in_bytes += lay["in_bytes"]
+            d0, o0 = self.d_in.data_ptr(), self.d_out.data_ptr()
+            arg = _abi.SmxCandidates(L, tot, d0 + lay["log_off"], d0 + lay["kind"], d0 + lay["sym"], d0 + lay["v0"],
+                                     o0 + lay["pair_a"], o0 + lay["pair_b"], cap, o0 + lay["counts"],
+                                     o0 + lay["log_info"], 0)
+            check(lib().smx_screen_candidates(C.byref(arg), self.ws.data_ptr(), ws.value, st))
+            self._copy_back(st, lay["out_bytes"])
+            out_bytes += lay["out_bytes"]
+            hout = self.h_out.numpy()
+            n_cand, n_bad = (int(x) for x in hout[:16].view(np.int64))
+            info = hout[lay["log_info"]: lay["log_info"] + 4 * L].view(np.int32)
+            if n_bad:
+                raise SmxError(-1, f"log {int(np.flatnonzero(info < 0)[0])}: invalid input: log offsets that "
+                                   "decrease or leave the columns, or kind >= 18")
+            if n_cand <= cap:
+                break
+            cap, retries = n_cand, retries + 1
+        pairs = np.stack([hout[lay["pair_a"]: lay["pair_a"] + 4 * n_cand].view(np.int32),
+                          hout[lay["pair_b"]: lay["pair_b"] + 4 * n_cand].view(np.int32)], axis=1)
+        t2 = time.perf_counter()
+        self.last = {"pack_s": t1 - t0, "device_s": t2 - t1, "unpack_s": 0.0, "in_bytes": in_bytes,
+                     "out_bytes": out_bytes, "n_candidates": n_cand, "retries": retries, "routed": 0}
+        return pairs, info.copy(), lay
+
+    def candidates(self, lsoa, start_cap: Optional[int] = None) -> np.ndarray:
+        """The pairs (i, j), i < j, of a LogsSoA's logs that share a symbol both rename to
+        different names, as an (n, 2) int32 array in ascending order -- every other pair has
+        no conflicts in either orientation (include/smx.h smx_screen_candidates).  One copy in
+        (kind, sym, v0, log_off), one call, one copy back, one sync; the call starts with a
+        capacity of 8 pairs per log (start_cap: another one) and runs once more with the
+        exact count when there are more: `last["retries"]`.  An invalid log raises SmxError
+        naming the first one."""
+        if lsoa.n_logs == 0:
+            self.last = {"pack_s": 0.0, "device_s": 0.0, "unpack_s": 0.0, "in_bytes": 0, "out_bytes": 0,
+                         "n_candidates": 0, "retries": 0, "routed": 0}
+            return np.zeros((0, 2), np.int32)
+        return self._candidates(lsoa, self._CAND_IN, start_cap)[0]
+
+    def screen_all(self, lsoa, start_cap: Optional[int] = None):
+        """(pairs, [conflict_pairs]): the candidate pairs of a LogsSoA (candidates()) and, for
+        each, its conflict pairs as screen() gives them; every pair i < j that is not listed
+        has none.  The six screen columns go to the device once: smx_screen_candidates runs
+        on them, counts and pairs come back with one sync, the host sizes conf_off from the
+        logs' rename counts, and smx_screen runs on the same device columns with its pair
+        lists pointing at the candidates' device output -- only conf_off is copied in for it.
+        Pairs over SCREEN_MAX_RENAMES renames go through compose() as in screen()."""
+        import time
+        if lsoa.n_logs == 0:
+            self.candidates(lsoa)
+            return np.zeros((0, 2), np.int32), []
+        pairs, ren, lay = self._candidates(lsoa, self._SCREEN_IN, start_cap)
+        pairs = pairs.copy()
+        last = self.last
+        t0 = time.perf_counter()
+        P, L, tot = len(pairs), lsoa.n_logs, int(lsoa.n_total)
+        if P == 0:
+            return pairs, []
+        conf_off = np.zeros(P + 1, np.int64)
+        np.cumsum(np.minimum(ren[pairs[:, 0]], ren[pairs[:, 1]]), out=conf_off[1:])  # never truncates
+        n_conf = int(conf_off[-1])
+        ws = C.c_size_t(0)
+        check(lib().smx_screen_workspace_bytes(L, tot, P, C.byref(ws)))
+        self._ensure(0, ws.value)  # (the workspace alone: the columns and the pairs stay on the device)
+        a_counts = _al(8 * n_conf + 8)
+        self._ensure_aux(conf_off.nbytes, a_counts + 8 * P)
+        self.h_aux_in.numpy()[: conf_off.nbytes] = conf_off.view(np.uint8)
+        t1 = time.perf_counter()
+        st = self.stream.cuda_stream
+        hip = _hiprt()
+        _hip_check(hip.hipMemcpyAsync(self.d_aux_in.data_ptr(), self.h_aux_in.data_ptr(), conf_off.nbytes, 1, st),
+                   "hipMemcpyAsync (conf_off)")
+        d0, o0, x0 = self.d_in.data_ptr(), self.d_out.data_ptr(), self.d_aux_out.data_ptr()
+        arg = _abi.SmxScreen(L, tot, P, d0 + lay["log_off"], *[d0 + lay[name] for name, _ in self._SCREEN_IN],
+                             o0 + lay["pair_a"], o0 + lay["pair_b"], x0, self.d_aux_in.data_ptr(), x0 + a_counts, 0)
+        check(lib().smx_screen(C.byref(arg), self.ws.data_ptr(), ws.value, st))
+        _hip_check(hip.hipMemcpyAsync(self.h_aux_out.data_ptr(), x0, a_counts + 8 * P, 2, st),
+                   "hipMemcpyAsync (conflicts)")
+        _hip_check(hip.hipStreamSynchronize(st), "hipStreamSynchronize")
+        t2 = time.perf_counter()
+        hout = self.h_aux_out.numpy()
+        counts = hout[a_counts: a_counts + 8 * P].view(np.int64)
+        bad = np.flatnonzero((counts < 0) & (counts != -2))
+        if len(bad):
+            p = int(bad[0])
+            raise SmxError(-1, f"pair {p} (logs {int(pairs[p, 0])}, {int(pairs[p, 1])}): invalid input")
+        over = np.flatnonzero(counts > conf_off[1:] - conf_off[:-1])
+        if len(over):
+            raise SmxError(-2, f"pair {int(over[0])}: {int(counts[over[0]])} conflicts exceed its capacity")
+        conf = hout[: 8 * n_conf].view(np.int32).reshape(-1, 2)
+        res = [None if counts[p] < 0 else conf[int(conf_off[p]): int(conf_off[p]) + int(counts[p])].copy()
+               for p in range(P)]
+        routed = [p for p in range(P) if res[p] is None]
+        self.last = {"pack_s": last["pack_s"] + t1 - t0, "device_s": last["device_s"] + t2 - t1,
+                     "unpack_s": time.perf_counter() - t2, "in_bytes": last["in_bytes"] + conf_off.nbytes,
+                     "out_bytes": last["out_bytes"] + a_counts + 8 * P, "n_candidates": P,
+                     "retries": last["retries"], "routed": len(routed)}
+        if routed:
+            # (copies: the columns may be views of the staging area that compose() packs into)
+            self._compose_routed(res, routed, [lsoa.pair(int(pairs[p, 0]), int(pairs[p, 1])) for p in routed], "pair")
+            for p in routed:
+                res[p] = res[p][4]
+        return pairs, res
+
 
 _sessions = {}
 
@@ -917,6 +1133,14 @@ def screen_soa(lsoa, pairs, device: str = "cuda"):
     that session)."""
     s = session(device)
     return (s if not s.busy else ComposeSession(device)).screen(lsoa, pairs)
+
+
+def screen_all_soa(lsoa, device: str = "cuda"):
+    """(pairs, [conflict_pairs]) of the candidate pairs i < j of a LogsSoA
+    (ComposeSession.screen_all on the thread's session, or on buffers of its own while a
+    drop-in merge of this thread holds that session)."""
+    s = session(device)
+    return (s if not s.busy else ComposeSession(device)).screen_all(lsoa)
 
 
 def set_small_limit(n: int) -> int:

@@ -13,7 +13,7 @@ it into the reference CLI, rebind the module attribute the CLI looks up
 """
 from __future__ import annotations
 
-from typing import Any, List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -123,4 +123,30 @@ def screen_conflicts(logs: Sequence[Sequence[Any]],
     for (i, j), cp in zip(pairs, found):
         a, b, na = ops[i], ops[j], len(ops[i])
         res.append([make(a[x], b[y - na]) for x, y in cp.tolist()])
+    return res
+
+
+def screen_all(logs: Sequence[Sequence[Any]]) -> Dict[Tuple[int, int], List[Any]]:
+    """``{(i, j): compose_oplogs(logs[i], logs[j])[1]}`` for the pairs ``i < j`` that have at
+    least one conflict, keys ascending: ``screen_conflicts(logs)`` restricted to its non-empty
+    entries, for a queue of many logs of which few can conflict.  The GPU first finds the pairs
+    that rename one symbol to different names (smx_screen_candidates; every other pair has no
+    conflicts) and screens only those, on columns copied once, so the cost follows the
+    conflicting part of the queue and not the number of pairs.  The result is sparse because
+    a dense list over thousands of logs is the cost this call removes.  Inputs are never
+    mutated and no ``Op`` is cloned."""
+    ops = [list(x) for x in logs]
+    if len(ops) < 2:
+        return {}
+    make = conflict_factory()
+    with dropin_session() as sess:
+        # marshalled straight into the session's pinned staging columns
+        # (sized for screen_all's starting capacity of pairs, so that it stages them in place)
+        lsoa = marshal_logs(ops, sess.staging_logs(sum(len(x) for x in ops), len(ops), max(9 * len(ops), 2048)))
+        pairs, found = sess.screen_all(lsoa)
+    res: Dict[Tuple[int, int], List[Any]] = {}
+    for (i, j), cp in zip(pairs.tolist(), found):
+        if len(cp):
+            a, b, na = ops[i], ops[j], len(ops[i])
+            res[(i, j)] = [make(a[x], b[y - na]) for x, y in cp.tolist()]
     return res

@@ -1,6 +1,7 @@
 // smx_batch.hip — the batched entry points of include/smx.h: smx_compose_batch and
 // smx_compose_batch_shared (kernels in smx_batch.h) and smx_screen
-// (kernels in smx_screen.h).
+// (kernels in smx_screen.h), and smx_screen_candidates (kernels in smx_cand.h,
+// DESIGN.md §14), which has a shape of its own: a sort and a bit matrix, no size classes.
 //
 // All three have one shape: a pre-pass sorts the items (merges, pairs) into three size
 // classes, then one kernel per class runs its list on a grid capped by what the device
@@ -13,6 +14,7 @@
 #undef SMALL_STAMPS
 #include "smx_batch.h"
 #include "smx_screen.h"
+#include "smx_cand.h"
 
 // The kernels with a residency-capped grid, and the threads of a workgroup of each.
 enum { R_BATCH = 0, R_SHARED = 3, R_EXTRACT = 6, R_SCREEN = 7, R_N = 10 };
@@ -199,6 +201,72 @@ extern "C" int smx_screen(const struct smx_screen* s, void* workspace, size_t wo
     HIP_TRY(hipGetLastError());
     return launch_classes(kScreenKernels, kScreenCaps, resident + R_SCREEN, s->n_pairs, s->grid_cap, st, w.cnt, w.lists,
                           w.list_stride, *s, w);
+  } catch (const std::exception& e) {
+    return smx_set_error(SMX_E_HIP, e.what());
+  }
+}
+
+extern "C" int smx_screen_candidates_workspace_bytes(int64_t n_logs, int64_t n_total, size_t* bytes) {
+  if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
+  if (n_logs < 0 || n_logs > SMX_CAND_MAX_LOGS || n_total < 0 || n_total > 0x7fffffffll)
+    return smx_set_error(SMX_E_ARG, "n_logs outside 0 .. SMX_CAND_MAX_LOGS or n_total outside 0 .. 2^31 - 1");
+  *bytes = cand_ws_bytes(n_logs, n_total);
+  return SMX_OK;
+}
+
+// Workgroups of BLOCK threads for `items` items, one each; at most `most`, and at most
+// grid_cap when that is positive; at least one.
+static dim3 cand_grid(i64 items, i64 most, i64 grid_cap) {
+  i64 g = SMX_CEIL_DIV(items, (i64)BLOCK);
+  if (g > most) g = most;
+  if (grid_cap > 0 && g > grid_cap) g = grid_cap;
+  return dim3((unsigned)(g > 0 ? g : 1));
+}
+
+extern "C" int smx_screen_candidates(const struct smx_candidates* c, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  if (!c) return smx_set_error(SMX_E_ARG, "null candidates");
+  if (c->n_logs < 0 || c->n_total < 0 || c->pair_cap < 0 || c->grid_cap < 0)
+    return smx_set_error(SMX_E_ARG, "negative size");
+  if (c->n_logs > SMX_CAND_MAX_LOGS || c->n_total > 0x7fffffffll)
+    return smx_set_error(SMX_E_ARG, "n_logs over SMX_CAND_MAX_LOGS or n_total over 2^31 - 1");
+  if (c->n_logs == 0) return SMX_OK;
+  if (!c->log_off || !c->counts) return smx_set_error(SMX_E_ARG, "null log_off / counts");
+  if (c->n_total > 0 && (!c->kind || !c->sym || !c->v0)) return smx_set_error(SMX_E_ARG, "null column");
+  if (c->pair_cap > 0 && (!c->pair_a || !c->pair_b))
+    return smx_set_error(SMX_E_ARG, "null pair_a / pair_b with pair_cap > 0");
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < cand_ws_bytes(c->n_logs, c->n_total))
+    return smx_set_error(SMX_E_WORKSPACE,
+                         "workspace too small or not 8-byte aligned (smx_screen_candidates_workspace_bytes)");
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  try {
+    hipStream_t st = (hipStream_t)stream;
+    const CandWs w = cand_ws(workspace, c->n_logs, c->n_total);
+    const i64 n = c->n_total, cap = c->grid_cap;
+    const int bits = cand_log_bits(c->n_logs);
+    if (n > 0) HIP_TRY(hipMemsetAsync(w.keys, 0xff, (size_t)n * 8, st));  // CAND_NONE everywhere
+    HIP_TRY(hipMemsetAsync(w.mat, 0, w.n_words * 4, st));
+    hipLaunchKernelGGL(k_cand_logs, dim3(1), dim3(1024), 0, st, *c, w);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cand_records, cand_grid(c->n_logs * BLOCK, c->n_logs, cap), dim3(BLOCK), 0, st, *c, w, bits);
+    HIP_TRY(hipGetLastError());
+    int shifts[8], nshift = 0;  // 33 + bits key bits: the records' and the sentinel's bit above them
+    for (int s = 0; s < 33 + bits; s += 8) shifts[nshift++] = s;
+    const RadixTemp tmp = {w.k2, w.v2, w.hist, nullptr};
+    HIP_TRY(radix_sort_pairs(w.keys, w.vals, n, shifts, nshift, tmp, st));
+    hipLaunchKernelGGL(k_cand_heads, cand_grid(n, 4096, cap), dim3(BLOCK), 0, st, w, n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY((scan_excl<OpSum, u32, u32>(w.flag, w.v2, n, nullptr, w.partials, w.n_ent, st)));
+    hipLaunchKernelGGL(k_cand_entries, cand_grid(n, 4096, cap), dim3(BLOCK), 0, st, w, n);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cand_pairs, cand_grid(n * (WAVE), CAND_PAIR_BLOCKS, cap), dim3(BLOCK), 0, st, *c, w, bits);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cand_popc, cand_grid((i64)w.n_words, 4096, cap), dim3(BLOCK), 0, st, w);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY((scan_excl<OpSum, u32, u32>(w.pop, w.wpos, (i64)w.n_words, nullptr, w.partials, w.n_cand, st)));
+    hipLaunchKernelGGL(k_cand_emit, cand_grid((i64)w.n_words, 4096, cap), dim3(BLOCK), 0, st, *c, w);
+    HIP_TRY(hipGetLastError());
+    return SMX_OK;
   } catch (const std::exception& e) {
     return smx_set_error(SMX_E_HIP, e.what());
   }

@@ -82,23 +82,31 @@ static inline ScreenWs screen_ws(void* workspace, int64_t n_logs, int64_t n_tota
   return w;
 }
 
-__global__ void __launch_bounds__(1024) k_screen_logs(ScreenArgs s, ScreenWs w) {
-  __shared__ i64 sc[1024 / WAVE + 1];
+// The bounds of every log, by one workgroup of 1024 threads (smx_screen and
+// smx_screen_candidates, smx_cand.h): linfo[l] = -1 for a log that starts below an earlier
+// offset (or below 0), ends before it starts or ends past n_total, else 0.
+// sc: 1024 / WAVE + 1 words of LDS.
+__device__ __forceinline__ void screen_log_bounds(const i64* log_off, i64 n_logs, i64 n_total, i32* linfo, i64* sc) {
   const int t = threadIdx.x;
-  if (t < SCREEN_CLASSES) w.cnt[t] = 0;
   i64 carry = 0;  // the largest offset before this chunk (negative offsets fail on their own)
-  for (i64 l0 = 0; l0 < s.n_logs; l0 += 1024) {
+  for (i64 l0 = 0; l0 < n_logs; l0 += 1024) {
     const i64 l = l0 + t;
-    const i64 o0 = l < s.n_logs ? s.log_off[l] : 0;
+    const i64 o0 = l < n_logs ? log_off[l] : 0;
     i64 tot;
     const i64 pre = block_excl_scan<OpMax, i64, 1024 / WAVE>(o0, sc, &tot);  // (syncs)
     const i64 pm = pre > carry ? pre : carry;
-    if (l < s.n_logs) {
-      const i64 o1 = s.log_off[l + 1];
-      w.linfo[l] = (o0 < pm || o1 < o0 || o1 > s.n_total) ? -1 : 0;
+    if (l < n_logs) {
+      const i64 o1 = log_off[l + 1];
+      linfo[l] = (o0 < pm || o1 < o0 || o1 > n_total) ? -1 : 0;
     }
     carry = tot > carry ? tot : carry;
   }
+}
+
+__global__ void __launch_bounds__(1024) k_screen_logs(ScreenArgs s, ScreenWs w) {
+  __shared__ i64 sc[1024 / WAVE + 1];
+  if (threadIdx.x < SCREEN_CLASSES) w.cnt[threadIdx.x] = 0;
+  screen_log_bounds(s.log_off, s.n_logs, s.n_total, w.linfo, sc);
 }
 
 __global__ void __launch_bounds__(SCREEN_T1) k_screen_extract(ScreenArgs s, ScreenWs w) {
