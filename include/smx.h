@@ -309,6 +309,47 @@ int smx_screen_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs,
 int smx_screen(const struct smx_screen* s, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * smx_screen with flags.  flags = 0 is smx_screen bit for bit -- the same launches, workspace
+ * size and results, counts -2 included: smx_screen(...) == smx_screen_ex(..., 0, stream), and
+ * smx_screen_workspace_bytes(...) == smx_screen_ex_workspace_bytes(..., 0, bytes).  A flag bit
+ * that is not defined here gives SMX_E_ARG before any HIP call (and before any other check).
+ *
+ * SMX_SCREEN_LARGE lifts the limit of 2048 renames: counts[p] = -2 is never reported, and a
+ * pair of any number of renames gets exactly what smx_compose reports for it -- counts[p] and
+ * the conflict pairs of smx_screen's contract above, in the same order.  Everything else is
+ * smx_screen's: the struct, the -1 rules (a kind >= 18 anywhere in a log, also past its 2048th
+ * rename, fails every pair that holds the log), truncation per pair (the full count in
+ * counts[p], the first conf_off[p+1] - conf_off[p] pairs written, nothing at or past the
+ * region), the counts-only form with conflicts = conf_off = NULL, self pairs, a pair with a
+ * side without renames (counts 0), grid_cap (which also caps the two added launches).
+ *
+ * How: a log over 2048 renames is sorted by one workgroup in tiles of 2048 (in LDS) and merge
+ * levels over two index arrays in the workspace; a pair whose renames together exceed 2048 is
+ * walked by one workgroup in rounds of up to 1024 sorted renames per side, each round starting
+ * at the pair of heads where the round before used up one side's 1024, so at most
+ * ceil(renames of A / 1024) + ceil(renames of B / 1024) rounds.  Pairs of at most 2048 renames
+ * run in smx_screen's three size classes as before, in the same call.
+ *
+ * Stream-ordered as smx_screen: eight launches with SMX_SCREEN_LARGE (six with flags = 0)
+ * whatever the data, no host synchronisation, no allocation, no read-back; the call clears the
+ * workspace state it needs, so one workspace serves any sequence of calls with either flags.
+ *
+ * Limits with SMX_SCREEN_LARGE: n_total <= 2^31 - 1 (SMX_E_ARG above it), which bounds every
+ * log's renames.  One workgroup sorts a large log and one workgroup walks a large pair, so one
+ * pair of two logs of millions of renames is served slowly; many pairs spread over the chip.
+ */
+#define SMX_SCREEN_LARGE 1u
+/* Workspace (8-byte aligned) for smx_screen_ex with the same flags.  With SMX_SCREEN_LARGE:
+ * smx_screen's and 8 bytes per op and 4 bytes per pair more (about 44 bytes per op). */
+int smx_screen_ex_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs, uint32_t flags, size_t* bytes);
+/* SMX_E_ARG (an unknown flag; then smx_screen's: negative sizes, grid_cap < 0, exactly one of
+ * conflicts / conf_off null, a null log_off / pair_a / pair_b / counts, a null column with
+ * n_total > 0; with SMX_SCREEN_LARGE n_total > 2^31 - 1) and SMX_E_WORKSPACE (too small for
+ * these flags or not 8-byte aligned) are reported before any HIP call; n_pairs = 0 or
+ * n_logs = 0 returns SMX_OK and launches nothing. */
+int smx_screen_ex(const struct smx_screen* s, void* workspace, size_t workspace_bytes, uint32_t flags, void* stream);
+
+/*
  * Candidate pairs for the screen: which pairs (i, j), i < j, of n_logs logs stored once can
  * have DivergentRename conflicts at all -- so that "which of these N pull requests conflict
  * with each other" does not start from all N (N - 1) / 2 pairs.  A DivergentRename needs a

@@ -199,6 +199,7 @@ class SmxRgaOut(C.Structure):
 
 # Every symbol include/smx.h declares (tests check the built library exports them).
 RGA_GROUPED = 1   # smx_rga_replay_ex flag (include/smx.h SMX_RGA_GROUPED)
+SCREEN_LARGE = 1  # smx_screen_ex flag (include/smx.h SMX_SCREEN_LARGE): no limit on renames
 
 EXPORTS = (
     "smx_compose_workspace_bytes",
@@ -214,6 +215,8 @@ EXPORTS = (
     "smx_compose_batch_shared",
     "smx_screen_workspace_bytes",
     "smx_screen",
+    "smx_screen_ex_workspace_bytes",
+    "smx_screen_ex",
     "smx_screen_candidates_workspace_bytes",
     "smx_screen_candidates",
     "smx_shard_step",
@@ -263,6 +266,12 @@ def declare(lib: C.CDLL) -> C.CDLL:
         lib.smx_screen_workspace_bytes.restype = C.c_int
         lib.smx_screen.argtypes = [C.POINTER(SmxScreen), C.c_void_p, C.c_size_t, C.c_void_p]
         lib.smx_screen.restype = C.c_int
+    if hasattr(lib, "smx_screen_ex"):  # (older builds, e.g. A/B baselines, lack it)
+        lib.smx_screen_ex_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_uint32,
+                                                      C.POINTER(C.c_size_t)]
+        lib.smx_screen_ex_workspace_bytes.restype = C.c_int
+        lib.smx_screen_ex.argtypes = [C.POINTER(SmxScreen), C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+        lib.smx_screen_ex.restype = C.c_int
     if hasattr(lib, "smx_screen_candidates"):  # (older builds, e.g. A/B baselines, lack it)
         lib.smx_screen_candidates_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]
         lib.smx_screen_candidates_workspace_bytes.restype = C.c_int

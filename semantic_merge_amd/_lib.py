@@ -360,6 +360,13 @@ def _rename_counts(kind, log_off) -> np.ndarray:
     return np.maximum(csum[off[1:]] - csum[off[:-1]], 0)
 
 
+def _over_limit(ren, pairs) -> int:
+    """How many of the (i, j) of `pairs` smx_screen sends back (counts -2) and SMX_SCREEN_LARGE
+    streams: both logs have renames and together more than SCREEN_MAX_RENAMES."""
+    ra, rb = ren[pairs[:, 0]].astype(np.int64), ren[pairs[:, 1]].astype(np.int64)
+    return int(((ra > 0) & (rb > 0) & (ra + rb > _abi.SCREEN_MAX_RENAMES)).sum())
+
+
 class DeviceScreen(_DeviceMany):
     """Device-resident inputs, outputs and workspace for repeated smx_screen calls on a
     LogsSoA and a list of (i, j) pairs (tests, tools/screen_probe.py).  The optional
@@ -370,13 +377,15 @@ class DeviceScreen(_DeviceMany):
     log_off       the offsets passed instead of the LogsSoA's own;
     n_total       smx_screen.n_total passed instead of the columns' real length;
     fill          every output word (conflict pairs, counts) starts as this value, and
-                  CONF_GUARD such words follow the last pair's conflict region."""
+                  CONF_GUARD such words follow the last pair's conflict region;
+    large         smx_screen_ex with SMX_SCREEN_LARGE (no limit on renames, no counts -2) and
+                  the workspace it asks for, instead of smx_screen."""
 
     _OUT = ("conf", "counts")
     _PER = 1
 
     def __init__(self, lsoa, pairs, device: str = "cuda", conflict_caps=None, grid_cap: int = 0, log_off=None,
-                 n_total: Optional[int] = None, fill: Optional[int] = None) -> None:
+                 n_total: Optional[int] = None, fill: Optional[int] = None, large: bool = False) -> None:
         self._open(device)
         self.lsoa = lsoa
         L = self.n_logs = lsoa.n_logs
@@ -393,10 +402,14 @@ class DeviceScreen(_DeviceMany):
         else:
             caps = np.zeros(P, np.int64) if self.null_conf else conflict_caps
         self._upload_cols([lsoa], 6)  # (no v1)
-        self._alloc(P, caps, 0, fill, lib().smx_screen_workspace_bytes, L, tot, P)
+        if large:
+            self._alloc(P, caps, 0, fill, lib().smx_screen_ex_workspace_bytes, L, tot, P, _abi.SCREEN_LARGE)
+            self._call = lambda arg, ws, nbytes, st: lib().smx_screen_ex(arg, ws, nbytes, _abi.SCREEN_LARGE, st)
+        else:
+            self._alloc(P, caps, 0, fill, lib().smx_screen_workspace_bytes, L, tot, P)
+            self._call = lib().smx_screen
         self._idx = [self._up(self.log_off), self._up(self.pairs[:, 0]), self._up(self.pairs[:, 1]),
                      self._up(self.conf_off)]
-        self._call = lib().smx_screen
         self._arg = _abi.SmxScreen(L, tot if n_total is None else n_total, P, self._idx[0].data_ptr(),
                                    *[_ptr(t) for t in self._in], _ptr(self._idx[1]), _ptr(self._idx[2]),
                                    0 if self.null_conf else self.conf.data_ptr(),
@@ -850,19 +863,24 @@ class ComposeSession:
         cols["v1"] = np.empty(n_total, np.int32)
         return cols
 
-    def screen(self, lsoa, pairs):
+    def screen(self, lsoa, pairs, large: bool = False):
         """The conflict pairs (an (n, 2) int32 array of (A index, B index) into
         log i || log j, as compose()'s fifth result) of every (i, j) of `pairs` over a
         LogsSoA: one host-to-device copy of the six columns (33 bytes per op, each log once),
         one smx_screen, one copy back of the counts and the conflict pairs, one stream sync.
         Pairs whose renames exceed SCREEN_MAX_RENAMES (the library sends them back, counts -2)
         go through compose(lsoa.pair(i, j)) afterwards, keeping only the conflicts.  Invalid
-        input raises SmxError naming the pair."""
+        input raises SmxError naming the pair.  large=True: smx_screen_ex with SMX_SCREEN_LARGE
+        screens those pairs too, in the same call -- nothing goes through compose()
+        (`last["routed"]` is 0, `last["large"]` the number of pairs over the limit)."""
         import time
         t0 = time.perf_counter()
         pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
         P, L, tot = len(pairs), lsoa.n_logs, int(lsoa.n_total)
         self.last = {"pack_s": 0.0, "device_s": 0.0, "unpack_s": 0.0, "in_bytes": 0, "out_bytes": 0, "routed": 0}
+        if large:
+            self.last["large"] = 0
+        flags = _abi.SCREEN_LARGE if large else 0
         if P == 0:
             return []
         bad = np.flatnonzero(((pairs < 0) | (pairs >= L)).any(axis=1))
@@ -874,14 +892,14 @@ class ComposeSession:
         np.cumsum(np.minimum(ren[pairs[:, 0]], ren[pairs[:, 1]]), out=conf_off[1:])  # never truncates
         lay = self._screen_layout(tot, L, P, int(conf_off[-1]))
         t1, t2 = self._staged_call(
-            lib().smx_screen_workspace_bytes, (L, tot, P), lay,
+            lib().smx_screen_ex_workspace_bytes, (L, tot, P, flags), lay,
             [(getattr(lsoa, name), lay[name], tot * w) for name, w in self._SCREEN_IN],
             (("log_off", log_off), ("pair_a", pairs[:, 0]), ("pair_b", pairs[:, 1]), ("conf_off", conf_off)),
             lambda d0, o0: _abi.SmxScreen(L, tot, P, d0 + lay["log_off"],
                                           *[d0 + lay[name] for name, _ in self._SCREEN_IN],
                                           d0 + lay["pair_a"], d0 + lay["pair_b"], o0 + lay["conf"],
                                           d0 + lay["conf_off"], o0 + lay["counts"], 0),
-            lib().smx_screen)
+            lambda arg, ws, nbytes, st: lib().smx_screen_ex(arg, ws, nbytes, flags, st))
         hout = self.h_out.numpy()
         counts = hout[lay["counts"]: lay["counts"] + 8 * P].view(np.int64)
         bad = np.flatnonzero((counts < 0) & (counts != -2))
@@ -898,6 +916,8 @@ class ComposeSession:
         routed = [p for p in range(P) if res[p] is None]
         self.last = {"pack_s": t1 - t0, "device_s": t2 - t1, "unpack_s": time.perf_counter() - t2,
                      "in_bytes": lay["in_bytes"], "out_bytes": lay["out_bytes"], "routed": len(routed)}
+        if large:
+            self.last["large"] = _over_limit(ren, pairs)
         if routed:
             # (copies: the columns may be views of the staging area that compose() packs into)
             self._compose_routed(res, routed, [lsoa.pair(int(pairs[p, 0]), int(pairs[p, 1])) for p in routed], "pair")
@@ -1005,21 +1025,28 @@ class ComposeSession:
             return np.zeros((0, 2), np.int32)
         return self._candidates(lsoa, self._CAND_IN, start_cap)[0]
 
-    def screen_all(self, lsoa, start_cap: Optional[int] = None):
+    def screen_all(self, lsoa, start_cap: Optional[int] = None, large: bool = False):
         """(pairs, [conflict_pairs]): the candidate pairs of a LogsSoA (candidates()) and, for
         each, its conflict pairs as screen() gives them; every pair i < j that is not listed
         has none.  The six screen columns go to the device once: smx_screen_candidates runs
         on them, counts and pairs come back with one sync, the host sizes conf_off from the
         logs' rename counts, and smx_screen runs on the same device columns with its pair
         lists pointing at the candidates' device output -- only conf_off is copied in for it.
-        Pairs over SCREEN_MAX_RENAMES renames go through compose() as in screen()."""
+        Pairs over SCREEN_MAX_RENAMES renames go through compose() as in screen(); with
+        large=True the second call is smx_screen_ex with SMX_SCREEN_LARGE and screens them too
+        (`last["routed"]` is 0, `last["large"]` their number)."""
         import time
+        flags = _abi.SCREEN_LARGE if large else 0
         if lsoa.n_logs == 0:
             self.candidates(lsoa)
+            if large:
+                self.last["large"] = 0
             return np.zeros((0, 2), np.int32), []
         pairs, ren, lay = self._candidates(lsoa, self._SCREEN_IN, start_cap)
         pairs = pairs.copy()
         last = self.last
+        if large:
+            last["large"] = _over_limit(ren, pairs)
         t0 = time.perf_counter()
         P, L, tot = len(pairs), lsoa.n_logs, int(lsoa.n_total)
         if P == 0:
@@ -1028,7 +1055,7 @@ class ComposeSession:
         np.cumsum(np.minimum(ren[pairs[:, 0]], ren[pairs[:, 1]]), out=conf_off[1:])  # never truncates
         n_conf = int(conf_off[-1])
         ws = C.c_size_t(0)
-        check(lib().smx_screen_workspace_bytes(L, tot, P, C.byref(ws)))
+        check(lib().smx_screen_ex_workspace_bytes(L, tot, P, flags, C.byref(ws)))
         self._ensure(0, ws.value)  # (the workspace alone: the columns and the pairs stay on the device)
         a_counts = _al(8 * n_conf + 8)
         self._ensure_aux(conf_off.nbytes, a_counts + 8 * P)
@@ -1041,7 +1068,7 @@ class ComposeSession:
         d0, o0, x0 = self.d_in.data_ptr(), self.d_out.data_ptr(), self.d_aux_out.data_ptr()
         arg = _abi.SmxScreen(L, tot, P, d0 + lay["log_off"], *[d0 + lay[name] for name, _ in self._SCREEN_IN],
                              o0 + lay["pair_a"], o0 + lay["pair_b"], x0, self.d_aux_in.data_ptr(), x0 + a_counts, 0)
-        check(lib().smx_screen(C.byref(arg), self.ws.data_ptr(), ws.value, st))
+        check(lib().smx_screen_ex(C.byref(arg), self.ws.data_ptr(), ws.value, flags, st))
         _hip_check(hip.hipMemcpyAsync(self.h_aux_out.data_ptr(), x0, a_counts + 8 * P, 2, st),
                    "hipMemcpyAsync (conflicts)")
         _hip_check(hip.hipStreamSynchronize(st), "hipStreamSynchronize")
@@ -1063,6 +1090,8 @@ class ComposeSession:
                      "unpack_s": time.perf_counter() - t2, "in_bytes": last["in_bytes"] + conf_off.nbytes,
                      "out_bytes": last["out_bytes"] + a_counts + 8 * P, "n_candidates": P,
                      "retries": last["retries"], "routed": len(routed)}
+        if large:
+            self.last["large"] = last["large"]
         if routed:
             # (copies: the columns may be views of the staging area that compose() packs into)
             self._compose_routed(res, routed, [lsoa.pair(int(pairs[p, 0]), int(pairs[p, 1])) for p in routed], "pair")
@@ -1127,20 +1156,20 @@ def compose_soa_shared(ssoa, shared_is_b: bool = False, device: str = "cuda"):
     return (s if not s.busy else ComposeSession(device)).compose_shared(ssoa, shared_is_b)
 
 
-def screen_soa(lsoa, pairs, device: str = "cuda"):
+def screen_soa(lsoa, pairs, device: str = "cuda", large: bool = False):
     """[conflict_pairs] of the (i, j) of `pairs` over a LogsSoA (ComposeSession.screen on the
     thread's session, or on buffers of its own while a drop-in merge of this thread holds
     that session)."""
     s = session(device)
-    return (s if not s.busy else ComposeSession(device)).screen(lsoa, pairs)
+    return (s if not s.busy else ComposeSession(device)).screen(lsoa, pairs, large=large)
 
 
-def screen_all_soa(lsoa, device: str = "cuda"):
+def screen_all_soa(lsoa, device: str = "cuda", large: bool = False):
     """(pairs, [conflict_pairs]) of the candidate pairs i < j of a LogsSoA
     (ComposeSession.screen_all on the thread's session, or on buffers of its own while a
     drop-in merge of this thread holds that session)."""
     s = session(device)
-    return (s if not s.busy else ComposeSession(device)).screen_all(lsoa)
+    return (s if not s.busy else ComposeSession(device)).screen_all(lsoa, large=large)
 
 
 def set_small_limit(n: int) -> int:

@@ -95,7 +95,7 @@ def compose_against(shared: Sequence[Any], branches: Sequence[Sequence[Any]],
 
 
 def screen_conflicts(logs: Sequence[Sequence[Any]],
-                     pairs: Optional[Sequence[Tuple[int, int]]] = None) -> List[List[Any]]:
+                     pairs: Optional[Sequence[Tuple[int, int]]] = None, large: bool = False) -> List[List[Any]]:
     """``[compose_oplogs(logs[i], logs[j])[1] for i, j in pairs]`` -- the DivergentRename
     conflicts alone, no composed ops -- for a caller that asks which of many logs conflict
     (a merge queue: every pull request against the target branch, or against each other
@@ -103,7 +103,9 @@ def screen_conflicts(logs: Sequence[Sequence[Any]],
     marshalled, copied to the GPU and has its renames sorted once, whatever the number of
     pairs that hold it; a pair costs one merge of two short lists (one copy in, one
     smx_screen, one copy back, one sync).  Pairs of more than 2048 renames follow through
-    the full composition one by one.  Inputs are never mutated and no ``Op`` is cloned: the
+    the full composition one by one; ``large=True`` screens them in the same call instead
+    (smx_screen_ex, SMX_SCREEN_LARGE), for logs of thousands of renames such as a busy target
+    branch's delta.  Inputs are never mutated and no ``Op`` is cloned: the
     conflicts are built from the input objects, as in the reference."""
     ops = [list(x) for x in logs]
     if pairs is None:
@@ -118,7 +120,7 @@ def screen_conflicts(logs: Sequence[Sequence[Any]],
     with dropin_session() as sess:
         # marshalled straight into the session's pinned staging columns
         lsoa = marshal_logs(ops, sess.staging_logs(sum(len(x) for x in ops), len(ops), len(pairs)))
-        found = sess.screen(lsoa, pairs)
+        found = sess.screen(lsoa, pairs, large=large)
     res: List[List[Any]] = []
     for (i, j), cp in zip(pairs, found):
         a, b, na = ops[i], ops[j], len(ops[i])
@@ -126,14 +128,15 @@ def screen_conflicts(logs: Sequence[Sequence[Any]],
     return res
 
 
-def screen_all(logs: Sequence[Sequence[Any]]) -> Dict[Tuple[int, int], List[Any]]:
+def screen_all(logs: Sequence[Sequence[Any]], large: bool = False) -> Dict[Tuple[int, int], List[Any]]:
     """``{(i, j): compose_oplogs(logs[i], logs[j])[1]}`` for the pairs ``i < j`` that have at
     least one conflict, keys ascending: ``screen_conflicts(logs)`` restricted to its non-empty
     entries, for a queue of many logs of which few can conflict.  The GPU first finds the pairs
     that rename one symbol to different names (smx_screen_candidates; every other pair has no
     conflicts) and screens only those, on columns copied once, so the cost follows the
     conflicting part of the queue and not the number of pairs.  The result is sparse because
-    a dense list over thousands of logs is the cost this call removes.  Inputs are never
+    a dense list over thousands of logs is the cost this call removes.  ``large`` as in
+    ``screen_conflicts``.  Inputs are never
     mutated and no ``Op`` is cloned."""
     ops = [list(x) for x in logs]
     if len(ops) < 2:
@@ -143,7 +146,7 @@ def screen_all(logs: Sequence[Sequence[Any]]) -> Dict[Tuple[int, int], List[Any]
         # marshalled straight into the session's pinned staging columns
         # (sized for screen_all's starting capacity of pairs, so that it stages them in place)
         lsoa = marshal_logs(ops, sess.staging_logs(sum(len(x) for x in ops), len(ops), max(9 * len(ops), 2048)))
-        pairs, found = sess.screen_all(lsoa)
+        pairs, found = sess.screen_all(lsoa, large=large)
     res: Dict[Tuple[int, int], List[Any]] = {}
     for (i, j), cp in zip(pairs.tolist(), found):
         if len(cp):

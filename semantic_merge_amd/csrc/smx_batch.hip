@@ -1,6 +1,6 @@
 // smx_batch.hip — the batched entry points of include/smx.h: smx_compose_batch and
-// smx_compose_batch_shared (kernels in smx_batch.h) and smx_screen
-// (kernels in smx_screen.h), and smx_screen_candidates (kernels in smx_cand.h,
+// smx_compose_batch_shared (kernels in smx_batch.h) and smx_screen /
+// smx_screen_ex (kernels in smx_screen.h), and smx_screen_candidates (kernels in smx_cand.h,
 // DESIGN.md §14), which has a shape of its own: a sort and a bit matrix, no size classes.
 //
 // All three have one shape: a pre-pass sorts the items (merges, pairs) into three size
@@ -17,7 +17,7 @@
 #include "smx_cand.h"
 
 // The kernels with a residency-capped grid, and the threads of a workgroup of each.
-enum { R_BATCH = 0, R_SHARED = 3, R_EXTRACT = 6, R_SCREEN = 7, R_N = 10 };
+enum { R_BATCH = 0, R_SHARED = 3, R_EXTRACT = 6, R_SCREEN = 7, R_EXTRACT_LARGE = 10, R_STREAM = 11, R_N = 12 };
 template <typename B>
 using BatchKernel = void (*)(B, const u32*, const u32*);
 template <typename B>
@@ -56,6 +56,10 @@ static int resident_of(const int** out) {
       fn[R_SCREEN + c] = (const void*)kScreenKernels[c];
       threads[R_SCREEN + c] = kScreenCaps[c] / 2;
     }
+    fn[R_EXTRACT_LARGE] = (const void*)k_screen_extract_large;
+    threads[R_EXTRACT_LARGE] = SCREEN_TL;
+    fn[R_STREAM] = (const void*)k_screen_stream;
+    threads[R_STREAM] = SCREEN_N / 2;
     int cus = 0;
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     for (int k = 0; k < R_N; ++k) {
@@ -163,19 +167,31 @@ extern "C" int smx_compose_batch_shared(const smx_batch_shared* b, void* workspa
   return batch_run(b, R_SHARED, workspace, stream);
 }
 
-extern "C" int smx_screen_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs, size_t* bytes) {
+extern "C" int smx_screen_ex_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs, uint32_t flags,
+                                             size_t* bytes) {
+  if (flags & ~(uint32_t)SMX_SCREEN_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_screen_ex flag");
   if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
   if (n_logs < 0 || n_logs > 0x7fffffffll || n_pairs < 0 || n_pairs > 0x7fffffffll || n_total < 0)
     return smx_set_error(SMX_E_ARG, "n_logs or n_pairs outside 0 .. 2^31 - 1, or n_total negative");
-  *bytes = screen_ws_bytes(n_logs, n_total, n_pairs);
+  const bool large = (flags & SMX_SCREEN_LARGE) != 0;
+  if (large && n_total > 0x7fffffffll) return smx_set_error(SMX_E_ARG, "SMX_SCREEN_LARGE: n_total over 2^31 - 1");
+  *bytes = screen_ws_bytes(n_logs, n_total, n_pairs) + (large ? screen_large_bytes(n_total, n_pairs) : 0);
   return SMX_OK;
 }
 
-extern "C" int smx_screen(const struct smx_screen* s, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int smx_screen_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs, size_t* bytes) {
+  return smx_screen_ex_workspace_bytes(n_logs, n_total, n_pairs, 0u, bytes);
+}
+
+extern "C" int smx_screen_ex(const struct smx_screen* s, void* workspace, size_t workspace_bytes, uint32_t flags,
+                             void* stream) {
+  if (flags & ~(uint32_t)SMX_SCREEN_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_screen_ex flag");
+  const bool large = (flags & SMX_SCREEN_LARGE) != 0;
   if (!s) return smx_set_error(SMX_E_ARG, "null screen");
   if (s->n_logs < 0 || s->n_logs > 0x7fffffffll || s->n_pairs < 0 || s->n_pairs > 0x7fffffffll || s->n_total < 0 ||
       s->grid_cap < 0)
     return smx_set_error(SMX_E_ARG, "negative size");
+  if (large && s->n_total > 0x7fffffffll) return smx_set_error(SMX_E_ARG, "SMX_SCREEN_LARGE: n_total over 2^31 - 1");
   if ((s->conflicts == nullptr) != (s->conf_off == nullptr))
     return smx_set_error(SMX_E_ARG, "conflicts and conf_off are both null or both set");
   if (s->n_pairs == 0 || s->n_logs == 0) return SMX_OK;
@@ -183,27 +199,49 @@ extern "C" int smx_screen(const struct smx_screen* s, void* workspace, size_t wo
     return smx_set_error(SMX_E_ARG, "null log_off / pair_a / pair_b / counts");
   if (s->n_total > 0 && (!s->kind || !s->ts || !s->oid_hi || !s->oid_lo || !s->sym || !s->v0))
     return smx_set_error(SMX_E_ARG, "null column");
-  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < screen_ws_bytes(s->n_logs, s->n_total, s->n_pairs))
-    return smx_set_error(SMX_E_WORKSPACE, "workspace too small or not 8-byte aligned (smx_screen_workspace_bytes)");
+  const size_t need = screen_ws_bytes(s->n_logs, s->n_total, s->n_pairs) +
+                      (large ? screen_large_bytes(s->n_total, s->n_pairs) : 0);
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < need)
+    return smx_set_error(SMX_E_WORKSPACE, large ? "workspace too small or not 8-byte aligned (smx_screen_ex_workspace_bytes)"
+                                                : "workspace too small or not 8-byte aligned (smx_screen_workspace_bytes)");
   (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
   try {
     const int* resident;
     if (int rc = resident_of(&resident)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const ScreenWs w = screen_ws(workspace, s->n_logs, s->n_total, s->n_pairs);
+    const ScreenLargeWs x = large ? screen_large_ws(workspace, s->n_logs, s->n_total, s->n_pairs) : ScreenLargeWs{};
+    const dim3 classify_grid((unsigned)SMX_CEIL_DIV(s->n_pairs, (i64)SCREEN_CHUNK));
     hipLaunchKernelGGL(k_screen_logs, dim3(1), dim3(1024), 0, st, *s, w);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_screen_extract, capped_grid(resident[R_EXTRACT], s->n_logs, s->grid_cap), dim3(SCREEN_T1), 0,
                        st, *s, w);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_screen_classify, dim3((unsigned)SMX_CEIL_DIV(s->n_pairs, (i64)SCREEN_CHUNK)), dim3(256), 0, st,
-                       *s, w);
+    if (large) {
+      hipLaunchKernelGGL(k_screen_extract_large, capped_grid(resident[R_EXTRACT_LARGE], s->n_logs, s->grid_cap),
+                         dim3(SCREEN_TL), 0, st, *s, w, x);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_screen_classify<true>, classify_grid, dim3(256), 0, st, *s, w, x.list);
+    } else {
+      hipLaunchKernelGGL(k_screen_classify<false>, classify_grid, dim3(256), 0, st, *s, w, (u32*)nullptr);
+    }
     HIP_TRY(hipGetLastError());
-    return launch_classes(kScreenKernels, kScreenCaps, resident + R_SCREEN, s->n_pairs, s->grid_cap, st, w.cnt, w.lists,
-                          w.list_stride, *s, w);
+    if (int rc = launch_classes(kScreenKernels, kScreenCaps, resident + R_SCREEN, s->n_pairs, s->grid_cap, st, w.cnt,
+                                w.lists, w.list_stride, *s, w))
+      return rc;
+    if (large) {
+      hipLaunchKernelGGL(k_screen_stream, capped_grid(resident[R_STREAM], s->n_pairs, s->grid_cap), dim3(SCREEN_N / 2),
+                         0, st, *s, w, w.cnt + SCREEN_CLASSES, x.list);
+      HIP_TRY(hipGetLastError());
+    }
+    return SMX_OK;
   } catch (const std::exception& e) {
     return smx_set_error(SMX_E_HIP, e.what());
   }
+}
+
+extern "C" int smx_screen(const struct smx_screen* s, void* workspace, size_t workspace_bytes, void* stream) {
+  return smx_screen_ex(s, workspace, workspace_bytes, 0u, stream);
 }
 
 extern "C" int smx_screen_candidates_workspace_bytes(int64_t n_logs, int64_t n_total, size_t* bytes) {
