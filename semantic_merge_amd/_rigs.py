@@ -1,0 +1,360 @@
+"""Resident-buffer rigs over libsmx's entry points, for tests, tools and bench.py (no product
+path): inputs uploaded once, outputs and workspace allocated once, the call repeated.  The
+optional arguments reach the corners of the C ABI that the product's path never passes."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import numpy as np
+
+from . import _abi
+from ._lib import CAND_COLS, OP_COLS, SCREEN_COLS, SmxError, _ptr, _rename_counts, _torch, check, lib
+from .marshal import SoA
+
+
+def _workspace(torch, dev, query, *sizes):
+    """(bytes, buffer): the workspace that `query(*sizes)` asks for, allocated on `dev`."""
+    ws = C.c_size_t(0)
+    check(query(*sizes, C.byref(ws)))
+    return ws.value, torch.empty(max(ws.value, 1), dtype=torch.uint8, device=dev)
+
+
+class DeviceCompose:
+    """Device-resident inputs, outputs and workspace for repeated smx_compose calls.
+
+    The optional arguments reach the corners of the C ABI (include/smx.h):
+    b_gap        branch B's columns start b_gap entries after branch A's (smx_ops.b_gap);
+                 the gap holds an invalid kind (0xFF) and symbol (0xFFFFFFFF), so a kernel
+                 that read it would report invalid input;
+    conflict_cap the capacity passed for the conflict pairs (default min(n_a, n_b), which
+                 always suffices); CONF_GUARD guard words follow the 2 * conflict_cap
+                 words (guard_intact());
+    ws_bytes     the workspace size passed (default: what smx_compose_workspace_bytes
+                 asks for; the buffer itself always has that size)."""
+
+    CONF_GUARD = 64
+    _GUARD_WORD = 0x5A5A5A5A
+
+    def __init__(self, soa: SoA, device: str = "cuda", b_gap: int = 0, conflict_cap: Optional[int] = None,
+                 ws_bytes: Optional[int] = None) -> None:
+        torch = self.torch = _torch()
+        dev = self.device = torch.device(device)
+        self.soa, self.n, na = soa, soa.n, soa.n_a
+        if b_gap < 0:
+            raise ValueError("b_gap must be >= 0")
+
+        def up(a, dt, fill=0):
+            a = np.ascontiguousarray(a)
+            if b_gap:
+                a = np.concatenate([a[:na], np.full(b_gap, fill, a.dtype), a[na:]])
+            return torch.from_numpy(a.view(dt)).to(dev, non_blocking=False)
+
+        gap = {"kind": 0xFF, "sym": 0xFFFFFFFF, "v0": -1, "v1": -1}  # (u64 columns: bit-identical payload)
+        cols = [up(getattr(soa, name), view, gap.get(name, 0)) for name, _, view in OP_COLS]
+        self.kind, self.ts, self.hi, self.lo, self.sym, self.v0, self.v1 = cols
+        outs = [torch.empty(max(self.n, 1), dtype=torch.int32, device=dev) for _ in range(4)]
+        self.order, self.addr, self.file, self.ctx = outs
+        if conflict_cap is None:
+            self.cap = max(min(soa.n_a, soa.n_b), 1)
+            self.conf = torch.empty(2 * self.cap, dtype=torch.int32, device=dev)
+        else:
+            self.cap = conflict_cap
+            self.conf = torch.full((2 * max(self.cap, 0) + self.CONF_GUARD,), self._GUARD_WORD,
+                                   dtype=torch.int32, device=dev)
+        self._guarded = conflict_cap is not None
+        self.counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        self.ws_needed, self.ws = _workspace(torch, dev, lib().smx_compose_workspace_bytes,
+                                             soa.n_a, soa.n_b, soa.n_sym)
+        self.ws_bytes = self.ws_needed if ws_bytes is None else ws_bytes
+        self._ops = _abi.SmxOps(soa.n_a, soa.n_b, soa.n_sym, *[_ptr(t) for t in cols], b_gap)
+        self._out = _abi.SmxComposeOut(*[_ptr(t) for t in outs], _ptr(self.conf), self.cap, _ptr(self.counts))
+
+    def _args(self, stream):
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        return (C.byref(self._ops), C.byref(self._out), _ptr(self.ws), self.ws_bytes, s.cuda_stream)
+
+    def run(self, stream=None) -> None:
+        """One composition on `stream` (default: torch's current stream)."""
+        check(lib().smx_compose(*self._args(stream)))
+
+    def run_async(self, stream=None) -> None:
+        """Enqueue the host-sync-free part (smx_compose_async; capturable in a graph)."""
+        check(lib().smx_compose_async(*self._args(stream)))
+
+    def finish(self, stream=None) -> None:
+        """Complete what run_async left (smx_compose_finish: one stream sync)."""
+        check(lib().smx_compose_finish(*self._args(stream)))
+
+    @staticmethod
+    def last_plan() -> str:
+        return _abi.PLAN_NAMES[lib().smx_last_plan()]
+
+    def guard_intact(self) -> bool:
+        """The CONF_GUARD words after the conflict pairs' capacity are as they were set
+        (a DeviceCompose built with conflict_cap)."""
+        if not self._guarded:
+            raise ValueError("no guard words: built without conflict_cap")
+        self.torch.cuda.synchronize(self.device)
+        return bool((self.conf[2 * max(self.cap, 0):] == self._GUARD_WORD).all().item())
+
+    def results(self, truncated: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The composed arrays and the conflict pairs.  More conflicts than conflict_cap
+        (include/smx.h: counts[1] > conflict_cap, only the first conflict_cap pairs
+        written) raise SmxError -2, or with truncated=True give those first pairs."""
+        self.torch.cuda.synchronize(self.device)
+        k, nc = (int(x) for x in self.counts.cpu().tolist())
+        if k < 0:
+            raise SmxError(-1, "invalid input: sym >= n_sym or kind >= 18")
+        if nc > self.cap:
+            if not truncated:
+                raise SmxError(-2, f"{nc} conflicts exceed capacity {self.cap}")
+            nc = self.cap
+        return tuple(t[:k].cpu().numpy() for t in (self.order, self.addr, self.file, self.ctx)) \
+            + (self.conf[: 2 * nc].cpu().numpy().reshape(nc, 2),)
+
+
+class _DeviceMany:
+    """What DeviceBatch, DeviceBatchShared and DeviceScreen share: the uploads, the outputs
+    filled with one value and followed by CONF_GUARD such words, the workspace, and run /
+    raw / results.  A subclass builds its struct (_arg) for its entry point (_call), names
+    its output arrays (_OUT) and says where item m's results start (_start)."""
+
+    CONF_GUARD = 64
+    _OUT = ("order", "addr", "file", "ctx", "conf", "counts")
+    _PER = 2  # counts words per item: (composed ops, conflicts), or the conflicts alone
+
+    def _open(self, device: str) -> None:
+        self.torch = _torch()
+        self.device = self.torch.device(device)
+
+    def _up(self, a, dt=None):
+        a = np.ascontiguousarray(a)
+        return self.torch.from_numpy(a.view(dt) if dt is not None else a).to(self.device)
+
+    def _upload_cols(self, sources, cols=OP_COLS) -> None:
+        """_in: the columns `cols` (rows of OP_COLS) of the sources, one after another, uploaded."""
+        self._in = [self._up(np.concatenate([np.ascontiguousarray(getattr(s, name)).astype(dt, copy=False)
+                                             for s in sources]) if sources else np.zeros(0, dt), view)
+                    for name, dt, view in cols]
+
+    def _workspace(self, query, *sizes) -> None:
+        """ws, ws_bytes: the workspace that `query(*sizes)` asks for."""
+        self.ws_bytes, self.ws = _workspace(self.torch, self.device, query, *sizes)
+
+    def _alloc(self, n: int, caps, n_out: int, fill: Optional[int]) -> None:
+        """conf_off from the n items' capacities; every output array of _OUT filled (the
+        results n_out entries long)."""
+        torch, dev = self.torch, self.device
+        self.conf_off = np.zeros(n + 1, np.int64)
+        np.cumsum(caps, out=self.conf_off[1:])
+        f = 0 if fill is None else fill
+        for name in self._OUT[:-2]:
+            setattr(self, name, torch.full((max(n_out, 1),), f, dtype=torch.int32, device=dev))
+        self.conf = torch.full((2 * int(self.conf_off[-1]) + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        self.counts = torch.full((self._PER * max(n, 1),), f, dtype=torch.int64, device=dev)
+
+    def run(self, stream=None) -> None:
+        """Enqueue one call of the entry point on `stream` (default: torch's current stream)."""
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(self._call(C.byref(self._arg), self.ws.data_ptr(), self.ws_bytes, s.cuda_stream))
+
+    def raw(self) -> dict:
+        """Every output array as the device holds it (after a device sync), on the host."""
+        self.torch.cuda.synchronize(self.device)
+        return {k: getattr(self, k).cpu().numpy() for k in self._OUT}
+
+    def results(self, raw: Optional[dict] = None):
+        """Per item its result arrays (if it has any) and conflict pairs, trimmed to its counts
+        and its conflict capacity, or its negative count for an item that failed."""
+        r = self.raw() if raw is None else raw
+        out = []
+        for m in range(len(self.conf_off) - 1):
+            k, nc = int(r["counts"][self._PER * m]), int(r["counts"][self._PER * (m + 1) - 1])
+            if k < 0:
+                out.append(k)
+                continue
+            c = int(self.conf_off[m])
+            nc = min(nc, int(self.conf_off[m + 1]) - c)
+            pairs = r["conf"][2 * c: 2 * (c + nc)].reshape(nc, 2)
+            if self._PER == 1:
+                out.append(pairs)
+            else:
+                o = self._start(m)
+                out.append(tuple(r[x][o: o + k] for x in self._OUT[:-2]) + (pairs,))
+        return out
+
+
+class DeviceBatch(_DeviceMany):
+    """Device-resident inputs, outputs and workspace for repeated smx_compose_batch calls
+    on a list of merges (tests, tools/batch_probe.py).  The optional arguments reach the
+    corners of the C ABI (include/smx.h smx_batch):
+    conflict_caps per-merge capacities of the conflict pairs (default min(n_a, n_b));
+    grid_cap      smx_batch.grid_cap;
+    n_a           per-merge n_a passed instead of the SoAs' own;
+    n_sym         the batch's symbol bound (default: the largest of the merges');
+    n_total       smx_batch.n_total passed instead of the columns' real length;
+    fill          every output word (results, conflict pairs, counts) starts as this value,
+                  and CONF_GUARD such words follow the last merge's conflict region."""
+
+    def __init__(self, soas, device: str = "cuda", conflict_caps=None, grid_cap: int = 0, n_a=None,
+                 n_sym: Optional[int] = None, fill: Optional[int] = None, n_total: Optional[int] = None) -> None:
+        self._open(device)
+        soas = self.soas = list(soas)
+        M = self.n_merges = len(soas)
+        self.off = np.zeros(M + 1, np.int64)
+        np.cumsum([s.n for s in soas], out=self.off[1:])
+        tot = self.n_total = int(self.off[-1])
+        self.n_a = np.asarray([s.n_a for s in soas] if n_a is None else n_a, np.int64).reshape(M)
+        self.n_sym = max([int(s.n_sym) for s in soas] + [1]) if n_sym is None else n_sym
+        self._upload_cols(soas)
+        self._alloc(M, [min(s.n_a, s.n_b) for s in soas] if conflict_caps is None else conflict_caps, tot, fill)
+        self._workspace(lib().smx_compose_batch_workspace_bytes, M)
+        self._idx = [self._up(self.off), self._up(self.n_a), self._up(self.conf_off)]
+        self._call = lib().smx_compose_batch
+        self._arg = _abi.SmxBatch(M, tot if n_total is None else n_total, self.n_sym, self._idx[0].data_ptr(),
+                                  self._idx[1].data_ptr(), *[t.data_ptr() for t in self._in], self.order.data_ptr(),
+                                  self.addr.data_ptr(), self.file.data_ptr(), self.ctx.data_ptr(), self.conf.data_ptr(),
+                                  self._idx[2].data_ptr(), self.counts.data_ptr(), grid_cap)
+
+    def _start(self, m: int) -> int:
+        return int(self.off[m])
+
+
+class DeviceBatchShared(_DeviceMany):
+    """Device-resident inputs, outputs and workspace for repeated smx_compose_batch_shared
+    calls on a SharedSoA (tests, tools/shared_probe.py).  The optional arguments reach the
+    corners of the C ABI (include/smx.h smx_batch_shared):
+    shared_is_b   smx_batch_shared.shared_is_b;
+    conflict_caps per-merge capacities of the conflict pairs (default min(n_shared, len_m));
+    grid_cap      smx_batch_shared.grid_cap;
+    off           the offsets passed instead of the SharedSoA's own;
+    n_sym         the symbol bound passed instead of the SharedSoA's;
+    n_total       smx_batch_shared.n_total passed instead of the columns' real length;
+    fill          every output word (results, conflict pairs, counts) starts as this value,
+                  and CONF_GUARD such words follow the last merge's conflict region."""
+
+    def __init__(self, ssoa, device: str = "cuda", shared_is_b: bool = False, conflict_caps=None, grid_cap: int = 0,
+                 off=None, n_sym: Optional[int] = None, fill: Optional[int] = None,
+                 n_total: Optional[int] = None) -> None:
+        self._open(device)
+        self.ssoa = ssoa
+        M = self.n_merges = ssoa.n_merges
+        S = self.n_shared = int(ssoa.n_shared)
+        self.off = np.asarray(ssoa.off if off is None else off, np.int64).reshape(M + 1)
+        tot = self.n_total = int(ssoa.n_total)
+        lens = np.diff(np.asarray(ssoa.off, np.int64))
+        self.n_sym = int(ssoa.n_sym) if n_sym is None else n_sym
+        self.n_out = tot - S + M * S
+        self._upload_cols([ssoa])
+        self._alloc(M, np.minimum(lens, S) if conflict_caps is None else conflict_caps, self.n_out, fill)
+        self._workspace(lib().smx_compose_batch_shared_workspace_bytes, M)
+        self._idx = [self._up(self.off), self._up(self.conf_off)]
+        self._call = lib().smx_compose_batch_shared
+        self._arg = _abi.SmxBatchShared(M, tot if n_total is None else n_total, self.n_sym, S, self._idx[0].data_ptr(),
+                                        *[t.data_ptr() for t in self._in], self.order.data_ptr(), self.addr.data_ptr(),
+                                        self.file.data_ptr(), self.ctx.data_ptr(), self.conf.data_ptr(),
+                                        self._idx[1].data_ptr(), self.counts.data_ptr(), grid_cap, int(shared_is_b))
+
+    def slot(self, m: int) -> int:
+        """r(m): where merge m's results start in order / addr / file / ctx."""
+        return int(self.off[m]) + (m - 1) * self.n_shared
+
+    _start = slot
+
+
+class DeviceScreen(_DeviceMany):
+    """Device-resident inputs, outputs and workspace for repeated smx_screen calls on a
+    LogsSoA and a list of (i, j) pairs (tests, tools/screen_probe.py).  The optional
+    arguments reach the corners of the C ABI (include/smx.h smx_screen):
+    conflict_caps per-pair capacities of the conflict pairs (default: min of the two logs'
+                  renames, which always suffices); "null": conflicts and conf_off are NULL;
+    grid_cap      smx_screen.grid_cap;
+    log_off       the offsets passed instead of the LogsSoA's own;
+    n_total       smx_screen.n_total passed instead of the columns' real length;
+    fill          every output word (conflict pairs, counts) starts as this value, and
+                  CONF_GUARD such words follow the last pair's conflict region;
+    large         smx_screen_ex with SMX_SCREEN_LARGE (no limit on renames, no counts -2) and
+                  the workspace it asks for, instead of smx_screen."""
+
+    _OUT = ("conf", "counts")
+    _PER = 1
+
+    def __init__(self, lsoa, pairs, device: str = "cuda", conflict_caps=None, grid_cap: int = 0, log_off=None,
+                 n_total: Optional[int] = None, fill: Optional[int] = None, large: bool = False) -> None:
+        self._open(device)
+        self.lsoa = lsoa
+        L = self.n_logs = lsoa.n_logs
+        self.pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+        P = self.n_pairs = len(self.pairs)
+        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
+        tot = self.n_total = int(lsoa.n_total)
+        self.null_conf = isinstance(conflict_caps, str) and conflict_caps == "null"
+        if conflict_caps is None:
+            ren = _rename_counts(lsoa.kind, lsoa.log_off)
+            ok = ((self.pairs >= 0) & (self.pairs < L)).all(axis=1)
+            pa, pb = np.where(ok, self.pairs[:, 0], 0), np.where(ok, self.pairs[:, 1], 0)
+            caps = np.where(ok, np.minimum(ren[pa], ren[pb]), 0) if L else np.zeros(P, np.int64)
+        else:
+            caps = np.zeros(P, np.int64) if self.null_conf else conflict_caps
+        self._upload_cols([lsoa], SCREEN_COLS)
+        self._alloc(P, caps, 0, fill)
+        if large:
+            self._workspace(lib().smx_screen_ex_workspace_bytes, L, tot, P, _abi.SCREEN_LARGE)
+            self._call = lambda arg, ws, nbytes, st: lib().smx_screen_ex(arg, ws, nbytes, _abi.SCREEN_LARGE, st)
+        else:
+            self._workspace(lib().smx_screen_workspace_bytes, L, tot, P)
+            self._call = lib().smx_screen
+        self._idx = [self._up(self.log_off), self._up(self.pairs[:, 0]), self._up(self.pairs[:, 1]),
+                     self._up(self.conf_off)]
+        self._arg = _abi.SmxScreen(L, tot if n_total is None else n_total, P, self._idx[0].data_ptr(),
+                                   *[_ptr(t) for t in self._in], _ptr(self._idx[1]), _ptr(self._idx[2]),
+                                   0 if self.null_conf else self.conf.data_ptr(),
+                                   0 if self.null_conf else self._idx[3].data_ptr(), self.counts.data_ptr(), grid_cap)
+
+
+class DeviceCandidates(_DeviceMany):
+    """Device-resident inputs, outputs and workspace for repeated smx_screen_candidates calls
+    on a LogsSoA (tests, tools/cand_probe.py).  The optional arguments reach the corners of
+    the C ABI (include/smx.h smx_candidates):
+    pair_cap      capacity of pair_a / pair_b (default: all n (n - 1) / 2 pairs); 0: both NULL;
+    grid_cap      smx_candidates.grid_cap;
+    log_off       the offsets passed instead of the LogsSoA's own;
+    n_total       smx_candidates.n_total passed instead of the columns' real length;
+    fill          every output word (pairs, counts, log_info) starts as this value, and
+                  CONF_GUARD such words follow pair_cap and the logs' entries;
+    with_log_info False: smx_candidates.log_info is NULL."""
+
+    _OUT = ("pair_a", "pair_b", "counts", "log_info")
+
+    def __init__(self, lsoa, device: str = "cuda", pair_cap: Optional[int] = None, grid_cap: int = 0, log_off=None,
+                 n_total: Optional[int] = None, fill: Optional[int] = None, with_log_info: bool = True) -> None:
+        self._open(device)
+        torch, dev = self.torch, self.device
+        self.lsoa = lsoa
+        L = self.n_logs = lsoa.n_logs
+        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
+        tot = self.n_total = int(lsoa.n_total)
+        self.pair_cap = L * (L - 1) // 2 if pair_cap is None else pair_cap
+        f = 0 if fill is None else fill
+        self._upload_cols([lsoa], CAND_COLS)
+        self.pair_a = torch.full((self.pair_cap + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        self.pair_b = torch.full((self.pair_cap + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        self.counts = torch.full((2 + self.CONF_GUARD,), f, dtype=torch.int64, device=dev)
+        self.log_info = torch.full((L + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        self._workspace(lib().smx_screen_candidates_workspace_bytes, L, tot)
+        self._idx = [self._up(self.log_off)]
+        self._call = lib().smx_screen_candidates
+        self._arg = _abi.SmxCandidates(L, tot if n_total is None else n_total, self._idx[0].data_ptr(),
+                                       *[_ptr(t) for t in self._in],
+                                       self.pair_a.data_ptr() if self.pair_cap else 0,
+                                       self.pair_b.data_ptr() if self.pair_cap else 0, self.pair_cap,
+                                       self.counts.data_ptr(), self.log_info.data_ptr() if with_log_info else 0, grid_cap)
+
+    def results(self, raw: Optional[dict] = None):
+        """(pairs, n_candidates, n_invalid, log_info): the written candidates as an (n, 2)
+        array (the first pair_cap of them), the full count, the invalid logs, every log's entry."""
+        r = self.raw() if raw is None else raw
+        n, bad = int(r["counts"][0]), int(r["counts"][1])
+        k = min(n, self.pair_cap)
+        return np.stack([r["pair_a"][:k], r["pair_b"][:k]], axis=1), n, bad, r["log_info"][: self.n_logs]

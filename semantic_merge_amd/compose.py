@@ -18,7 +18,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._abi import BATCH_MAX_OPS
-from ._lib import dropin_session
+from ._session import dropin_session
 from .marshal import marshal_logs, marshal_native, marshal_shared
 from .materialize import conflict_factory, materialize_conflicts, materialize_ops_native
 

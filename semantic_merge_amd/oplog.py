@@ -157,7 +157,7 @@ def decode_pair(text_a: Any, text_b: Any, op_cls: type = Op, target_cls: type = 
 def compose_json(text_a: Any, text_b: Any, op_cls: type = Op, target_cls: type = Target):
     """compose_oplogs(OpLog.from_json(text_a).ops, OpLog.from_json(text_b).ops) with the
     decode and the marshal fused (decode_pair)."""
-    from ._lib import dropin_session
+    from ._session import dropin_session
     from .materialize import materialize_conflicts, materialize_ops_native
     ops_a, ops_b, soa = decode_pair(text_a, text_b, op_cls, target_cls)
     with dropin_session() as sess:  # (views of its staging area, materialised while held)
