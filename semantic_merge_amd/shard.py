@@ -46,7 +46,7 @@ FIELDS = ("kind", "ts", "hi", "lo", "sym", "v0", "v1")
 S_KINDS, S_REN, S_MVNONE, S_FAIL = 0, 18, 20, 21
 S_OPEN, S_AHEAD, S_D, S_NCONF, S_NSKIP, S_OVER, S_WIDTH = 22, 23, 24, 25, 26, 27, 28
 S_TABOVER = 31   # a value too wide for the 32-bit partial tables (smx_shard.tab32)
-TAB32_MAX_BITS = 8  # the widest rank tag smx_shard_step accepts in 32-bit entries (smx_compose.hip TABLES)
+TAB32_MAX_BITS = 8  # the widest rank tag smx_shard_step accepts in 32-bit entries (smx_shard.h TABLES)
 
 
 def tab32_bits(world: int) -> int:

@@ -404,3 +404,85 @@ def test_dropin_reentrant_merge_from_materialise():
     assert got == want
     assert [(i, t, a, p) for i, t, a, p, _ in want[0]] == [
         (d["id"], d["type"], d["target"]["addressId"], d["params"]) for d in case["out"]]
+
+
+# ---------------------------------------------------------------------------
+# every fallback of the order plans, at the smallest shape that takes it
+
+_FALLBACK_PLANS = {"halving": "presorted", "wide_rearm": "presorted-wide", "wide_fresh": "presorted-wide",
+                   "segmented": "segmented", "radix_seg_over": "radix", "radix_unordered": "radix",
+                   "radix_lo": "radix+oid_lo"}
+_fallback_cache = {}
+
+
+def _fallback_case(name):
+    """(log, oracle result): a log of distinct timestamps (local op i of A at 2i, of B at
+    2i + 1, so the merged order alternates) with one equal-timestamp group of `h` ops per
+    branch from local op 500 on (merged positions 1000 .. 1000 + 2h), or one defect.
+
+    halving         h = 700: the 1792-op target's window [1000, 3584) and the 768-op
+                    target's [1000, 3072) overflow a 2048-op window, the 256-op target's
+                    windows hold the group (1400 ops) and at most 255 more
+    wide_fresh      h = 1025: 2050 ops, just over a normal window at every target; too
+                    short for k_fpart's long-group test (a branch's chunk samples 2048 ops
+                    apart), so the wide windows start over (run_presorted at the wide level)
+    wide_rearm      h = 2400: k_fpart's long-group verdict, then the wide windows over the
+                    standing plan (run_presorted_rewide)
+    segmented       h = 4100: 8200 ops, just over a wide window; each branch's group fits a
+                    segmented-sort tile
+    radix_seg_over  h = 8200 per branch: longer than the segmented sort's tiles hold
+    radix_unordered no group; one timestamp of A decreases
+    radix_lo        ... and two neighbours in A share (timestamp, oid_hi)"""
+    if name in _fallback_cache:
+        return _fallback_cache[name]
+    h = {"halving": 700, "wide_fresh": 1025, "wide_rearm": 2400, "segmented": 4100, "radix_seg_over": 8200}.get(name, 0)
+    per_branch = max(3000, h + 900)
+    soa = synth.lift_soa(synth.lift_logs(synth.LiftSpec(2 * per_branch, 50, 83, mix=synth.ADVERSARIAL_MIX)))
+    assert min(soa.n_a, soa.n_b) >= 500 + h + 300 and soa.n > 2048
+    for side, (lo, m) in enumerate(((0, soa.n_a), (soa.n_a, soa.n_b))):
+        soa.ts[lo:lo + m] = np.uint64(1000) + np.uint64(2) * np.arange(m, dtype=np.uint64) + np.uint64(side)
+        soa.ts[lo + 500:lo + 500 + h] = np.uint64(2000)  # one timestamp on both branches
+    if name in ("radix_unordered", "radix_lo"):
+        soa.ts[1500] = soa.ts[1499] - np.uint64(3)
+    if name == "radix_lo":
+        soa.ts[101] = soa.ts[100]
+        soa.oid_hi[101] = soa.oid_hi[100]
+        soa.oid_lo[101] = soa.oid_lo[100] ^ np.uint64(1)
+    _fallback_cache[name] = (soa, oracle.compose(soa))
+    return _fallback_cache[name]
+
+
+@pytest.mark.parametrize("mode", ["sync", "async"])
+@pytest.mark.parametrize("name", list(_FALLBACK_PLANS))
+def test_gpu_order_fallbacks(name, mode):
+    """Each branch of the fallback chain behind a failed presorted attempt, through the
+    synchronous smx_compose and through smx_compose_async + smx_compose_finish: the plan
+    that ends the chain and parity with the oracle.  The halving loop ends on the plan it
+    began with, so its case also counts the presorted window launches."""
+    from semantic_merge_amd import _lib
+    soa, ref = _fallback_case(name)
+    dc = DeviceCompose(soa)
+    L = _lib.lib()
+    L.smx_set_profiling(1)
+    try:
+        L.smx_reset_stage_times()
+        if mode == "sync":
+            dc.run()
+        else:
+            dc.run_async()
+            dc.torch.cuda.synchronize()
+            assert int(dc.counts[0].item()) == -2  # the presorted attempt failed: finish has work
+            dc.finish()
+        dc.torch.cuda.synchronize()
+        st = _lib.stage_times()
+    finally:
+        L.smx_set_profiling(0)
+    plan = dc.last_plan()
+    print(f"PLAN {mode} {name} -> {plan}; stage calls {({k: c for k, (ms, c) in st.items() if c})}")
+    _eq_soa(dc.results(), ref, f"{name} ({mode}, plan {plan})")
+    assert plan == _FALLBACK_PLANS[name]
+    if name == "halving":
+        assert st["window"][1] == 3, st  # targets 1792, 768, 256
+        assert st["window_wide"][1] == 0 and st["gsort"][1] == 0, st
+    if mode == "async" and name == list(_FALLBACK_PLANS)[-1]:
+        _fallback_cache.clear()
