@@ -11,6 +11,7 @@ from semantic_merge_amd.compose import compose_oplogs
 from semantic_merge_amd.marshal import marshal
 
 from _shapes import alternating_groups as _alternating_groups
+from _tail_shapes import chain_case as _chain
 from _util import _eq_soa, assert_case, jline, load, to_ops
 
 pytestmark = pytest.mark.gpu
@@ -290,28 +291,6 @@ def test_invalid_input_fails_loudly():
     soa.kind[11] = 40
     with pytest.raises(SmxError):
         compose_soa(soa)
-
-
-def _chain(n_ren, seed, interleave):
-    """One DivergentRename region as long as the logs: every op renames symbol 0.  A's
-    renames all take name class 0; B's class 1 (every head pair conflicts) or, with
-    interleave, a random class per rename and interleaved timestamps (equal names do
-    not conflict, so the pairing drifts along the chain)."""
-    from semantic_merge_amd.marshal import SoA
-    rng = np.random.default_rng(seed)
-    na = nb = n_ren
-    kind = np.full(na + nb, 1, np.uint8)
-    if interleave:
-        ts = np.concatenate([np.arange(na, dtype=np.uint64) * 2, np.arange(nb, dtype=np.uint64) * 2 + 1])
-    else:
-        ts = np.concatenate([np.arange(na, dtype=np.uint64), np.uint64(na) + np.arange(nb, dtype=np.uint64)])
-    hi = rng.integers(0, 2**63, size=na + nb, dtype=np.int64).astype(np.uint64)
-    lo = rng.integers(0, 2**63, size=na + nb, dtype=np.int64).astype(np.uint64)
-    sym = np.zeros(na + nb, np.uint32)
-    v0 = np.concatenate([np.zeros(na, np.int32),
-                         rng.integers(0, 2, nb).astype(np.int32) if interleave else np.ones(nb, np.int32)])
-    v1 = v0.copy()
-    return SoA(na, nb, kind, ts, hi, lo, sym, v0, v1, 1, ["a", "b"])
 
 
 @pytest.mark.parametrize("interleave", [False, True])
