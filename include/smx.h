@@ -252,6 +252,54 @@ int smx_compose_batch_shared_workspace_bytes(int64_t n_merges, size_t* bytes);
 int smx_compose_batch_shared(const smx_batch_shared* b, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * smx_compose_batch and smx_compose_batch_shared with flags.  flags = 0 is the unflagged call
+ * bit for bit -- the same launches, workspace size and results, counts -2 included:
+ * smx_compose_batch(...) == smx_compose_batch_ex(..., 0, stream), and
+ * smx_compose_batch_workspace_bytes(n, bytes) == smx_compose_batch_ex_workspace_bytes(n, any, 0,
+ * bytes); the shared forms alike.  A flag bit that is not defined here gives SMX_E_ARG before
+ * any HIP call (and before any other check).
+ *
+ * SMX_BATCH_LARGE lifts the limit of 2048 ops per merge: counts -2 is never reported, and a
+ * merge of any length (the shared form counts n_shared + len_m) gets exactly what smx_compose
+ * gives on that merge alone -- counts[2m], order/addr/file/ctx, counts[2m+1] and the conflict
+ * pairs, in the same order and at the same places of the struct.  Everything else is the
+ * unflagged contract: the -1 rules (bounds checked before any column of the merge is read; a
+ * kind >= 18 or sym >= n_sym anywhere in the merge found before anything is written for it),
+ * truncation by conf_off, nothing written at or past a merge's regions, failed merges that do
+ * not touch their neighbours, grid_cap (which also caps the added launch), shared_is_b.
+ *
+ * How: a merge over 2048 ops is one 1024-thread workgroup's work, through global memory: its op
+ * indices sorted in tiles of 2048 (in LDS) and merge levels between two index arrays, the
+ * DivergentRename walk in rounds of up to 1024 renames per side from the two heads (as
+ * SMX_SCREEN_LARGE), the chains in an exact open-addressing table on the 32-bit symbol, emit.
+ * Merges of at most 2048 ops run in the three size classes as before, in the same call.
+ *
+ * Stream-ordered as smx_compose_batch: five launches with SMX_BATCH_LARGE (four with flags = 0)
+ * whatever the data, no host synchronisation, no allocation, no read-back; the call clears the
+ * workspace state it needs, so one workspace serves any sequence of calls with either flags.
+ *
+ * Limits with SMX_BATCH_LARGE: n_total <= 2^31 - 1, and for the shared form the result size
+ * n_out = n_total - n_shared + n_merges * n_shared too (SMX_E_ARG above it).  One workgroup
+ * runs a large merge, so one merge of millions of ops is served slowly (smx_compose spreads it
+ * over the chip); many merges spread over the chip.
+ */
+#define SMX_BATCH_LARGE 1u
+/* Workspace for the _ex calls with the same flags (8-byte aligned with SMX_BATCH_LARGE).  With
+ * SMX_BATCH_LARGE it is linear in the result size: the unflagged bytes, 4 bytes per merge, and
+ * 64 bytes per op of n_total (shared: per entry of n_out); a large merge works in the slice at
+ * its own result offset, so there are no per-workgroup slots and no cap on a merge's length. */
+int smx_compose_batch_ex_workspace_bytes(int64_t n_merges, int64_t n_total, uint32_t flags, size_t* bytes);
+int smx_compose_batch_shared_ex_workspace_bytes(int64_t n_merges, int64_t n_total, int64_t n_shared, uint32_t flags,
+                                                size_t* bytes);
+/* SMX_E_ARG (an unknown flag; then the unflagged calls'; with SMX_BATCH_LARGE n_total or n_out
+ * over 2^31 - 1) and SMX_E_WORKSPACE (too small for these flags, or with SMX_BATCH_LARGE not
+ * 8-byte aligned) are reported before any HIP call; n_merges = 0 returns SMX_OK and launches
+ * nothing. */
+int smx_compose_batch_ex(const smx_batch* b, void* workspace, size_t workspace_bytes, uint32_t flags, void* stream);
+int smx_compose_batch_shared_ex(const smx_batch_shared* b, void* workspace, size_t workspace_bytes, uint32_t flags,
+                                void* stream);
+
+/*
  * Conflict screen: which of n_pairs pairs of logs, taken from n_logs logs stored once, have
  * DivergentRename conflicts, and which ones -- without composing any pair (a merge queue asking
  * which pull requests conflict with the target branch, or with each other).  The conflict

@@ -200,6 +200,7 @@ class SmxRgaOut(C.Structure):
 # Every symbol include/smx.h declares (tests check the built library exports them).
 RGA_GROUPED = 1   # smx_rga_replay_ex flag (include/smx.h SMX_RGA_GROUPED)
 SCREEN_LARGE = 1  # smx_screen_ex flag (include/smx.h SMX_SCREEN_LARGE): no limit on renames
+BATCH_LARGE = 1   # smx_compose_batch_ex / _shared_ex flag (include/smx.h SMX_BATCH_LARGE): no limit on ops
 
 EXPORTS = (
     "smx_compose_workspace_bytes",
@@ -213,6 +214,10 @@ EXPORTS = (
     "smx_compose_batch",
     "smx_compose_batch_shared_workspace_bytes",
     "smx_compose_batch_shared",
+    "smx_compose_batch_ex_workspace_bytes",
+    "smx_compose_batch_ex",
+    "smx_compose_batch_shared_ex_workspace_bytes",
+    "smx_compose_batch_shared_ex",
     "smx_screen_workspace_bytes",
     "smx_screen",
     "smx_screen_ex_workspace_bytes",
@@ -261,6 +266,17 @@ def declare(lib: C.CDLL) -> C.CDLL:
         lib.smx_compose_batch_shared_workspace_bytes.restype = C.c_int
         lib.smx_compose_batch_shared.argtypes = [C.POINTER(SmxBatchShared), C.c_void_p, C.c_size_t, C.c_void_p]
         lib.smx_compose_batch_shared.restype = C.c_int
+    if hasattr(lib, "smx_compose_batch_ex"):  # (older builds, e.g. A/B baselines, lack it)
+        lib.smx_compose_batch_ex_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_uint32, C.POINTER(C.c_size_t)]
+        lib.smx_compose_batch_ex_workspace_bytes.restype = C.c_int
+        lib.smx_compose_batch_ex.argtypes = [C.POINTER(SmxBatch), C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+        lib.smx_compose_batch_ex.restype = C.c_int
+        lib.smx_compose_batch_shared_ex_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_uint32,
+                                                                    C.POINTER(C.c_size_t)]
+        lib.smx_compose_batch_shared_ex_workspace_bytes.restype = C.c_int
+        lib.smx_compose_batch_shared_ex.argtypes = [C.POINTER(SmxBatchShared), C.c_void_p, C.c_size_t, C.c_uint32,
+                                                    C.c_void_p]
+        lib.smx_compose_batch_shared_ex.restype = C.c_int
     if hasattr(lib, "smx_screen"):  # (older builds, e.g. A/B baselines, lack it)
         lib.smx_screen_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]
         lib.smx_screen_workspace_bytes.restype = C.c_int

@@ -195,10 +195,13 @@ class DeviceBatch(_DeviceMany):
     n_sym         the batch's symbol bound (default: the largest of the merges');
     n_total       smx_batch.n_total passed instead of the columns' real length;
     fill          every output word (results, conflict pairs, counts) starts as this value,
-                  and CONF_GUARD such words follow the last merge's conflict region."""
+                  and CONF_GUARD such words follow the last merge's conflict region;
+    flags         smx_compose_batch_ex's flags (_abi.BATCH_LARGE: no limit on a merge's ops, no
+                  counts -2) and the workspace it asks for with them."""
 
     def __init__(self, soas, device: str = "cuda", conflict_caps=None, grid_cap: int = 0, n_a=None,
-                 n_sym: Optional[int] = None, fill: Optional[int] = None, n_total: Optional[int] = None) -> None:
+                 n_sym: Optional[int] = None, fill: Optional[int] = None, n_total: Optional[int] = None,
+                 flags: int = 0) -> None:
         self._open(device)
         soas = self.soas = list(soas)
         M = self.n_merges = len(soas)
@@ -209,9 +212,10 @@ class DeviceBatch(_DeviceMany):
         self.n_sym = max([int(s.n_sym) for s in soas] + [1]) if n_sym is None else n_sym
         self._upload_cols(soas)
         self._alloc(M, [min(s.n_a, s.n_b) for s in soas] if conflict_caps is None else conflict_caps, tot, fill)
-        self._workspace(lib().smx_compose_batch_workspace_bytes, M)
+        self.flags = flags
+        self._workspace(lib().smx_compose_batch_ex_workspace_bytes, M, tot, flags)
         self._idx = [self._up(self.off), self._up(self.n_a), self._up(self.conf_off)]
-        self._call = lib().smx_compose_batch
+        self._call = lambda arg, ws, nbytes, st: lib().smx_compose_batch_ex(arg, ws, nbytes, self.flags, st)
         self._arg = _abi.SmxBatch(M, tot if n_total is None else n_total, self.n_sym, self._idx[0].data_ptr(),
                                   self._idx[1].data_ptr(), *[t.data_ptr() for t in self._in], self.order.data_ptr(),
                                   self.addr.data_ptr(), self.file.data_ptr(), self.ctx.data_ptr(), self.conf.data_ptr(),
@@ -232,11 +236,13 @@ class DeviceBatchShared(_DeviceMany):
     n_sym         the symbol bound passed instead of the SharedSoA's;
     n_total       smx_batch_shared.n_total passed instead of the columns' real length;
     fill          every output word (results, conflict pairs, counts) starts as this value,
-                  and CONF_GUARD such words follow the last merge's conflict region."""
+                  and CONF_GUARD such words follow the last merge's conflict region;
+    flags         smx_compose_batch_shared_ex's flags (_abi.BATCH_LARGE) and the workspace it
+                  asks for with them."""
 
     def __init__(self, ssoa, device: str = "cuda", shared_is_b: bool = False, conflict_caps=None, grid_cap: int = 0,
                  off=None, n_sym: Optional[int] = None, fill: Optional[int] = None,
-                 n_total: Optional[int] = None) -> None:
+                 n_total: Optional[int] = None, flags: int = 0) -> None:
         self._open(device)
         self.ssoa = ssoa
         M = self.n_merges = ssoa.n_merges
@@ -248,9 +254,10 @@ class DeviceBatchShared(_DeviceMany):
         self.n_out = tot - S + M * S
         self._upload_cols([ssoa])
         self._alloc(M, np.minimum(lens, S) if conflict_caps is None else conflict_caps, self.n_out, fill)
-        self._workspace(lib().smx_compose_batch_shared_workspace_bytes, M)
+        self.flags = flags
+        self._workspace(lib().smx_compose_batch_shared_ex_workspace_bytes, M, tot, S, flags)
         self._idx = [self._up(self.off), self._up(self.conf_off)]
-        self._call = lib().smx_compose_batch_shared
+        self._call = lambda arg, ws, nbytes, st: lib().smx_compose_batch_shared_ex(arg, ws, nbytes, self.flags, st)
         self._arg = _abi.SmxBatchShared(M, tot if n_total is None else n_total, self.n_sym, S, self._idx[0].data_ptr(),
                                         *[t.data_ptr() for t in self._in], self.order.data_ptr(), self.addr.data_ptr(),
                                         self.file.data_ptr(), self.ctx.data_ptr(), self.conf.data_ptr(),

@@ -132,6 +132,11 @@ class ComposeSession:
     last merge in seconds."""
 
     ASYNC_MAX = 1 << 22  # smx_compose_async + one sync below this many ops (SMX_EARLY_MIN)
+    # large=True: merges of up to this many ops join the batch (SMX_BATCH_LARGE: one workgroup
+    # each); longer ones belong on the whole chip and go through compose().  Measured (DESIGN.md
+    # §16, profiles/batch_large/): the largest probed size at which a batch of 16 merges still
+    # beats the loop of smx_compose calls -- 1.9x at 16,000 ops, 0.4x at 64,000.
+    LARGE_MAX = 16000
 
     def __init__(self, device: str = "cuda") -> None:
         self.torch = _torch()
@@ -311,9 +316,10 @@ class ComposeSession:
             + [("off", (m + 1) * 8), ("n_a", m * 8), ("conf_off", (m + 1) * 8)], q, 4 * tot, 16 * m)}
 
     def staging_many(self, ns):
-        """The input columns of a batch of merges of ns ops (each at most BATCH_MAX_OPS) as
-        views of the pinned staging area, one dict per merge, laid out as compose_many()
-        copies them: SoAs marshalled into them are not packed again."""
+        """The input columns of a batch of merges of ns ops (each at most BATCH_MAX_OPS, or with
+        compose_many(large=True) of any size) as views of the pinned staging area, one dict per
+        merge, laid out as compose_many() copies them: SoAs marshalled into them are not packed
+        again."""
         lay = self._batch_layout(ns)
         self._ensure(self.main, lay["in_bytes"], lay["out_bytes"], 0)
         hin = self.main.hin
@@ -321,18 +327,26 @@ class ComposeSession:
         return [{name: hin[lay[name] + int(offs[m]) * dt.itemsize: lay[name] + int(offs[m + 1]) * dt.itemsize].view(dt)
                  for name, dt, _ in OP_COLS} for m in range(len(ns))]
 
-    def compose_many(self, soas, copy: bool = True):
+    def compose_many(self, soas, copy: bool = True, large: bool = False, large_max: Optional[int] = None):
         """[(order, addr, file, ctx, conflict_pairs)] of independent merges, in input order.
         The merges of at most BATCH_MAX_OPS ops are packed at consecutive offsets of the
         staging area and run as one batch: one host-to-device copy, one smx_compose_batch,
         one copy back, one stream sync.  Larger merges (and any the library sends back,
         counts -2) go through compose() afterwards.  An invalid merge raises SmxError naming
         its index.  copy=False: views of the staging area, valid until the session's next
-        merge (taken only when no merge is routed through compose())."""
+        merge (taken only when no merge is routed through compose()).  large=True: merges of up
+        to large_max ops (default LARGE_MAX, measured: DESIGN.md §16) join the batch too (smx_compose_batch_ex
+        with SMX_BATCH_LARGE), and only longer ones go through compose(); `last` then holds the
+        call's legs, "large" (merges over BATCH_MAX_OPS ops that ran in the batch) and "routed"."""
+        t0 = time.perf_counter()
         soas = list(soas)
-        small = [i for i, s in enumerate(soas) if s.n <= _abi.BATCH_MAX_OPS]
-        routed = [i for i, s in enumerate(soas) if s.n > _abi.BATCH_MAX_OPS]
+        flags = _abi.BATCH_LARGE if large else 0
+        limit = (self.LARGE_MAX if large_max is None else max(int(large_max), _abi.BATCH_MAX_OPS)) if large \
+            else _abi.BATCH_MAX_OPS
+        small = [i for i, s in enumerate(soas) if s.n <= limit]
+        routed = [i for i, s in enumerate(soas) if s.n > limit]
         res = [None] * len(soas)
+        legs = _last(("large", "routed"))
         if small:
             M = len(small)
             ns = [soas[i].n for i in small]
@@ -350,22 +364,26 @@ class ComposeSession:
                 cols += [(getattr(soa, name), lay[name] + int(off[m]) * dt.itemsize, n * dt.itemsize)
                          for name, dt, _ in OP_COLS]
             q = lay["q"]
-            self._staged_call(
-                self.main, lib().smx_compose_batch_workspace_bytes, (M,), lay, cols,
+            t1, t2 = self._staged_call(
+                self.main, lib().smx_compose_batch_ex_workspace_bytes, (M, lay["n_total"], flags), lay, cols,
                 (("off", off), ("n_a", n_a), ("conf_off", conf_off)),
                 lambda d0, o0: _abi.SmxBatch(M, lay["n_total"], n_sym, d0 + lay["off"], d0 + lay["n_a"],
                                              *[d0 + lay[name] for name, _, _ in OP_COLS],
                                              o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"],
                                              d0 + lay["conf_off"], o0 + lay["counts"], 0),
-                lib().smx_compose_batch)
+                lambda arg, ws, nbytes, st: lib().smx_compose_batch_ex(arg, ws, nbytes, flags, st))
             for i, r in zip(small, self._batch_results(lay, conf_off, off[:-1], small)):
                 res[i] = r
                 if r is None:
                     routed.append(i)
             if copy or routed:  # (compose() below reuses the staging area)
                 res = [r if r is None else tuple(x.copy() for x in r) for r in res]
+            legs = _last(pack_s=t1 - t0, device_s=t2 - t1, unpack_s=time.perf_counter() - t2,
+                         large=sum(n > _abi.BATCH_MAX_OPS for n in ns) if large else 0)
         routed.sort()
         self._compose_routed(res, routed, [soas[i] for i in routed], "merge", keep_last=False)
+        if large:
+            self.last = {**legs, "routed": len(routed)}
         return res
 
     # -- batched compose against one shared log (smx_compose_batch_shared) -------------------
@@ -382,15 +400,16 @@ class ComposeSession:
             + [("off", (m + 1) * 8), ("conf_off", (m + 1) * 8)], q, 8 * (n_total - n_shared), 16 * m)}
 
     def staging_shared(self, n_total: int, n_shared: int, n_merges: int) -> dict:
-        """The input columns of a shared-log batch of n_total ops as views of the pinned
-        staging area, laid out as compose_shared() copies them: a SharedSoA marshalled into
-        them is not packed again."""
+        """The input columns of a shared-log batch of n_total ops (of any size) as views of the
+        pinned staging area, laid out as compose_shared() copies them: a SharedSoA marshalled
+        into them is not packed again."""
         lay = self._shared_layout(n_total, n_shared, n_merges)
         self._ensure(self.main, lay["in_bytes"], lay["out_bytes"], 0)
         hin = self.main.hin
         return {name: hin[lay[name]: lay[name] + n_total * dt.itemsize].view(dt) for name, dt, _ in OP_COLS}
 
-    def compose_shared(self, ssoa, shared_is_b: bool = False, copy: bool = True):
+    def compose_shared(self, ssoa, shared_is_b: bool = False, copy: bool = True, large: bool = False,
+                       large_max: Optional[int] = None):
         """[(order, addr, file, ctx, conflict_pairs)] of the merges (shared, branch m) -- or
         (branch m, shared) with shared_is_b -- of a SharedSoA, in branch order.  The columns,
         the shared log once, are staged as they are: one host-to-device copy, one
@@ -398,7 +417,11 @@ class ComposeSession:
         ops (the library sends them back, counts -2) go through compose(ssoa.merge(m))
         afterwards.  Invalid input raises SmxError naming the merge.  copy=False: views of
         the staging area, valid until the session's next merge (taken only when no merge is
-        routed through compose())."""
+        routed through compose()).  large=True: merges of up to large_max ops, the shared log
+        counted (default LARGE_MAX), run in the batch too (smx_compose_batch_shared_ex
+        with SMX_BATCH_LARGE) and `last` gains "large" and "routed"; the call takes every merge
+        of the columns or none, so a batch that holds a merge over large_max runs as large=False
+        does (that merge and every other one over BATCH_MAX_OPS ops through compose())."""
         t0 = time.perf_counter()
         M, S, tot = ssoa.n_merges, int(ssoa.n_shared), int(ssoa.n_total)
         off = np.ascontiguousarray(ssoa.off, dtype=np.int64)
@@ -414,20 +437,23 @@ class ComposeSession:
                 at = o0 + int(np.argmax(sym[o0:o1] >= ssoa.n_sym))
                 raise SmxError(-1, f"merge {int(np.searchsorted(off, at, 'right')) - 1}: invalid input: sym >= n_sym")
         res = [None] * M
-        self.last = _last(("in_bytes",))
-        if M and (S + lens <= _abi.BATCH_MAX_OPS).any():
+        self.last = _last(("in_bytes",) + (("large", "routed") if large else ()))
+        limit = self.LARGE_MAX if large_max is None else max(int(large_max), _abi.BATCH_MAX_OPS)
+        flags = _abi.BATCH_LARGE if large and M and bool((S + lens <= limit).all()) else 0
+        n_large = int((S + lens > _abi.BATCH_MAX_OPS).sum()) if flags else 0
+        if M and (flags or (S + lens <= _abi.BATCH_MAX_OPS).any()):
             lay = self._shared_layout(tot, S, M)
             conf_off = np.concatenate([[0], np.cumsum(np.minimum(lens, S), dtype=np.int64)])  # (never truncates)
             q = lay["q"]
             t1, t2 = self._staged_call(
-                self.main, lib().smx_compose_batch_shared_workspace_bytes, (M,), lay,
+                self.main, lib().smx_compose_batch_shared_ex_workspace_bytes, (M, tot, S, flags), lay,
                 [(getattr(ssoa, name), lay[name], tot * dt.itemsize) for name, dt, _ in OP_COLS],
                 (("off", off), ("conf_off", conf_off)),
                 lambda d0, o0: _abi.SmxBatchShared(M, tot, int(ssoa.n_sym), S, d0 + lay["off"],
                                                    *[d0 + lay[name] for name, _, _ in OP_COLS],
                                                    o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"],
                                                    d0 + lay["conf_off"], o0 + lay["counts"], 0, int(bool(shared_is_b))),
-                lib().smx_compose_batch_shared)
+                lambda arg, ws, nbytes, st: lib().smx_compose_batch_shared_ex(arg, ws, nbytes, flags, st))
             res = self._batch_results(lay, conf_off, off[:-1] + (np.arange(M) - 1) * S, range(M))
             routed = [m for m in range(M) if res[m] is None]
             if copy or routed:  # (compose() below reuses the staging area)
@@ -436,6 +462,8 @@ class ComposeSession:
                               in_bytes=lay["in_bytes"])
         else:
             routed = list(range(M))
+        if large:
+            self.last.update(large=n_large, routed=len(routed))
         if routed:
             # (copies: the columns may be views of the staging area that compose() packs into)
             self._compose_routed(res, routed, [ssoa.merge(m, shared_is_b) for m in routed], "merge")
@@ -674,14 +702,15 @@ def compose_soa(soa: SoA, device: str = "cuda"):
     return _free_session(device).compose(soa)
 
 
-def compose_soa_many(soas, device: str = "cuda"):
+def compose_soa_many(soas, device: str = "cuda", large: bool = False, large_max: Optional[int] = None):
     """ComposeSession.compose_many on the thread's free session: independent merges in one batch."""
-    return _free_session(device).compose_many(soas)
+    return _free_session(device).compose_many(soas, large=large, large_max=large_max)
 
 
-def compose_soa_shared(ssoa, shared_is_b: bool = False, device: str = "cuda"):
+def compose_soa_shared(ssoa, shared_is_b: bool = False, device: str = "cuda", large: bool = False,
+                       large_max: Optional[int] = None):
     """ComposeSession.compose_shared on the thread's free session: a SharedSoA's merges in one batch."""
-    return _free_session(device).compose_shared(ssoa, shared_is_b)
+    return _free_session(device).compose_shared(ssoa, shared_is_b, large=large, large_max=large_max)
 
 
 def screen_soa(lsoa, pairs, device: str = "cuda", large: bool = False):

@@ -18,7 +18,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._abi import BATCH_MAX_OPS
-from ._session import dropin_session
+from ._session import ComposeSession, dropin_session
 from .marshal import marshal_logs, marshal_native, marshal_shared
 from .materialize import conflict_factory, materialize_conflicts, materialize_ops_native
 
@@ -38,20 +38,25 @@ def compose_oplogs(delta_a: Sequence[Any], delta_b: Sequence[Any]) -> Tuple[List
     return out, conflicts
 
 
-def compose_many(pairs: Sequence[Tuple[Sequence[Any], Sequence[Any]]]) -> List[Tuple[List[Any], List[Any]]]:
+def compose_many(pairs: Sequence[Tuple[Sequence[Any], Sequence[Any]]],
+                 large: bool = False) -> List[Tuple[List[Any], List[Any]]]:
     """``[compose_oplogs(a, b) for a, b in pairs]`` with the merges of at most 2048 ops run
     as one GPU batch (one copy in, one smx_compose_batch, one copy back, one sync); larger
-    merges take ``compose_oplogs`` one by one.  Inputs are never mutated."""
+    merges take ``compose_oplogs`` one by one.  ``large=True``: merges of up to
+    ``ComposeSession.LARGE_MAX`` ops join the batch too (smx_compose_batch_ex, SMX_BATCH_LARGE),
+    for batches with a tail just past 2048 ops; only longer ones go one by one.  Inputs are
+    never mutated."""
     logs = [(list(a), list(b)) for a, b in pairs]
     res: List[Any] = [None] * len(logs)
-    small = [i for i, (a, b) in enumerate(logs) if len(a) + len(b) <= BATCH_MAX_OPS]
+    limit = ComposeSession.LARGE_MAX if large else BATCH_MAX_OPS
+    small = [i for i, (a, b) in enumerate(logs) if len(a) + len(b) <= limit]
     if small:
         with dropin_session() as sess:
             # each merge marshalled straight into its slice of the pinned staging columns;
             # the results are views of the staging area, materialised while the session is held
             cols = sess.staging_many([len(logs[i][0]) + len(logs[i][1]) for i in small])
             soas = [marshal_native(logs[i][0], logs[i][1], c) for i, c in zip(small, cols)]
-            for i, soa, (order, addr, file, ctx, cpairs) in zip(small, soas, sess.compose_many(soas, copy=False)):
+            for i, soa, (order, addr, file, ctx, cpairs) in zip(small, soas, sess.compose_many(soas, copy=False, large=large)):
                 ops = logs[i][0] + logs[i][1]
                 res[i] = (materialize_ops_native(ops, soa.kind, soa.strings, order, addr, file, ctx),
                           materialize_conflicts(ops, cpairs))
@@ -62,14 +67,16 @@ def compose_many(pairs: Sequence[Tuple[Sequence[Any], Sequence[Any]]]) -> List[T
 
 
 def compose_against(shared: Sequence[Any], branches: Sequence[Sequence[Any]],
-                    shared_side: str = "a") -> List[Tuple[List[Any], List[Any]]]:
+                    shared_side: str = "a", large: bool = False) -> List[Tuple[List[Any], List[Any]]]:
     """``[compose_oplogs(shared, b) for b in branches]`` -- or ``compose_oplogs(b, shared)``
     with ``shared_side="b"`` -- for merges that all have one log on one side: a merge queue
     composing every pull request's delta against the target branch's, a rebase composing
     every commit of a stack against the upstream delta.  The shared log is marshalled and
     copied to the GPU once, and the merges of at most 2048 ops run as one batch (one copy in,
     one smx_compose_batch_shared, one copy back, one sync); larger merges follow one by one.
-    Inputs are never mutated."""
+    ``large=True``: merges of up to ``ComposeSession.LARGE_MAX`` ops, the shared log counted,
+    run in the batch too (smx_compose_batch_shared_ex, SMX_BATCH_LARGE) -- a shared log of more
+    than 2048 ops no longer sends every merge through the loop.  Inputs are never mutated."""
     if shared_side not in ("a", "b"):
         raise ValueError("shared_side must be 'a' or 'b'")
     is_b = shared_side == "b"
@@ -85,7 +92,7 @@ def compose_against(shared: Sequence[Any], branches: Sequence[Sequence[Any]],
         ssoa = marshal_shared(sh, logs, sess.staging_shared(n_total, len(sh), len(logs)))
         kind = ssoa.kind.copy()  # (a merge routed through compose() reuses the staging columns)
         k_sh = kind[: len(sh)]
-        for m, (order, addr, file, ctx, cpairs) in enumerate(sess.compose_shared(ssoa, is_b, copy=False)):
+        for m, (order, addr, file, ctx, cpairs) in enumerate(sess.compose_shared(ssoa, is_b, copy=False, large=large)):
             k_own = kind[int(ssoa.off[m]): int(ssoa.off[m + 1])]
             ops = logs[m] + sh if is_b else sh + logs[m]
             k = np.concatenate([k_own, k_sh] if is_b else [k_sh, k_own])

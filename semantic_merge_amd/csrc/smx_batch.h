@@ -15,7 +15,12 @@
 //   k_compose_batch<N> a grid capped by the class's residency; workgroup b runs the merges
 //                     b, b + grid, ... of the class list one after another, a barrier
 //                     between two (compose_small sets up all its LDS state per merge)
-// Nothing here waits, allocates or reads back: three or four launches on the caller's stream.
+// Nothing here waits, allocates or reads back: four launches on the caller's stream.
+//
+// With SMX_BATCH_LARGE (smx_compose_batch_ex) the limit of SMALL_N ops is gone, in five launches:
+//   k_batch_classify<.., true>  no -2; a merge over SMALL_N ops goes on a fourth list
+//   k_compose_batch_large  after the three classes: one 1024-thread workgroup per merge of that
+//                     list runs the same four steps through global memory (smx_batch_large.h)
 //
 // smx_compose_batch_shared is the same for merges that all have one log on one side (a merge
 // queue against the target branch, a rebase against upstream): the shared log is stored once,
@@ -55,14 +60,22 @@ __device__ __forceinline__ i64 batch_check(const smx_batch_shared& b, i64 m) {
   return b.n_shared + (o1 - o0);
 }
 
-template <typename B>
-__global__ void __launch_bounds__(256) k_batch_classify(B b, u32* cnt, u32* lists, size_t list_stride) {
-  __shared__ u32 c[BATCH_CLASSES];
+// LARGE (SMX_BATCH_LARGE): no merge gets -2; one over SMALL_N ops goes on a fourth list,
+// large_list, for k_compose_batch_large (smx_batch_large.h), its count in cnt[BATCH_CLASSES].
+template <typename B, bool LARGE>
+__global__ void __launch_bounds__(256) k_batch_classify(B b, u32* cnt, u32* lists, size_t list_stride,
+                                                        u32* large_list) {
+  constexpr int NC = BATCH_CLASSES + (LARGE ? 1 : 0);
+  __shared__ u32 c[NC];
   const int t = threadIdx.x;
-  if (t < BATCH_CLASSES) c[t] = 0;
+  if (t < NC) c[t] = 0;
   __syncthreads();
   for (i64 m = t; m < b.n_merges; m += 256) {
     const i64 len = batch_check(b, m);
+    if (LARGE && len == -2) {
+      large_list[atomicAdd(&c[BATCH_CLASSES], 1u)] = (u32)m;
+      continue;
+    }
     if (len < 0) {
       b.counts[2 * m] = len;
       b.counts[2 * m + 1] = len;
@@ -73,7 +86,7 @@ __global__ void __launch_bounds__(256) k_batch_classify(B b, u32* cnt, u32* list
     lists[(size_t)k * list_stride + atomicAdd(&c[k], 1u)] = (u32)m;
   }
   __syncthreads();
-  if (t < BATCH_CLASSES) cnt[t] = c[t];
+  if (t < NC) cnt[t] = c[t];
 }
 
 // Merge m's input and output as compose_small takes them.

@@ -1,5 +1,6 @@
 // smx_batch.hip — the batched entry points of include/smx.h: smx_compose_batch and
-// smx_compose_batch_shared (kernels in smx_batch.h) and smx_screen /
+// smx_compose_batch_shared with their _ex forms (kernels in smx_batch.h and smx_batch_large.h,
+// DESIGN.md §11-12 and §16) and smx_screen /
 // smx_screen_ex (kernels in smx_screen.h), and smx_screen_candidates (kernels in smx_cand.h,
 // DESIGN.md §14), which has a shape of its own: a sort and a bit matrix, no size classes.
 //
@@ -12,12 +13,22 @@
 // (the small kernel's phase stamps belong to the single merge: smx_compose.hip defines the
 // array and reads it, and the batch kernels compiled here keep none)
 #undef SMALL_STAMPS
-#include "smx_batch.h"
+#include "smx_batch_large.h"
 #include "smx_screen.h"
 #include "smx_cand.h"
 
 // The kernels with a residency-capped grid, and the threads of a workgroup of each.
-enum { R_BATCH = 0, R_SHARED = 3, R_EXTRACT = 6, R_SCREEN = 7, R_EXTRACT_LARGE = 10, R_STREAM = 11, R_N = 12 };
+enum {
+  R_BATCH = 0,
+  R_SHARED = 3,
+  R_EXTRACT = 6,
+  R_SCREEN = 7,
+  R_EXTRACT_LARGE = 10,
+  R_STREAM = 11,
+  R_LARGE = 12,
+  R_LARGE_SHARED = 13,
+  R_N = 14
+};
 template <typename B>
 using BatchKernel = void (*)(B, const u32*, const u32*);
 template <typename B>
@@ -60,6 +71,9 @@ static int resident_of(const int** out) {
     threads[R_EXTRACT_LARGE] = SCREEN_TL;
     fn[R_STREAM] = (const void*)k_screen_stream;
     threads[R_STREAM] = SCREEN_N / 2;
+    fn[R_LARGE] = (const void*)k_compose_batch_large<smx_batch>;
+    fn[R_LARGE_SHARED] = (const void*)k_compose_batch_large<smx_batch_shared>;
+    threads[R_LARGE] = threads[R_LARGE_SHARED] = LARGE_NT;
     int cus = 0;
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     for (int k = 0; k < R_N; ++k) {
@@ -93,39 +107,74 @@ static int launch_classes(K* const (&kern)[3], const int (&cap)[3], const int* r
   return SMX_OK;
 }
 
-extern "C" int smx_compose_batch_workspace_bytes(int64_t n_merges, size_t* bytes) {
+// The unflagged workspace: the class counts and the three class lists.
+static size_t batch_base_bytes(int64_t n_merges) { return BATCH_HDR + BATCH_CLASSES * batch_list_bytes(n_merges); }
+
+// Both workspace queries: n_ops result entries (n_total, or the shared form's n_out).
+static int batch_ws_query(int64_t n_merges, int64_t n_total, int64_t n_shared, uint32_t flags, size_t* bytes) {
+  if (flags & ~(uint32_t)SMX_BATCH_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_compose_batch_ex flag");
   if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
   if (n_merges < 0 || n_merges > 0x7fffffffll) return smx_set_error(SMX_E_ARG, "n_merges outside 0 .. 2^31 - 1");
-  *bytes = BATCH_HDR + BATCH_CLASSES * batch_list_bytes(n_merges);
+  size_t need = batch_base_bytes(n_merges);
+  if (flags & SMX_BATCH_LARGE) {
+    if (n_total < 0 || n_shared < 0 || n_shared > n_total)
+      return smx_set_error(SMX_E_ARG, "n_total negative, or n_shared outside 0 .. n_total");
+    const int64_t n_out = n_total - n_shared + n_merges * n_shared;
+    if (n_total > 0x7fffffffll || n_out > 0x7fffffffll)
+      return smx_set_error(SMX_E_ARG, "SMX_BATCH_LARGE: n_total (shared: or n_out) over 2^31 - 1");
+    need += batch_large_bytes(n_merges, n_out);
+  }
+  *bytes = need;
   return SMX_OK;
 }
 
+extern "C" int smx_compose_batch_ex_workspace_bytes(int64_t n_merges, int64_t n_total, uint32_t flags, size_t* bytes) {
+  return batch_ws_query(n_merges, n_total, 0, flags, bytes);
+}
+
+extern "C" int smx_compose_batch_shared_ex_workspace_bytes(int64_t n_merges, int64_t n_total, int64_t n_shared,
+                                                           uint32_t flags, size_t* bytes) {
+  return batch_ws_query(n_merges, n_total, n_shared, flags, bytes);
+}
+
+extern "C" int smx_compose_batch_workspace_bytes(int64_t n_merges, size_t* bytes) {
+  return smx_compose_batch_ex_workspace_bytes(n_merges, 0, 0u, bytes);
+}
+
 extern "C" int smx_compose_batch_shared_workspace_bytes(int64_t n_merges, size_t* bytes) {
-  return smx_compose_batch_workspace_bytes(n_merges, bytes);  // the same class counts and lists
+  return smx_compose_batch_shared_ex_workspace_bytes(n_merges, 0, 0, 0u, bytes);  // the same class counts and lists
 }
 
 // What the two batch structs are checked for alike, from n_sym's bound on; `index_ok`: the
-// struct's own index arrays are set, `index_names` names them.  (A batch of no merges is
-// valid whatever else it holds; batch_run returns at once on it.)
+// struct's own index arrays are set, `index_names` names them; n_ops: the result entries.
+// (A batch of no merges is valid whatever else it holds; batch_run returns at once on it.)
 template <typename B>
-static int batch_check_args(const B* b, bool index_ok, const char* index_names, const void* workspace,
-                            size_t workspace_bytes, const char* ws_query) {
+static int batch_check_args(const B* b, bool index_ok, const char* index_names, int64_t n_ops, const void* workspace,
+                            size_t workspace_bytes, uint32_t flags, const char* ws_query) {
+  const bool large = (flags & SMX_BATCH_LARGE) != 0;
   if (b->n_sym > 0xffffffffll) return smx_set_error(SMX_E_ARG, "n_sym over 2^32 - 1");
+  if (large && (b->n_total > 0x7fffffffll || n_ops > 0x7fffffffll))
+    return smx_set_error(SMX_E_ARG, "SMX_BATCH_LARGE: n_total (shared: or n_out) over 2^31 - 1");
   if (b->n_merges == 0) return SMX_OK;
   if (!index_ok || !b->conf_off || !b->counts || !b->conflicts)
     return smx_set_error(SMX_E_ARG, (std::string("null ") + index_names + " / conf_off / counts / conflicts").c_str());
   if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1 || !b->order ||
                          !b->addr || !b->file || !b->ctx))
     return smx_set_error(SMX_E_ARG, "null column or result array");
-  if (!workspace || workspace_bytes < BATCH_HDR + BATCH_CLASSES * batch_list_bytes(b->n_merges))
-    return smx_set_error(SMX_E_WORKSPACE, (std::string("workspace too small (") + ws_query + ")").c_str());
+  const size_t need = batch_base_bytes(b->n_merges) + (large ? batch_large_bytes(b->n_merges, n_ops) : 0);
+  if (!workspace || workspace_bytes < need || (large && ((uintptr_t)workspace & 7)))
+    return smx_set_error(SMX_E_WORKSPACE,
+                         (std::string(large ? "workspace too small or not 8-byte aligned (" : "workspace too small (") +
+                          ws_query + ")").c_str());
   (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
   return SMX_OK;
 }
 
-// k_batch_classify, then the three classes' k_compose_batch.
+// k_batch_classify, then the three classes' k_compose_batch; with SMX_BATCH_LARGE the fourth
+// list's k_compose_batch_large after them.
 template <typename B>
-static int batch_run(const B* b, int first, void* workspace, void* stream) {
+static int batch_run(const B* b, int first, int first_large, int64_t n_ops, void* workspace, uint32_t flags,
+                     void* stream) {
   if (b->n_merges == 0) return SMX_OK;
   try {
     const int* resident;
@@ -134,37 +183,65 @@ static int batch_run(const B* b, int first, void* workspace, void* stream) {
     const size_t stride = batch_list_bytes(b->n_merges) / 4;
     u32* cnt = (u32*)workspace;
     u32* lists = (u32*)((char*)workspace + BATCH_HDR);
-    hipLaunchKernelGGL(k_batch_classify<B>, dim3(1), dim3(256), 0, st, *b, cnt, lists, stride);
+    const bool large = (flags & SMX_BATCH_LARGE) != 0;
+    const BatchLargeWs x =
+        large ? batch_large_ws((char*)workspace + batch_base_bytes(b->n_merges), b->n_merges, n_ops) : BatchLargeWs{};
+    if (large)
+      hipLaunchKernelGGL((k_batch_classify<B, true>), dim3(1), dim3(256), 0, st, *b, cnt, lists, stride, x.list);
+    else
+      hipLaunchKernelGGL((k_batch_classify<B, false>), dim3(1), dim3(256), 0, st, *b, cnt, lists, stride,
+                         (u32*)nullptr);
     HIP_TRY(hipGetLastError());
-    return launch_classes(kBatchKernels<B>, kBatchCaps, resident + first, b->n_merges, b->grid_cap, st, cnt, lists,
-                          stride, *b);
+    if (int rc = launch_classes(kBatchKernels<B>, kBatchCaps, resident + first, b->n_merges, b->grid_cap, st, cnt, lists,
+                                stride, *b))
+      return rc;
+    if (large) {
+      hipLaunchKernelGGL(k_compose_batch_large<B>, capped_grid(resident[first_large], b->n_merges, b->grid_cap),
+                         dim3(LARGE_NT), 0, st, *b, (const u32*)(cnt + BATCH_CLASSES), x);
+      HIP_TRY(hipGetLastError());
+    }
+    return SMX_OK;
   } catch (const std::exception& e) {
     return smx_set_error(SMX_E_HIP, e.what());
   }
 }
 
-extern "C" int smx_compose_batch(const smx_batch* b, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int smx_compose_batch_ex(const smx_batch* b, void* workspace, size_t workspace_bytes, uint32_t flags,
+                                    void* stream) {
+  if (flags & ~(uint32_t)SMX_BATCH_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_compose_batch_ex flag");
   if (!b) return smx_set_error(SMX_E_ARG, "null batch");
   if (b->n_merges < 0 || b->n_merges > 0x7fffffffll || b->n_total < 0 || b->n_sym < 0 || b->grid_cap < 0)
     return smx_set_error(SMX_E_ARG, "negative size");
-  if (int rc = batch_check_args(b, b->off && b->n_a, "off / n_a", workspace, workspace_bytes,
-                                "smx_compose_batch_workspace_bytes"))
+  if (int rc = batch_check_args(b, b->off && b->n_a, "off / n_a", b->n_total, workspace, workspace_bytes, flags,
+                                flags ? "smx_compose_batch_ex_workspace_bytes" : "smx_compose_batch_workspace_bytes"))
     return rc;
-  return batch_run(b, R_BATCH, workspace, stream);
+  return batch_run(b, R_BATCH, R_LARGE, b->n_total, workspace, flags, stream);
 }
 
-extern "C" int smx_compose_batch_shared(const smx_batch_shared* b, void* workspace, size_t workspace_bytes,
-                                        void* stream) {
+extern "C" int smx_compose_batch(const smx_batch* b, void* workspace, size_t workspace_bytes, void* stream) {
+  return smx_compose_batch_ex(b, workspace, workspace_bytes, 0u, stream);
+}
+
+extern "C" int smx_compose_batch_shared_ex(const smx_batch_shared* b, void* workspace, size_t workspace_bytes,
+                                           uint32_t flags, void* stream) {
+  if (flags & ~(uint32_t)SMX_BATCH_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_compose_batch_shared_ex flag");
   if (!b) return smx_set_error(SMX_E_ARG, "null batch");
   if (b->n_merges < 0 || b->n_merges > 0x7fffffffll || b->n_total < 0 || b->n_sym < 0 || b->n_shared < 0 ||
       b->grid_cap < 0)
     return smx_set_error(SMX_E_ARG, "negative size");
   if (b->n_shared > b->n_total) return smx_set_error(SMX_E_ARG, "n_shared over n_total");
   if (b->shared_is_b != 0 && b->shared_is_b != 1) return smx_set_error(SMX_E_ARG, "shared_is_b is neither 0 nor 1");
-  if (int rc = batch_check_args(b, b->off != nullptr, "off", workspace, workspace_bytes,
-                                "smx_compose_batch_shared_workspace_bytes"))
+  const int64_t n_out = b->n_total - b->n_shared + b->n_merges * b->n_shared;  // (each factor <= 2^31: no overflow)
+  if (int rc = batch_check_args(b, b->off != nullptr, "off", n_out, workspace, workspace_bytes, flags,
+                                flags ? "smx_compose_batch_shared_ex_workspace_bytes"
+                                      : "smx_compose_batch_shared_workspace_bytes"))
     return rc;
-  return batch_run(b, R_SHARED, workspace, stream);
+  return batch_run(b, R_SHARED, R_LARGE_SHARED, n_out, workspace, flags, stream);
+}
+
+extern "C" int smx_compose_batch_shared(const smx_batch_shared* b, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+  return smx_compose_batch_shared_ex(b, workspace, workspace_bytes, 0u, stream);
 }
 
 extern "C" int smx_screen_ex_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs, uint32_t flags,
