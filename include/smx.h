@@ -10,6 +10,8 @@
  *                    each, in one call (a merge queue, a rebase, a monorepo)
  *   smx_compose_batch_shared <- the same, for merges that all have one log on one side,
  *                    stored once
+ *   smx_compose_pairs <- the same, for pairs (i, j) over logs stored once, laid out as
+ *                    smx_screen takes them
  *   smx_screen    <- the conflict list of the same loop alone (what semmerge/__main__.py
  *                    looks at first), for many pairs of logs, from the logs' renames
  *   smx_rga_replay <- semmerge/crdt.py:23-57  RGA.insert/move/delete/materialize,
@@ -460,6 +462,76 @@ int smx_screen_candidates_workspace_bytes(int64_t n_logs, int64_t n_total, size_
  * with pair_cap > 0) and SMX_E_WORKSPACE (too small or not 8-byte aligned) are reported before
  * any HIP call; n_logs = 0 returns SMX_OK and launches nothing (counts is not written). */
 int smx_screen_candidates(const struct smx_candidates* c, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Batched compose of pairs of logs stored once: n_pairs merges over n_logs logs, laid out as
+ * smx_screen takes them (log_off, pair_a, pair_b), so that the pairs a screen left clean, M
+ * pull requests against K release branches or every pair of a merge train are composed without
+ * repeating a log once per pair that holds it.  Pair p composes (log pair_a[p] as A, log
+ * pair_b[p] as B).  Self pairs (i, i), (i, j) together with (j, i), the same pair listed twice
+ * and a log b stored before log a are all ordinary pairs.  Symbol and string ids form one
+ * domain for all the logs; n_sym bounds all the symbols.
+ *
+ * For every valid pair the results are exactly those of smx_compose on (log a, log b) alone:
+ *   results    counts[2p] entries of order/addr/file/ctx starting at res_off[p]; the pair's
+ *              region [res_off[p], res_off[p+1]) has room for len_a + len_b entries at least
+ *   order[]    local to the pair: A's ops are 0 .. len_a-1, B's are len_a + j (smx_screen's
+ *              indices)
+ *   conflicts  conf_off, counts[2p+1] and truncation exactly as in smx_batch: the full number
+ *              in counts[2p+1], the first conf_off[p+1] - conf_off[p] pairs written at
+ *              conflicts[2 * conf_off[p]], nothing at or past the pair's regions
+ *
+ * Checked on the device, per pair, before any column of the pair is read:
+ *   counts[2p] = counts[2p+1] = -1  pair_a[p] or pair_b[p] outside [0, n_logs); either log
+ *                                   invalid under smx_screen's log_off rules (log_off[l] < 0 or
+ *                                   below an earlier offset, log_off[l+1] < log_off[l] or
+ *                                   > n_total); res_off[p] < 0 or below an earlier res_off entry
+ *                                   (the same rule: valid pairs' regions never overlap),
+ *                                   res_off[p+1] - res_off[p] < len_a + len_b, res_off[p+1] >
+ *                                   n_out; conf_off negative or decreasing; or an op with
+ *                                   kind >= 18 or sym >= n_sym in either log, which fails
+ *                                   every pair that holds the log, and only those
+ *   counts[2p] = counts[2p+1] = -2  len_a + len_b > 2048 without SMX_BATCH_LARGE: send that
+ *                                   pair through smx_compose
+ * A failed pair writes nothing else and does not affect its neighbours.
+ *
+ * flags is 0 or SMX_BATCH_LARGE; any other bit gives SMX_E_ARG before every other check.  With
+ * SMX_BATCH_LARGE counts -2 is never reported: a pair over 2048 ops is one 1024-thread
+ * workgroup's work through global memory, as in smx_compose_batch_ex, in the workspace slice
+ * at res_off[p].
+ *
+ * Stream-ordered as smx_compose_batch: five launches with flags = 0, six with SMX_BATCH_LARGE,
+ * whatever the data; no host synchronisation, no allocation, no read-back; the call clears the
+ * workspace state it needs, so one workspace serves any sequence of calls with either flags.
+ * A device pre-pass checks the log and result offsets (a running maximum each) and sorts the
+ * pairs into smx_compose_batch's size classes.  Each pair sorts its two logs again: a log held
+ * by k pairs is loaded and ordered k times (only the copy to the device and its columns are
+ * shared).
+ */
+typedef struct smx_pairs {
+  int64_t n_logs, n_total, n_pairs, n_sym, n_out;
+  const int64_t* log_off;                 /* device [n_logs+1], as smx_screen */
+  const uint8_t* kind; const uint64_t* ts, *oid_hi, *oid_lo;
+  const uint32_t* sym; const int32_t* v0, *v1;     /* as smx_ops, n_total entries, one id domain for all logs */
+  const int32_t* pair_a, *pair_b;         /* device [n_pairs]: pair p composes (log pair_a[p] as A, log pair_b[p] as B) */
+  const int64_t* res_off;                 /* device [n_pairs+1]: pair p's results at [res_off[p], res_off[p+1]) of
+                                             the result arrays */
+  int32_t* order, *addr, *file, *ctx;     /* n_out entries */
+  int32_t* conflicts; const int64_t* conf_off;     /* as smx_batch, per pair */
+  int64_t* counts;                        /* [2*n_pairs]: composed ops, conflicts */
+  int32_t grid_cap;                       /* as smx_batch */
+} smx_pairs;
+/* Workspace (8-byte aligned) for n_logs and n_pairs in 0 .. 2^31 - 1 and these flags: 4 bytes
+ * per log and 16 per pair; with SMX_BATCH_LARGE 4 bytes per pair and 64 per entry of n_out
+ * more (n_out <= 2^31 - 1; without the flag n_out only has to be >= 0). */
+int smx_compose_pairs_workspace_bytes(int64_t n_logs, int64_t n_pairs, int64_t n_out, uint32_t flags, size_t* bytes);
+/* SMX_E_ARG (an unknown flag; then a null struct, negative sizes, n_logs or n_pairs over
+ * 2^31 - 1, grid_cap < 0, n_sym > 2^32 - 1; with SMX_BATCH_LARGE n_total or n_out over
+ * 2^31 - 1; a null log_off / pair_a / pair_b / res_off / conflicts / conf_off / counts, a null
+ * column with n_total > 0, a null result array with n_out > 0) and SMX_E_WORKSPACE (too small
+ * for these flags, or not 8-byte aligned) are reported before any HIP call; n_pairs = 0 or
+ * n_logs = 0 returns SMX_OK and launches nothing. */
+int smx_compose_pairs(const struct smx_pairs* p, void* workspace, size_t workspace_bytes, uint32_t flags, void* stream);
 
 /*
  * Sharded single merge: one process per GPU, shard r of G.

@@ -3,7 +3,7 @@ from .ops import Op, Target  # noqa: F401
 from .conflict import Conflict  # noqa: F401
 
 __all__ = ["Op", "Target", "Conflict", "compose_oplogs", "compose_many", "compose_against",
-           "screen_conflicts", "screen_all"]
+           "compose_pairs", "screen_conflicts", "screen_all"]
 
 
 def __getattr__(name):
@@ -17,6 +17,9 @@ def __getattr__(name):
     if name == "compose_against":
         from .compose import compose_against
         return compose_against
+    if name == "compose_pairs":
+        from .compose import compose_pairs
+        return compose_pairs
     if name == "screen_conflicts":
         from .compose import screen_conflicts
         return screen_conflicts

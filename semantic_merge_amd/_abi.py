@@ -127,7 +127,36 @@ class SmxCandidates(C.Structure):
     ]
 
 
-CAND_MAX_LOGS = 16384         # logs per smx_screen_candidates call (include/smx.h SMX_CAND_MAX_LOGS)
+class SmxPairs(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_int64),
+        ("n_total", C.c_int64),
+        ("n_pairs", C.c_int64),
+        ("n_sym", C.c_int64),
+        ("n_out", C.c_int64),
+        ("log_off", C.c_void_p),
+        ("kind", C.c_void_p),
+        ("ts", C.c_void_p),
+        ("oid_hi", C.c_void_p),
+        ("oid_lo", C.c_void_p),
+        ("sym", C.c_void_p),
+        ("v0", C.c_void_p),
+        ("v1", C.c_void_p),
+        ("pair_a", C.c_void_p),
+        ("pair_b", C.c_void_p),
+        ("res_off", C.c_void_p),
+        ("order", C.c_void_p),
+        ("addr", C.c_void_p),
+        ("file", C.c_void_p),
+        ("ctx", C.c_void_p),
+        ("conflicts", C.c_void_p),
+        ("conf_off", C.c_void_p),
+        ("counts", C.c_void_p),
+        ("grid_cap", C.c_int32),
+    ]
+
+
+CAND_MAX_LOGS = 16384        # logs per smx_screen_candidates call (include/smx.h SMX_CAND_MAX_LOGS)
 SCREEN_MAX_RENAMES = 2048     # renames per pair of smx_screen, both logs together (more: counts -2)
 SCREEN_CLASSES = (128, 512, 2048)  # its size classes, in renames (csrc/smx_screen.h)
 BATCH_MAX_OPS = 2048          # ops per merge of smx_compose_batch (larger: counts -2)
@@ -218,6 +247,8 @@ EXPORTS = (
     "smx_compose_batch_ex",
     "smx_compose_batch_shared_ex_workspace_bytes",
     "smx_compose_batch_shared_ex",
+    "smx_compose_pairs_workspace_bytes",
+    "smx_compose_pairs",
     "smx_screen_workspace_bytes",
     "smx_screen",
     "smx_screen_ex_workspace_bytes",
@@ -277,6 +308,12 @@ def declare(lib: C.CDLL) -> C.CDLL:
         lib.smx_compose_batch_shared_ex.argtypes = [C.POINTER(SmxBatchShared), C.c_void_p, C.c_size_t, C.c_uint32,
                                                     C.c_void_p]
         lib.smx_compose_batch_shared_ex.restype = C.c_int
+    if hasattr(lib, "smx_compose_pairs"):  # (older builds, e.g. A/B baselines, lack it)
+        lib.smx_compose_pairs_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_uint32,
+                                                          C.POINTER(C.c_size_t)]
+        lib.smx_compose_pairs_workspace_bytes.restype = C.c_int
+        lib.smx_compose_pairs.argtypes = [C.POINTER(SmxPairs), C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+        lib.smx_compose_pairs.restype = C.c_int
     if hasattr(lib, "smx_screen"):  # (older builds, e.g. A/B baselines, lack it)
         lib.smx_screen_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]
         lib.smx_screen_workspace_bytes.restype = C.c_int

@@ -156,9 +156,10 @@ def rga_replay_device(batch, device: str = "cuda", tombstones: bool = False, gro
 # (bench.py, the tests and the tools import them from _lib); resolved on first use, because
 # both modules import this one.
 _MOVED = {**dict.fromkeys(("ComposeSession", "session", "dropin_session", "compose_soa", "compose_soa_many",
-                          "compose_soa_shared", "screen_soa", "screen_all_soa"), "_session"),
-          **dict.fromkeys(("DeviceCompose", "DeviceBatch", "DeviceBatchShared", "DeviceScreen", "DeviceCandidates"),
-                          "_rigs")}
+                          "compose_soa_shared", "compose_pairs_soa", "screen_soa", "screen_all_soa"),
+                          "_session"),
+          **dict.fromkeys(("DeviceCompose", "DeviceBatch", "DeviceBatchShared", "DevicePairs", "DeviceScreen",
+                           "DeviceCandidates"), "_rigs")}
 
 
 def __getattr__(name: str):

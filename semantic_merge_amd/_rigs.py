@@ -270,6 +270,62 @@ class DeviceBatchShared(_DeviceMany):
     _start = slot
 
 
+class DevicePairs(_DeviceMany):
+    """Device-resident inputs, outputs and workspace for repeated smx_compose_pairs calls on a
+    LogsSoA and a list of (i, j) pairs (tests, tools/pairs_probe.py).  The optional arguments
+    reach the corners of the C ABI (include/smx.h smx_pairs):
+    conflict_caps per-pair capacities of the conflict pairs (default min(len_a, len_b));
+    grid_cap      smx_pairs.grid_cap;
+    log_off       the offsets passed instead of the LogsSoA's own;
+    res_off       the result offsets passed (default: len_a + len_b entries per pair, one after
+                  another; a pair with an index outside the logs gets none);
+    n_sym         the symbol bound passed instead of the LogsSoA's;
+    n_total       smx_pairs.n_total passed instead of the columns' real length;
+    n_out         smx_pairs.n_out passed instead of the result arrays' real length, res_off[-1];
+    fill          every output word (results, conflict pairs, counts) starts as this value,
+                  and CONF_GUARD such words follow the last pair's regions;
+    flags         smx_compose_pairs' flags (_abi.BATCH_LARGE: no limit on a pair's ops, no
+                  counts -2) and the workspace it asks for with them."""
+
+    def __init__(self, lsoa, pairs, device: str = "cuda", conflict_caps=None, grid_cap: int = 0, log_off=None,
+                 res_off=None, n_sym: Optional[int] = None, n_total: Optional[int] = None,
+                 n_out: Optional[int] = None, fill: Optional[int] = None, flags: int = 0) -> None:
+        self._open(device)
+        self.lsoa = lsoa
+        L = self.n_logs = lsoa.n_logs
+        self.pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+        P = self.n_pairs = len(self.pairs)
+        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
+        tot = self.n_total = int(lsoa.n_total)
+        lens = np.diff(np.asarray(lsoa.log_off, np.int64))
+        ok = ((self.pairs >= 0) & (self.pairs < L)).all(axis=1)
+        pa, pb = np.where(ok, self.pairs[:, 0], 0), np.where(ok, self.pairs[:, 1], 0)
+        self.len_a = np.where(ok, lens[pa], 0) if L else np.zeros(P, np.int64)
+        self.len_b = np.where(ok, lens[pb], 0) if L else np.zeros(P, np.int64)
+        if res_off is None:
+            res_off = np.concatenate([[0], np.cumsum(self.len_a + self.len_b, dtype=np.int64)])
+        self.res_off = np.asarray(res_off, np.int64).reshape(P + 1)
+        self.n_out = max(int(self.res_off.max()), 0) if P else 0
+        self.n_sym = int(lsoa.n_sym) if n_sym is None else n_sym
+        self._upload_cols([lsoa])
+        self._alloc(P, np.minimum(self.len_a, self.len_b) if conflict_caps is None else conflict_caps,
+                    self.n_out + self.CONF_GUARD, fill)
+        self.flags = flags
+        self._workspace(lib().smx_compose_pairs_workspace_bytes, L, P, self.n_out, flags)
+        self._idx = [self._up(self.log_off), self._up(self.pairs[:, 0]), self._up(self.pairs[:, 1]),
+                     self._up(self.res_off), self._up(self.conf_off)]
+        self._call = lambda arg, ws, nbytes, st: lib().smx_compose_pairs(arg, ws, nbytes, self.flags, st)
+        self._arg = _abi.SmxPairs(L, tot if n_total is None else n_total, P, self.n_sym,
+                                  self.n_out if n_out is None else n_out, self._idx[0].data_ptr(),
+                                  *[t.data_ptr() for t in self._in], self._idx[1].data_ptr(), self._idx[2].data_ptr(),
+                                  self._idx[3].data_ptr(), self.order.data_ptr(), self.addr.data_ptr(),
+                                  self.file.data_ptr(), self.ctx.data_ptr(), self.conf.data_ptr(),
+                                  self._idx[4].data_ptr(), self.counts.data_ptr(), grid_cap)
+
+    def _start(self, m: int) -> int:
+        return int(self.res_off[m])
+
+
 class DeviceScreen(_DeviceMany):
     """Device-resident inputs, outputs and workspace for repeated smx_screen calls on a
     LogsSoA and a list of (i, j) pairs (tests, tools/screen_probe.py).  The optional

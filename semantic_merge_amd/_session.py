@@ -269,10 +269,10 @@ class ComposeSession:
         area.copy_back(st, lay["out_bytes"])
         return t1, time.perf_counter()
 
-    def _batch_results(self, lay, conf_off, starts, labels):
+    def _batch_results(self, lay, conf_off, starts, labels, what: str = "merge"):
         """Per merge of a batch that ran: its results (views of the output staging area,
         from entry starts[m] of the four arrays), or None for a merge the library sent back
-        (counts -2).  labels[m] names merge m in an error."""
+        (counts -2).  labels[m] names merge m (`what` labels[m]) in an error."""
         hout = self.main.hout
         counts = hout[lay["counts"]: lay["counts"] + 16 * len(labels)].view(np.int64).tolist()
         q, conf, co, starts = lay["q"], lay["conf"], conf_off.tolist(), starts.tolist()
@@ -283,9 +283,9 @@ class ComposeSession:
                 res.append(None)
                 continue
             if k < 0:
-                raise SmxError(-1, f"merge {i}: invalid input: sym >= n_sym or kind >= 18")
+                raise SmxError(-1, f"{what} {i}: invalid input: sym >= n_sym or kind >= 18")
             if nc > co[m + 1] - co[m]:
-                raise SmxError(-2, f"merge {i}: {nc} conflicts exceed capacity {co[m + 1] - co[m]}")
+                raise SmxError(-2, f"{what} {i}: {nc} conflicts exceed capacity {co[m + 1] - co[m]}")
             res.append(_sliced(hout, q, starts[m], k, conf + 8 * co[m], nc))
         return res
 
@@ -467,6 +467,106 @@ class ComposeSession:
         if routed:
             # (copies: the columns may be views of the staging area that compose() packs into)
             self._compose_routed(res, routed, [ssoa.merge(m, shared_is_b) for m in routed], "merge")
+        return res
+
+    # -- batched compose of pairs of logs stored once (smx_compose_pairs) ----------------------
+
+    @staticmethod
+    def _pairs_layout(n_total: int, n_logs: int, n_pairs: int, n_out: int = 0, n_conf: int = 0):
+        """Byte offsets of a pairs batch in the staging areas: the seven input columns for
+        n_total ops (every log once), then log_off / pair_a / pair_b / res_off / conf_off; the
+        four outputs of n_out entries, the conflict pairs and the counts."""
+        q = _al(n_out * 4)
+        return {"q": q, **ComposeSession._layout(
+            n_total, [(name, n_total * dt.itemsize) for name, dt, _ in OP_COLS]
+            + [("log_off", (n_logs + 1) * 8), ("pair_a", n_pairs * 4), ("pair_b", n_pairs * 4),
+               ("res_off", (n_pairs + 1) * 8), ("conf_off", (n_pairs + 1) * 8)], q, 8 * n_conf, 16 * n_pairs)}
+
+    def staging_pairs(self, n_total: int, n_logs: int, n_pairs: int) -> dict:
+        """The seven input columns of a pairs batch of n_total ops as views of the pinned staging
+        area, laid out as compose_pairs() copies them (the columns come first, so their places
+        depend on n_total alone): a LogsSoA marshalled into them is not packed again."""
+        lay = self._pairs_layout(n_total, n_logs, n_pairs)
+        self._ensure(self.main, lay["in_bytes"], lay["out_bytes"], 0)
+        hin = self.main.hin
+        return {name: hin[lay[name]: lay[name] + n_total * dt.itemsize].view(dt) for name, dt, _ in OP_COLS}
+
+    def compose_pairs(self, lsoa, pairs, copy: bool = True, large: bool = False, large_max: Optional[int] = None):
+        """[(order, addr, file, ctx, conflict_pairs)] of the merges (log i, log j) for every
+        (i, j) of `pairs` over a LogsSoA, in input order, each as compose(lsoa.pair(i, j)) gives
+        it.  The columns, every log once, are staged as they are: one host-to-device copy (37
+        bytes per op of the logs plus the index arrays, whatever the number of pairs that hold a
+        log), one smx_compose_pairs, one copy back, one stream sync.  Pairs over BATCH_MAX_OPS
+        ops (and any the library sends back, counts -2) go through compose(lsoa.pair(i, j))
+        afterwards.  Invalid input raises SmxError naming the pair.  copy=False: views of the
+        staging area, valid until the session's next merge (taken only when no pair is routed
+        through compose()).  large=True: pairs of up to large_max ops (default LARGE_MAX) run in
+        the batch too (SMX_BATCH_LARGE) and only longer ones are routed.  `last` holds the
+        call's legs, "in_bytes", "large" (pairs over BATCH_MAX_OPS ops that ran in the batch) and
+        "routed"."""
+        t0 = time.perf_counter()
+        pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        P, L, tot = len(pairs), lsoa.n_logs, int(lsoa.n_total)
+        self.last = _last(("in_bytes", "large", "routed"))
+        if P == 0:
+            return []
+        bad = np.flatnonzero(((pairs < 0) | (pairs >= L)).any(axis=1))
+        if len(bad):
+            raise SmxError(-1, f"pair {int(bad[0])}: a log index outside [0, {L})")
+        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
+        lens = log_off[1:] - log_off[:-1]
+        if int(log_off[0]) < 0 or (lens < 0).any() or int(log_off[-1]) > tot:
+            raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
+        if tot:  # (the batch has one bound for all its symbols; entries that no log covers are no pair's)
+            over = np.flatnonzero(np.asarray(lsoa.sym) >= lsoa.n_sym)
+            held = np.zeros(L, bool)
+            held[pairs.reshape(-1)] = True
+            for at in over.tolist():
+                l = int(np.searchsorted(log_off, at, "right")) - 1
+                if 0 <= l < L and at < log_off[l + 1] and held[l]:
+                    p = int(np.flatnonzero((pairs == l).any(axis=1))[0])
+                    raise SmxError(-1, f"pair {p}: invalid input: sym >= n_sym")
+        la, lb = lens[pairs[:, 0]], lens[pairs[:, 1]]
+        flags = _abi.BATCH_LARGE if large else 0
+        limit = (self.LARGE_MAX if large_max is None else max(int(large_max), _abi.BATCH_MAX_OPS)) if large \
+            else _abi.BATCH_MAX_OPS
+        inb = np.flatnonzero(la + lb <= limit)
+        routed = np.flatnonzero(la + lb > limit).tolist()
+        res = [None] * P
+        if len(inb):
+            M = len(inb)
+            sub = np.ascontiguousarray(pairs[inb])
+            na, nb = la[inb], lb[inb]
+            res_off = np.concatenate([[0], np.cumsum(na + nb, dtype=np.int64)])
+            conf_off = np.concatenate([[0], np.cumsum(np.minimum(na, nb), dtype=np.int64)])  # (never truncates)
+            n_out = int(res_off[-1])
+            lay = self._pairs_layout(tot, L, M, n_out, int(conf_off[-1]))
+            q = lay["q"]
+            t1, t2 = self._staged_call(
+                self.main, lib().smx_compose_pairs_workspace_bytes, (L, M, n_out, flags), lay,
+                [(getattr(lsoa, name), lay[name], tot * dt.itemsize) for name, dt, _ in OP_COLS],
+                (("log_off", log_off), ("pair_a", np.ascontiguousarray(sub[:, 0])),
+                 ("pair_b", np.ascontiguousarray(sub[:, 1])), ("res_off", res_off), ("conf_off", conf_off)),
+                lambda d0, o0: _abi.SmxPairs(L, tot, M, int(lsoa.n_sym), n_out, d0 + lay["log_off"],
+                                             *[d0 + lay[name] for name, _, _ in OP_COLS],
+                                             d0 + lay["pair_a"], d0 + lay["pair_b"], d0 + lay["res_off"],
+                                             o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"],
+                                             d0 + lay["conf_off"], o0 + lay["counts"], 0),
+                lambda arg, ws, nbytes, st: lib().smx_compose_pairs(arg, ws, nbytes, flags, st))
+            for p, r in zip(inb.tolist(), self._batch_results(lay, conf_off, res_off[:-1], inb.tolist(), "pair")):
+                res[p] = r
+                if r is None:
+                    routed.append(p)
+            if copy or routed:  # (compose() below reuses the staging area)
+                res = [r if r is None else tuple(x.copy() for x in r) for r in res]
+            self.last = _last(pack_s=t1 - t0, device_s=t2 - t1, unpack_s=time.perf_counter() - t2,
+                              in_bytes=lay["in_bytes"],
+                              large=int((na + nb > _abi.BATCH_MAX_OPS).sum()) if large else 0)
+        routed.sort()
+        self.last["routed"] = len(routed)
+        if routed:
+            # (copies: the columns may be views of the staging area that compose() packs into)
+            self._compose_routed(res, routed, [lsoa.pair(int(pairs[p, 0]), int(pairs[p, 1])) for p in routed], "pair")
         return res
 
     # -- conflict screen (smx_screen): many pairs of logs stored once, conflicts only ---------
@@ -711,6 +811,11 @@ def compose_soa_shared(ssoa, shared_is_b: bool = False, device: str = "cuda", la
                        large_max: Optional[int] = None):
     """ComposeSession.compose_shared on the thread's free session: a SharedSoA's merges in one batch."""
     return _free_session(device).compose_shared(ssoa, shared_is_b, large=large, large_max=large_max)
+
+
+def compose_pairs_soa(lsoa, pairs, device: str = "cuda", large: bool = False, large_max: Optional[int] = None):
+    """ComposeSession.compose_pairs on the thread's free session: the (i, j) of `pairs` over a LogsSoA in one batch."""
+    return _free_session(device).compose_pairs(lsoa, pairs, large=large, large_max=large_max)
 
 
 def screen_soa(lsoa, pairs, device: str = "cuda", large: bool = False):

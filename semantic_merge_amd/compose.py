@@ -101,6 +101,41 @@ def compose_against(shared: Sequence[Any], branches: Sequence[Sequence[Any]],
     return res
 
 
+def compose_pairs(logs: Sequence[Sequence[Any]], pairs: Optional[Sequence[Tuple[int, int]]] = None,
+                  large: bool = False) -> List[Tuple[List[Any], List[Any]]]:
+    """``[compose_oplogs(logs[i], logs[j]) for i, j in pairs]`` for pairs over logs given once:
+    the clean pairs that ``screen_all`` left over, M pull requests against K release branches,
+    every pair of a merge train.  ``pairs=None``: all ``i < j``.  Every log is marshalled and
+    copied to the GPU once, whatever the number of pairs that hold it, and the pairs of at most
+    2048 ops run as one batch (one copy in, one smx_compose_pairs, one copy back, one sync);
+    larger pairs follow one by one.  ``large=True``: pairs of up to ``ComposeSession.LARGE_MAX``
+    ops run in the batch too (SMX_BATCH_LARGE).  A pair outside the logs raises ``IndexError``.
+    Inputs are never mutated."""
+    ops = [list(x) for x in logs]
+    if pairs is None:
+        pairs = [(i, j) for i in range(len(ops)) for j in range(i + 1, len(ops))]
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    for i, j in pairs:
+        if not (0 <= i < len(ops) and 0 <= j < len(ops)):
+            raise IndexError(f"pair ({i}, {j}) outside the {len(ops)} logs")
+    if not pairs:
+        return []
+    res: List[Tuple[List[Any], List[Any]]] = []
+    with dropin_session() as sess:
+        # marshalled straight into the session's pinned staging columns; the results are
+        # views of its staging area too, materialised while the session is held
+        lsoa = marshal_logs(ops, sess.staging_pairs(sum(len(x) for x in ops), len(ops), len(pairs)))
+        kind = lsoa.kind.copy()  # (a pair routed through compose() reuses the staging columns)
+        off = lsoa.log_off.tolist()
+        for (i, j), (order, addr, file, ctx, cpairs) in zip(pairs, sess.compose_pairs(lsoa, pairs, copy=False,
+                                                                                      large=large)):
+            both = ops[i] + ops[j]
+            k = np.concatenate([kind[off[i]: off[i + 1]], kind[off[j]: off[j + 1]]])
+            res.append((materialize_ops_native(both, k, lsoa.strings, order, addr, file, ctx),
+                        materialize_conflicts(both, cpairs)))
+    return res
+
+
 def screen_conflicts(logs: Sequence[Sequence[Any]],
                      pairs: Optional[Sequence[Tuple[int, int]]] = None, large: bool = False) -> List[List[Any]]:
     """``[compose_oplogs(logs[i], logs[j])[1] for i, j in pairs]`` -- the DivergentRename

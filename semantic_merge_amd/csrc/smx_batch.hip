@@ -1,6 +1,6 @@
 // smx_batch.hip — the batched entry points of include/smx.h: smx_compose_batch and
-// smx_compose_batch_shared with their _ex forms (kernels in smx_batch.h and smx_batch_large.h,
-// DESIGN.md §11-12 and §16) and smx_screen /
+// smx_compose_batch_shared with their _ex forms and smx_compose_pairs (kernels in smx_batch.h
+// and smx_batch_large.h) and smx_screen /
 // smx_screen_ex (kernels in smx_screen.h), and smx_screen_candidates (kernels in smx_cand.h,
 // DESIGN.md §14), which has a shape of its own: a sort and a bit matrix, no size classes.
 //
@@ -27,7 +27,9 @@ enum {
   R_STREAM = 11,
   R_LARGE = 12,
   R_LARGE_SHARED = 13,
-  R_N = 14
+  R_PAIRS = 14,
+  R_LARGE_PAIRS = 17,
+  R_N = 18
 };
 template <typename B>
 using BatchKernel = void (*)(B, const u32*, const u32*);
@@ -59,7 +61,8 @@ static int resident_of(const int** out) {
     for (int c = 0; c < BATCH_CLASSES; ++c) {
       fn[R_BATCH + c] = (const void*)kBatchKernels<smx_batch>[c];
       fn[R_SHARED + c] = (const void*)kBatchKernels<smx_batch_shared>[c];
-      threads[R_BATCH + c] = threads[R_SHARED + c] = kBatchCaps[c] / 2;
+      fn[R_PAIRS + c] = (const void*)kBatchKernels<smx_pairs>[c];
+      threads[R_BATCH + c] = threads[R_SHARED + c] = threads[R_PAIRS + c] = kBatchCaps[c] / 2;
     }
     fn[R_EXTRACT] = (const void*)k_screen_extract;
     threads[R_EXTRACT] = SCREEN_T1;
@@ -73,7 +76,8 @@ static int resident_of(const int** out) {
     threads[R_STREAM] = SCREEN_N / 2;
     fn[R_LARGE] = (const void*)k_compose_batch_large<smx_batch>;
     fn[R_LARGE_SHARED] = (const void*)k_compose_batch_large<smx_batch_shared>;
-    threads[R_LARGE] = threads[R_LARGE_SHARED] = LARGE_NT;
+    fn[R_LARGE_PAIRS] = (const void*)k_compose_batch_large<smx_pairs>;
+    threads[R_LARGE] = threads[R_LARGE_SHARED] = threads[R_LARGE_PAIRS] = LARGE_NT;
     int cus = 0;
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     for (int k = 0; k < R_N; ++k) {
@@ -242,6 +246,84 @@ extern "C" int smx_compose_batch_shared_ex(const smx_batch_shared* b, void* work
 extern "C" int smx_compose_batch_shared(const smx_batch_shared* b, void* workspace, size_t workspace_bytes,
                                         void* stream) {
   return smx_compose_batch_shared_ex(b, workspace, workspace_bytes, 0u, stream);
+}
+
+// The pairs form's workspace: the class counts, linfo and rinfo, the three class lists; with
+// SMX_BATCH_LARGE the fourth list and the slices, n_out entries long.
+static size_t pairs_base_bytes(int64_t n_logs, int64_t n_pairs) {
+  return BATCH_HDR + pairs_info_bytes(n_logs, n_pairs) + BATCH_CLASSES * batch_list_bytes(n_pairs);
+}
+
+extern "C" int smx_compose_pairs_workspace_bytes(int64_t n_logs, int64_t n_pairs, int64_t n_out, uint32_t flags,
+                                                 size_t* bytes) {
+  if (flags & ~(uint32_t)SMX_BATCH_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_compose_pairs flag");
+  if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
+  if (n_logs < 0 || n_logs > 0x7fffffffll || n_pairs < 0 || n_pairs > 0x7fffffffll || n_out < 0)
+    return smx_set_error(SMX_E_ARG, "n_logs or n_pairs outside 0 .. 2^31 - 1, or n_out negative");
+  const bool large = (flags & SMX_BATCH_LARGE) != 0;
+  if (large && n_out > 0x7fffffffll) return smx_set_error(SMX_E_ARG, "SMX_BATCH_LARGE: n_out over 2^31 - 1");
+  *bytes = pairs_base_bytes(n_logs, n_pairs) + (large ? batch_large_bytes(n_pairs, n_out) : 0);
+  return SMX_OK;
+}
+
+// k_pairs_offsets and k_pairs_classify, then the three classes' k_compose_batch; with
+// SMX_BATCH_LARGE the fourth list's k_compose_batch_large after them.
+extern "C" int smx_compose_pairs(const struct smx_pairs* b, void* workspace, size_t workspace_bytes, uint32_t flags,
+                                 void* stream) {
+  if (flags & ~(uint32_t)SMX_BATCH_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_compose_pairs flag");
+  const bool large = (flags & SMX_BATCH_LARGE) != 0;
+  if (!b) return smx_set_error(SMX_E_ARG, "null pairs");
+  if (b->n_logs < 0 || b->n_logs > 0x7fffffffll || b->n_pairs < 0 || b->n_pairs > 0x7fffffffll || b->n_total < 0 ||
+      b->n_sym < 0 || b->n_out < 0 || b->grid_cap < 0)
+    return smx_set_error(SMX_E_ARG, "negative size");
+  if (b->n_sym > 0xffffffffll) return smx_set_error(SMX_E_ARG, "n_sym over 2^32 - 1");
+  if (large && (b->n_total > 0x7fffffffll || b->n_out > 0x7fffffffll))
+    return smx_set_error(SMX_E_ARG, "SMX_BATCH_LARGE: n_total or n_out over 2^31 - 1");
+  if (b->n_pairs == 0 || b->n_logs == 0) return SMX_OK;
+  if (!b->log_off || !b->pair_a || !b->pair_b || !b->res_off || !b->conf_off || !b->counts || !b->conflicts)
+    return smx_set_error(SMX_E_ARG, "null log_off / pair_a / pair_b / res_off / conf_off / counts / conflicts");
+  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1))
+    return smx_set_error(SMX_E_ARG, "null column");
+  if (b->n_out > 0 && (!b->order || !b->addr || !b->file || !b->ctx))
+    return smx_set_error(SMX_E_ARG, "null result array");
+  const size_t base = pairs_base_bytes(b->n_logs, b->n_pairs);
+  const size_t need = base + (large ? batch_large_bytes(b->n_pairs, b->n_out) : 0);
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < need)
+    return smx_set_error(SMX_E_WORKSPACE,
+                         "workspace too small or not 8-byte aligned (smx_compose_pairs_workspace_bytes)");
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  try {
+    const int* resident;
+    if (int rc = resident_of(&resident)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t stride = batch_list_bytes(b->n_pairs) / 4;
+    u32* cnt = (u32*)workspace;
+    i32* linfo = (i32*)((char*)workspace + BATCH_HDR);
+    i32* rinfo = (i32*)((char*)linfo + batch_list_bytes(b->n_logs));
+    u32* lists = (u32*)((char*)workspace + BATCH_HDR + pairs_info_bytes(b->n_logs, b->n_pairs));
+    const BatchLargeWs x = large ? batch_large_ws((char*)workspace + base, b->n_pairs, b->n_out) : BatchLargeWs{};
+    const dim3 classify_grid((unsigned)SMX_CEIL_DIV(b->n_pairs, (i64)BATCH_CHUNK));
+    hipLaunchKernelGGL(k_pairs_offsets, dim3(1), dim3(1024), 0, st, *b, cnt, linfo, rinfo);
+    HIP_TRY(hipGetLastError());
+    if (large)
+      hipLaunchKernelGGL(k_pairs_classify<true>, classify_grid, dim3(256), 0, st, *b, cnt, (const i32*)linfo,
+                         (const i32*)rinfo, lists, stride, x.list);
+    else
+      hipLaunchKernelGGL(k_pairs_classify<false>, classify_grid, dim3(256), 0, st, *b, cnt, (const i32*)linfo,
+                         (const i32*)rinfo, lists, stride, (u32*)nullptr);
+    HIP_TRY(hipGetLastError());
+    if (int rc = launch_classes(kBatchKernels<smx_pairs>, kBatchCaps, resident + R_PAIRS, b->n_pairs, b->grid_cap, st,
+                                cnt, lists, stride, *b))
+      return rc;
+    if (large) {
+      hipLaunchKernelGGL(k_compose_batch_large<smx_pairs>, capped_grid(resident[R_LARGE_PAIRS], b->n_pairs, b->grid_cap),
+                         dim3(LARGE_NT), 0, st, *b, (const u32*)(cnt + BATCH_CLASSES), x);
+      HIP_TRY(hipGetLastError());
+    }
+    return SMX_OK;
+  } catch (const std::exception& e) {
+    return smx_set_error(SMX_E_HIP, e.what());
+  }
 }
 
 extern "C" int smx_screen_ex_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs, uint32_t flags,

@@ -89,6 +89,7 @@ static inline BatchLargeWs batch_large_ws(void* at, int64_t n_merges, int64_t n_
 // Where merge m's slice of the workspace starts: where its results do.
 __device__ __forceinline__ i64 batch_slice(const smx_batch& b, i64 m) { return b.off[m]; }
 __device__ __forceinline__ i64 batch_slice(const smx_batch_shared& b, i64 m) { return b.off[m] + (m - 1) * b.n_shared; }
+__device__ __forceinline__ i64 batch_slice(const smx_pairs& b, i64 m) { return b.res_off[m]; }
 
 // The LDS of the sort's tiles and of the walk's rounds, one after the other.
 struct LargeSortLds {
