@@ -302,6 +302,44 @@ class ComposeSession:
         if keep_last:
             self.last = last
 
+    # (the three batched composes share four more: the limit, the layout, the struct's end, the results' way)
+    def _limit(self, large: bool, large_max: Optional[int]) -> int:
+        """The most ops of a merge that runs in the batch (large_max: default LARGE_MAX, at least BATCH_MAX_OPS)."""
+        if not large:
+            return _abi.BATCH_MAX_OPS
+        return self.LARGE_MAX if large_max is None else max(int(large_max), _abi.BATCH_MAX_OPS)
+
+    @staticmethod
+    def _compose_layout(n_total: int, index, n_out: int, conf_bytes: int, n_items: int) -> dict:
+        """Byte offsets of a batched compose: the seven columns for n_total ops, then the index arrays ((name,
+        nbytes)); the four outputs of n_out entries (q bytes each), the conflict pairs, n_items pairs of counts."""
+        q = _al(n_out * 4)
+        return {"q": q, **ComposeSession._layout(
+            n_total, [(name, n_total * dt.itemsize) for name, dt, _ in OP_COLS] + index, q, conf_bytes, 16 * n_items)}
+
+    def _columns(self, lay, n_total: int, cols=OP_COLS) -> dict:
+        """The columns `cols` of n_total ops as views of the pinned staging area, at their places in `lay`."""
+        self._ensure(self.main, lay["in_bytes"], lay["out_bytes"], 0)
+        hin = self.main.hin
+        return {name: hin[lay[name]: lay[name] + n_total * dt.itemsize].view(dt) for name, dt, _ in cols}
+
+    @staticmethod
+    def _out_fields(lay, d0: int, o0: int):
+        """The struct fields behind every form's inputs: the four results, conflicts, conf_off and counts."""
+        q = lay["q"]
+        return o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"], d0 + lay["conf_off"], o0 + lay["counts"]
+
+    @staticmethod
+    def _take(res, routed, labels, results, copy: bool) -> None:
+        """results[m] into res[labels[m]], the items sent back (None) onto `routed`; copies unless
+        copy is False and nothing is routed (compose() of a routed item reuses the staging area)."""
+        for i, r in zip(labels, results):
+            res[i] = r
+            if r is None:
+                routed.append(i)
+        if copy or routed:
+            res[:] = [r if r is None else tuple(x.copy() for x in r) for r in res]
+
     # -- batched compose (smx_compose_batch): many small merges, one launch sequence --------
 
     @staticmethod
@@ -310,10 +348,8 @@ class ComposeSession:
         columns for sum(ns) ops, then off / n_a / conf_off; the four outputs, the conflict
         pairs (at most sum(ns) / 2) and the counts."""
         m, tot = len(ns), int(sum(ns))
-        q = _al(tot * 4)
-        return {"q": q, **ComposeSession._layout(
-            tot, [(name, tot * dt.itemsize) for name, dt, _ in OP_COLS]
-            + [("off", (m + 1) * 8), ("n_a", m * 8), ("conf_off", (m + 1) * 8)], q, 4 * tot, 16 * m)}
+        return ComposeSession._compose_layout(tot, [("off", (m + 1) * 8), ("n_a", m * 8), ("conf_off", (m + 1) * 8)],
+                                              tot, 4 * tot, m)
 
     def staging_many(self, ns):
         """The input columns of a batch of merges of ns ops (each at most BATCH_MAX_OPS, or with
@@ -341,8 +377,7 @@ class ComposeSession:
         t0 = time.perf_counter()
         soas = list(soas)
         flags = _abi.BATCH_LARGE if large else 0
-        limit = (self.LARGE_MAX if large_max is None else max(int(large_max), _abi.BATCH_MAX_OPS)) if large \
-            else _abi.BATCH_MAX_OPS
+        limit = self._limit(large, large_max)
         small = [i for i, s in enumerate(soas) if s.n <= limit]
         routed = [i for i, s in enumerate(soas) if s.n > limit]
         res = [None] * len(soas)
@@ -363,21 +398,14 @@ class ComposeSession:
                     raise SmxError(-1, f"merge {i}: invalid input: sym >= n_sym")
                 cols += [(getattr(soa, name), lay[name] + int(off[m]) * dt.itemsize, n * dt.itemsize)
                          for name, dt, _ in OP_COLS]
-            q = lay["q"]
             t1, t2 = self._staged_call(
                 self.main, lib().smx_compose_batch_ex_workspace_bytes, (M, lay["n_total"], flags), lay, cols,
                 (("off", off), ("n_a", n_a), ("conf_off", conf_off)),
                 lambda d0, o0: _abi.SmxBatch(M, lay["n_total"], n_sym, d0 + lay["off"], d0 + lay["n_a"],
                                              *[d0 + lay[name] for name, _, _ in OP_COLS],
-                                             o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"],
-                                             d0 + lay["conf_off"], o0 + lay["counts"], 0),
+                                             *self._out_fields(lay, d0, o0), 0),
                 lambda arg, ws, nbytes, st: lib().smx_compose_batch_ex(arg, ws, nbytes, flags, st))
-            for i, r in zip(small, self._batch_results(lay, conf_off, off[:-1], small)):
-                res[i] = r
-                if r is None:
-                    routed.append(i)
-            if copy or routed:  # (compose() below reuses the staging area)
-                res = [r if r is None else tuple(x.copy() for x in r) for r in res]
+            self._take(res, routed, small, self._batch_results(lay, conf_off, off[:-1], small), copy)
             legs = _last(pack_s=t1 - t0, device_s=t2 - t1, unpack_s=time.perf_counter() - t2,
                          large=sum(n > _abi.BATCH_MAX_OPS for n in ns) if large else 0)
         routed.sort()
@@ -394,19 +422,14 @@ class ComposeSession:
         n_total ops (the shared log once), then off / conf_off; the four outputs of
         n_total - n_shared + m * n_shared entries, the conflict pairs (at most
         n_total - n_shared) and the counts."""
-        q = _al((n_total - n_shared + m * n_shared) * 4)
-        return {"q": q, **ComposeSession._layout(
-            n_total, [(name, n_total * dt.itemsize) for name, dt, _ in OP_COLS]
-            + [("off", (m + 1) * 8), ("conf_off", (m + 1) * 8)], q, 8 * (n_total - n_shared), 16 * m)}
+        return ComposeSession._compose_layout(n_total, [("off", (m + 1) * 8), ("conf_off", (m + 1) * 8)],
+                                              n_total - n_shared + m * n_shared, 8 * (n_total - n_shared), m)
 
     def staging_shared(self, n_total: int, n_shared: int, n_merges: int) -> dict:
         """The input columns of a shared-log batch of n_total ops (of any size) as views of the
         pinned staging area, laid out as compose_shared() copies them: a SharedSoA marshalled
         into them is not packed again."""
-        lay = self._shared_layout(n_total, n_shared, n_merges)
-        self._ensure(self.main, lay["in_bytes"], lay["out_bytes"], 0)
-        hin = self.main.hin
-        return {name: hin[lay[name]: lay[name] + n_total * dt.itemsize].view(dt) for name, dt, _ in OP_COLS}
+        return self._columns(self._shared_layout(n_total, n_shared, n_merges), n_total)
 
     def compose_shared(self, ssoa, shared_is_b: bool = False, copy: bool = True, large: bool = False,
                        large_max: Optional[int] = None):
@@ -438,26 +461,22 @@ class ComposeSession:
                 raise SmxError(-1, f"merge {int(np.searchsorted(off, at, 'right')) - 1}: invalid input: sym >= n_sym")
         res = [None] * M
         self.last = _last(("in_bytes",) + (("large", "routed") if large else ()))
-        limit = self.LARGE_MAX if large_max is None else max(int(large_max), _abi.BATCH_MAX_OPS)
-        flags = _abi.BATCH_LARGE if large and M and bool((S + lens <= limit).all()) else 0
+        flags = _abi.BATCH_LARGE if large and M and bool((S + lens <= self._limit(large, large_max)).all()) else 0
         n_large = int((S + lens > _abi.BATCH_MAX_OPS).sum()) if flags else 0
         if M and (flags or (S + lens <= _abi.BATCH_MAX_OPS).any()):
             lay = self._shared_layout(tot, S, M)
             conf_off = np.concatenate([[0], np.cumsum(np.minimum(lens, S), dtype=np.int64)])  # (never truncates)
-            q = lay["q"]
+            routed = []
             t1, t2 = self._staged_call(
                 self.main, lib().smx_compose_batch_shared_ex_workspace_bytes, (M, tot, S, flags), lay,
                 [(getattr(ssoa, name), lay[name], tot * dt.itemsize) for name, dt, _ in OP_COLS],
                 (("off", off), ("conf_off", conf_off)),
                 lambda d0, o0: _abi.SmxBatchShared(M, tot, int(ssoa.n_sym), S, d0 + lay["off"],
                                                    *[d0 + lay[name] for name, _, _ in OP_COLS],
-                                                   o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"],
-                                                   d0 + lay["conf_off"], o0 + lay["counts"], 0, int(bool(shared_is_b))),
+                                                   *self._out_fields(lay, d0, o0), 0, int(bool(shared_is_b))),
                 lambda arg, ws, nbytes, st: lib().smx_compose_batch_shared_ex(arg, ws, nbytes, flags, st))
-            res = self._batch_results(lay, conf_off, off[:-1] + (np.arange(M) - 1) * S, range(M))
-            routed = [m for m in range(M) if res[m] is None]
-            if copy or routed:  # (compose() below reuses the staging area)
-                res = [r if r is None else tuple(x.copy() for x in r) for r in res]
+            self._take(res, routed, range(M),
+                       self._batch_results(lay, conf_off, off[:-1] + (np.arange(M) - 1) * S, range(M)), copy)
             self.last = _last(pack_s=t1 - t0, device_s=t2 - t1, unpack_s=time.perf_counter() - t2,
                               in_bytes=lay["in_bytes"])
         else:
@@ -476,20 +495,15 @@ class ComposeSession:
         """Byte offsets of a pairs batch in the staging areas: the seven input columns for
         n_total ops (every log once), then log_off / pair_a / pair_b / res_off / conf_off; the
         four outputs of n_out entries, the conflict pairs and the counts."""
-        q = _al(n_out * 4)
-        return {"q": q, **ComposeSession._layout(
-            n_total, [(name, n_total * dt.itemsize) for name, dt, _ in OP_COLS]
-            + [("log_off", (n_logs + 1) * 8), ("pair_a", n_pairs * 4), ("pair_b", n_pairs * 4),
-               ("res_off", (n_pairs + 1) * 8), ("conf_off", (n_pairs + 1) * 8)], q, 8 * n_conf, 16 * n_pairs)}
+        return ComposeSession._compose_layout(
+            n_total, [("log_off", (n_logs + 1) * 8), ("pair_a", n_pairs * 4), ("pair_b", n_pairs * 4),
+                      ("res_off", (n_pairs + 1) * 8), ("conf_off", (n_pairs + 1) * 8)], n_out, 8 * n_conf, n_pairs)
 
     def staging_pairs(self, n_total: int, n_logs: int, n_pairs: int) -> dict:
         """The seven input columns of a pairs batch of n_total ops as views of the pinned staging
         area, laid out as compose_pairs() copies them (the columns come first, so their places
         depend on n_total alone): a LogsSoA marshalled into them is not packed again."""
-        lay = self._pairs_layout(n_total, n_logs, n_pairs)
-        self._ensure(self.main, lay["in_bytes"], lay["out_bytes"], 0)
-        hin = self.main.hin
-        return {name: hin[lay[name]: lay[name] + n_total * dt.itemsize].view(dt) for name, dt, _ in OP_COLS}
+        return self._columns(self._pairs_layout(n_total, n_logs, n_pairs), n_total)
 
     def compose_pairs(self, lsoa, pairs, copy: bool = True, large: bool = False, large_max: Optional[int] = None):
         """[(order, addr, file, ctx, conflict_pairs)] of the merges (log i, log j) for every
@@ -528,8 +542,7 @@ class ComposeSession:
                     raise SmxError(-1, f"pair {p}: invalid input: sym >= n_sym")
         la, lb = lens[pairs[:, 0]], lens[pairs[:, 1]]
         flags = _abi.BATCH_LARGE if large else 0
-        limit = (self.LARGE_MAX if large_max is None else max(int(large_max), _abi.BATCH_MAX_OPS)) if large \
-            else _abi.BATCH_MAX_OPS
+        limit = self._limit(large, large_max)
         inb = np.flatnonzero(la + lb <= limit)
         routed = np.flatnonzero(la + lb > limit).tolist()
         res = [None] * P
@@ -541,7 +554,6 @@ class ComposeSession:
             conf_off = np.concatenate([[0], np.cumsum(np.minimum(na, nb), dtype=np.int64)])  # (never truncates)
             n_out = int(res_off[-1])
             lay = self._pairs_layout(tot, L, M, n_out, int(conf_off[-1]))
-            q = lay["q"]
             t1, t2 = self._staged_call(
                 self.main, lib().smx_compose_pairs_workspace_bytes, (L, M, n_out, flags), lay,
                 [(getattr(lsoa, name), lay[name], tot * dt.itemsize) for name, dt, _ in OP_COLS],
@@ -550,15 +562,10 @@ class ComposeSession:
                 lambda d0, o0: _abi.SmxPairs(L, tot, M, int(lsoa.n_sym), n_out, d0 + lay["log_off"],
                                              *[d0 + lay[name] for name, _, _ in OP_COLS],
                                              d0 + lay["pair_a"], d0 + lay["pair_b"], d0 + lay["res_off"],
-                                             o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"],
-                                             d0 + lay["conf_off"], o0 + lay["counts"], 0),
+                                             *self._out_fields(lay, d0, o0), 0),
                 lambda arg, ws, nbytes, st: lib().smx_compose_pairs(arg, ws, nbytes, flags, st))
-            for p, r in zip(inb.tolist(), self._batch_results(lay, conf_off, res_off[:-1], inb.tolist(), "pair")):
-                res[p] = r
-                if r is None:
-                    routed.append(p)
-            if copy or routed:  # (compose() below reuses the staging area)
-                res = [r if r is None else tuple(x.copy() for x in r) for r in res]
+            self._take(res, routed, inb.tolist(),
+                       self._batch_results(lay, conf_off, res_off[:-1], inb.tolist(), "pair"), copy)
             self.last = _last(pack_s=t1 - t0, device_s=t2 - t1, unpack_s=time.perf_counter() - t2,
                               in_bytes=lay["in_bytes"],
                               large=int((na + nb > _abi.BATCH_MAX_OPS).sum()) if large else 0)
@@ -587,10 +594,7 @@ class ComposeSession:
         laid out as screen() copies them (plus a v1 column of its own, which the marshaller
         fills and the screen does not read): a LogsSoA marshalled into them is not packed
         again."""
-        lay = self._screen_layout(n_total, n_logs, n_pairs)
-        self._ensure(self.main, lay["in_bytes"], lay["out_bytes"], 0)
-        hin = self.main.hin
-        cols = {name: hin[lay[name]: lay[name] + n_total * dt.itemsize].view(dt) for name, dt, _ in SCREEN_COLS}
+        cols = self._columns(self._screen_layout(n_total, n_logs, n_pairs), n_total, SCREEN_COLS)
         cols["v1"] = np.empty(n_total, np.int32)
         return cols
 

@@ -7,7 +7,10 @@
 // All three have one shape: a pre-pass sorts the items (merges, pairs) into three size
 // classes, then one kernel per class runs its list on a grid capped by what the device
 // holds at once.  That shape is here once: the residency cache (resident_of) and the
-// per-class launch (launch_classes).  Nothing here waits, allocates or reads back.
+// per-class launch (launch_classes).  The three compose batches go further: they have one
+// size function, one argument check and one runner (batch_ws_size, batch_check_args, batch_run)
+// over a description of each form (batch_form, batch_prepass).  Nothing here waits, allocates
+// or reads back.
 #include <exception>
 
 // (the small kernel's phase stamps belong to the single merge: smx_compose.hip defines the
@@ -111,24 +114,94 @@ static int launch_classes(K* const (&kern)[3], const int (&cap)[3], const int* r
   return SMX_OK;
 }
 
-// The unflagged workspace: the class counts and the three class lists.
-static size_t batch_base_bytes(int64_t n_merges) { return BATCH_HDR + BATCH_CLASSES * batch_list_bytes(n_merges); }
+// The three compose batches' workspace: the class counts, `info` bytes of the form's own, the
+// three class lists (base); with SMX_BATCH_LARGE the fourth list and the slices, n_ops result
+// entries long, behind them (total).
+struct BatchWsSize { size_t base, total; };
+static BatchWsSize batch_ws_size(size_t info, int64_t n_items, int64_t n_ops, bool large) {
+  const size_t base = BATCH_HDR + info + BATCH_CLASSES * batch_list_bytes(n_items);
+  return {base, base + (large ? batch_large_bytes(n_items, n_ops) : 0)};
+}
 
-// Both workspace queries: n_ops result entries (n_total, or the shared form's n_out).
+// What the host has to know of a form beside batch_check and batch_merge (smx_batch.h); the
+// sizes every form has (its items, n_total, n_sym, grid_cap) are checked in batch_check_args.
+struct BatchForm {
+  const char* plain_query;          // the size query of its unflagged call, for messages
+  int first, first_large;           // its rows of resident_of: the three class kernels', the large kernel's
+  bool aligned = false;             // the workspace is 8-byte aligned whatever the flags
+  const char* own_error = nullptr;  // what the checks only this struct has object to
+  int64_t items, n_ops;             // its merges or pairs; its result entries
+  bool empty;                       // nothing to do, whatever else the struct holds
+  size_t info = 0;                  // workspace bytes between BATCH_HDR and the class lists
+  const char* index_names;          // its own index arrays, and whether all of them are set
+  bool index_ok;
+};
+static BatchForm batch_form(const smx_batch& b) {
+  BatchForm f;
+  f.plain_query = "smx_compose_batch_workspace_bytes", f.first = R_BATCH, f.first_large = R_LARGE;
+  f.items = b.n_merges, f.n_ops = b.n_total, f.empty = b.n_merges == 0;
+  f.index_names = "off / n_a", f.index_ok = b.off && b.n_a;
+  return f;
+}
+static BatchForm batch_form(const smx_batch_shared& b) {
+  BatchForm f;
+  f.plain_query = "smx_compose_batch_shared_workspace_bytes", f.first = R_SHARED, f.first_large = R_LARGE_SHARED;
+  f.own_error = b.n_shared < 0 ? "negative size" : b.n_shared > b.n_total ? "n_shared over n_total" : nullptr;
+  if (!f.own_error && b.shared_is_b != 0 && b.shared_is_b != 1) f.own_error = "shared_is_b is neither 0 nor 1";
+  // (past the checks each factor is <= 2^31: no overflow; before them the value is not used)
+  f.n_ops = (int64_t)((uint64_t)b.n_total - (uint64_t)b.n_shared + (uint64_t)b.n_merges * (uint64_t)b.n_shared);
+  f.items = b.n_merges, f.empty = b.n_merges == 0, f.index_names = "off", f.index_ok = b.off != nullptr;
+  return f;
+}
+static BatchForm batch_form(const smx_pairs& b) {
+  BatchForm f;
+  f.plain_query = "smx_compose_pairs_workspace_bytes", f.first = R_PAIRS, f.first_large = R_LARGE_PAIRS;
+  f.aligned = true, f.info = pairs_info_bytes(b.n_logs, b.n_pairs);
+  if (b.n_logs < 0 || b.n_logs > 0x7fffffffll || b.n_out < 0) f.own_error = "negative size";
+  f.items = b.n_pairs, f.n_ops = b.n_out, f.empty = b.n_pairs == 0 || b.n_logs == 0;
+  f.index_names = "log_off / pair_a / pair_b / res_off", f.index_ok = b.log_off && b.pair_a && b.pair_b && b.res_off;
+  return f;
+}
+
+// The launches that fill the class counts and lists (with `large` also large_list, else null)
+// from the workspace's `info` region: k_batch_classify, or the pairs form's two kernels.
+template <typename B>
+static int batch_prepass(const B& b, u32* cnt, char*, u32* lists, size_t stride, u32* large_list, bool large,
+                         hipStream_t st) {
+  auto* classify = large ? k_batch_classify<B, true> : k_batch_classify<B, false>;
+  hipLaunchKernelGGL(classify, dim3(1), dim3(256), 0, st, b, cnt, lists, stride, large_list);
+  HIP_TRY(hipGetLastError());
+  return SMX_OK;
+}
+static int batch_prepass(const smx_pairs& b, u32* cnt, char* info, u32* lists, size_t stride, u32* large_list,
+                         bool large, hipStream_t st) {
+  i32* linfo = (i32*)info;
+  i32* rinfo = (i32*)(info + batch_list_bytes(b.n_logs));
+  hipLaunchKernelGGL(k_pairs_offsets, dim3(1), dim3(1024), 0, st, b, cnt, linfo, rinfo);
+  HIP_TRY(hipGetLastError());
+  auto* classify = large ? k_pairs_classify<true> : k_pairs_classify<false>;
+  hipLaunchKernelGGL(classify, dim3((unsigned)SMX_CEIL_DIV(b.n_pairs, (i64)BATCH_CHUNK)), dim3(256), 0, st, b, cnt,
+                     (const i32*)linfo, (const i32*)rinfo, lists, stride, large_list);
+  HIP_TRY(hipGetLastError());
+  return SMX_OK;
+}
+
+// The size queries of smx_batch and smx_batch_shared (n_shared 0).  Without the flag the size
+// depends on n_merges alone, and n_total and n_shared are not looked at.
 static int batch_ws_query(int64_t n_merges, int64_t n_total, int64_t n_shared, uint32_t flags, size_t* bytes) {
   if (flags & ~(uint32_t)SMX_BATCH_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_compose_batch_ex flag");
   if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
   if (n_merges < 0 || n_merges > 0x7fffffffll) return smx_set_error(SMX_E_ARG, "n_merges outside 0 .. 2^31 - 1");
-  size_t need = batch_base_bytes(n_merges);
-  if (flags & SMX_BATCH_LARGE) {
+  const bool large = (flags & SMX_BATCH_LARGE) != 0;
+  int64_t n_out = 0;
+  if (large) {
     if (n_total < 0 || n_shared < 0 || n_shared > n_total)
       return smx_set_error(SMX_E_ARG, "n_total negative, or n_shared outside 0 .. n_total");
-    const int64_t n_out = n_total - n_shared + n_merges * n_shared;
+    n_out = n_total - n_shared + n_merges * n_shared;
     if (n_total > 0x7fffffffll || n_out > 0x7fffffffll)
       return smx_set_error(SMX_E_ARG, "SMX_BATCH_LARGE: n_total (shared: or n_out) over 2^31 - 1");
-    need += batch_large_bytes(n_merges, n_out);
   }
-  *bytes = need;
+  *bytes = batch_ws_size(0, n_merges, n_out, large).total;
   return SMX_OK;
 }
 
@@ -149,58 +222,79 @@ extern "C" int smx_compose_batch_shared_workspace_bytes(int64_t n_merges, size_t
   return smx_compose_batch_shared_ex_workspace_bytes(n_merges, 0, 0, 0u, bytes);  // the same class counts and lists
 }
 
-// What the two batch structs are checked for alike, from n_sym's bound on; `index_ok`: the
-// struct's own index arrays are set, `index_names` names them; n_ops: the result entries.
-// (A batch of no merges is valid whatever else it holds; batch_run returns at once on it.)
-template <typename B>
-static int batch_check_args(const B* b, bool index_ok, const char* index_names, int64_t n_ops, const void* workspace,
-                            size_t workspace_bytes, uint32_t flags, const char* ws_query) {
+extern "C" int smx_compose_pairs_workspace_bytes(int64_t n_logs, int64_t n_pairs, int64_t n_out, uint32_t flags,
+                                                 size_t* bytes) {
+  if (flags & ~(uint32_t)SMX_BATCH_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_compose_pairs flag");
+  if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
+  if (n_logs < 0 || n_logs > 0x7fffffffll || n_pairs < 0 || n_pairs > 0x7fffffffll || n_out < 0)
+    return smx_set_error(SMX_E_ARG, "n_logs or n_pairs outside 0 .. 2^31 - 1, or n_out negative");
   const bool large = (flags & SMX_BATCH_LARGE) != 0;
+  if (large && n_out > 0x7fffffffll) return smx_set_error(SMX_E_ARG, "SMX_BATCH_LARGE: n_out over 2^31 - 1");
+  *bytes = batch_ws_size(pairs_info_bytes(n_logs, n_pairs), n_pairs, n_out, large).total;
+  return SMX_OK;
+}
+
+// What the three structs are checked for, in the order that decides which failure a caller
+// sees; `name`: the entry point; *form: the struct's batch_form, for batch_run.  (An empty batch
+// is valid whatever else it holds; batch_run returns at once on it.)
+template <typename B>
+static int batch_check_args(const char* name, const B* b, const void* workspace, size_t workspace_bytes,
+                            uint32_t flags, BatchForm* form) {
+  const bool large = (flags & SMX_BATCH_LARGE) != 0;
+  if (flags & ~(uint32_t)SMX_BATCH_LARGE)
+    return smx_set_error(SMX_E_ARG, (std::string("unknown ") + name + " flag").c_str());
+  if (!b) return smx_set_error(SMX_E_ARG, "null batch struct");
+  const BatchForm& f = *form = batch_form(*b);
+  if (f.items < 0 || f.items > 0x7fffffffll || b->n_total < 0 || b->n_sym < 0 || b->grid_cap < 0)
+    return smx_set_error(SMX_E_ARG, "negative size");
+  if (f.own_error) return smx_set_error(SMX_E_ARG, f.own_error);
   if (b->n_sym > 0xffffffffll) return smx_set_error(SMX_E_ARG, "n_sym over 2^32 - 1");
-  if (large && (b->n_total > 0x7fffffffll || n_ops > 0x7fffffffll))
-    return smx_set_error(SMX_E_ARG, "SMX_BATCH_LARGE: n_total (shared: or n_out) over 2^31 - 1");
-  if (b->n_merges == 0) return SMX_OK;
-  if (!index_ok || !b->conf_off || !b->counts || !b->conflicts)
-    return smx_set_error(SMX_E_ARG, (std::string("null ") + index_names + " / conf_off / counts / conflicts").c_str());
-  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1 || !b->order ||
-                         !b->addr || !b->file || !b->ctx))
-    return smx_set_error(SMX_E_ARG, "null column or result array");
-  const size_t need = batch_base_bytes(b->n_merges) + (large ? batch_large_bytes(b->n_merges, n_ops) : 0);
-  if (!workspace || workspace_bytes < need || (large && ((uintptr_t)workspace & 7)))
+  if (large && (b->n_total > 0x7fffffffll || f.n_ops > 0x7fffffffll))
+    return smx_set_error(SMX_E_ARG, "SMX_BATCH_LARGE: n_total or n_out (the result entries) over 2^31 - 1");
+  if (f.empty) return SMX_OK;
+  if (!f.index_ok || !b->conf_off || !b->counts || !b->conflicts)
+    return smx_set_error(SMX_E_ARG,
+                         (std::string("null ") + f.index_names + " / conf_off / counts / conflicts").c_str());
+  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1))
+    return smx_set_error(SMX_E_ARG, "null column");
+  // (a shared batch of at least one merge has result entries exactly when n_total > 0)
+  if (f.n_ops > 0 && (!b->order || !b->addr || !b->file || !b->ctx))
+    return smx_set_error(SMX_E_ARG, "null result array");
+  const bool aligned = large || f.aligned;
+  if (!workspace || workspace_bytes < batch_ws_size(f.info, f.items, f.n_ops, large).total ||
+      (aligned && ((uintptr_t)workspace & 7)))
     return smx_set_error(SMX_E_WORKSPACE,
-                         (std::string(large ? "workspace too small or not 8-byte aligned (" : "workspace too small (") +
-                          ws_query + ")").c_str());
+                         (std::string("workspace too small") + (aligned ? " or not 8-byte aligned (" : " (") +
+                          (flags ? std::string(name) + "_workspace_bytes" : f.plain_query) + ")").c_str());
   (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
   return SMX_OK;
 }
 
-// k_batch_classify, then the three classes' k_compose_batch; with SMX_BATCH_LARGE the fourth
-// list's k_compose_batch_large after them.
+// The checks; then the form's pre-pass and the three classes' k_compose_batch, with
+// SMX_BATCH_LARGE the fourth list's k_compose_batch_large after them.
 template <typename B>
-static int batch_run(const B* b, int first, int first_large, int64_t n_ops, void* workspace, uint32_t flags,
+static int batch_run(const char* name, const B* b, void* workspace, size_t workspace_bytes, uint32_t flags,
                      void* stream) {
-  if (b->n_merges == 0) return SMX_OK;
+  BatchForm f;
+  if (int rc = batch_check_args(name, b, workspace, workspace_bytes, flags, &f)) return rc;
+  if (f.empty) return SMX_OK;
   try {
     const int* resident;
     if (int rc = resident_of(&resident)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const size_t stride = batch_list_bytes(b->n_merges) / 4;
-    u32* cnt = (u32*)workspace;
-    u32* lists = (u32*)((char*)workspace + BATCH_HDR);
     const bool large = (flags & SMX_BATCH_LARGE) != 0;
-    const BatchLargeWs x =
-        large ? batch_large_ws((char*)workspace + batch_base_bytes(b->n_merges), b->n_merges, n_ops) : BatchLargeWs{};
-    if (large)
-      hipLaunchKernelGGL((k_batch_classify<B, true>), dim3(1), dim3(256), 0, st, *b, cnt, lists, stride, x.list);
-    else
-      hipLaunchKernelGGL((k_batch_classify<B, false>), dim3(1), dim3(256), 0, st, *b, cnt, lists, stride,
-                         (u32*)nullptr);
-    HIP_TRY(hipGetLastError());
-    if (int rc = launch_classes(kBatchKernels<B>, kBatchCaps, resident + first, b->n_merges, b->grid_cap, st, cnt, lists,
+    const size_t stride = batch_list_bytes(f.items) / 4;
+    u32* cnt = (u32*)workspace;
+    char* info = (char*)workspace + BATCH_HDR;
+    u32* lists = (u32*)(info + f.info);
+    const size_t base = batch_ws_size(f.info, f.items, f.n_ops, large).base;
+    const BatchLargeWs x = large ? batch_large_ws((char*)workspace + base, f.items, f.n_ops) : BatchLargeWs{};
+    if (int rc = batch_prepass(*b, cnt, info, lists, stride, x.list, large, st)) return rc;
+    if (int rc = launch_classes(kBatchKernels<B>, kBatchCaps, resident + f.first, f.items, b->grid_cap, st, cnt, lists,
                                 stride, *b))
       return rc;
     if (large) {
-      hipLaunchKernelGGL(k_compose_batch_large<B>, capped_grid(resident[first_large], b->n_merges, b->grid_cap),
+      hipLaunchKernelGGL(k_compose_batch_large<B>, capped_grid(resident[f.first_large], f.items, b->grid_cap),
                          dim3(LARGE_NT), 0, st, *b, (const u32*)(cnt + BATCH_CLASSES), x);
       HIP_TRY(hipGetLastError());
     }
@@ -212,14 +306,7 @@ static int batch_run(const B* b, int first, int first_large, int64_t n_ops, void
 
 extern "C" int smx_compose_batch_ex(const smx_batch* b, void* workspace, size_t workspace_bytes, uint32_t flags,
                                     void* stream) {
-  if (flags & ~(uint32_t)SMX_BATCH_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_compose_batch_ex flag");
-  if (!b) return smx_set_error(SMX_E_ARG, "null batch");
-  if (b->n_merges < 0 || b->n_merges > 0x7fffffffll || b->n_total < 0 || b->n_sym < 0 || b->grid_cap < 0)
-    return smx_set_error(SMX_E_ARG, "negative size");
-  if (int rc = batch_check_args(b, b->off && b->n_a, "off / n_a", b->n_total, workspace, workspace_bytes, flags,
-                                flags ? "smx_compose_batch_ex_workspace_bytes" : "smx_compose_batch_workspace_bytes"))
-    return rc;
-  return batch_run(b, R_BATCH, R_LARGE, b->n_total, workspace, flags, stream);
+  return batch_run(__func__, b, workspace, workspace_bytes, flags, stream);
 }
 
 extern "C" int smx_compose_batch(const smx_batch* b, void* workspace, size_t workspace_bytes, void* stream) {
@@ -228,19 +315,7 @@ extern "C" int smx_compose_batch(const smx_batch* b, void* workspace, size_t wor
 
 extern "C" int smx_compose_batch_shared_ex(const smx_batch_shared* b, void* workspace, size_t workspace_bytes,
                                            uint32_t flags, void* stream) {
-  if (flags & ~(uint32_t)SMX_BATCH_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_compose_batch_shared_ex flag");
-  if (!b) return smx_set_error(SMX_E_ARG, "null batch");
-  if (b->n_merges < 0 || b->n_merges > 0x7fffffffll || b->n_total < 0 || b->n_sym < 0 || b->n_shared < 0 ||
-      b->grid_cap < 0)
-    return smx_set_error(SMX_E_ARG, "negative size");
-  if (b->n_shared > b->n_total) return smx_set_error(SMX_E_ARG, "n_shared over n_total");
-  if (b->shared_is_b != 0 && b->shared_is_b != 1) return smx_set_error(SMX_E_ARG, "shared_is_b is neither 0 nor 1");
-  const int64_t n_out = b->n_total - b->n_shared + b->n_merges * b->n_shared;  // (each factor <= 2^31: no overflow)
-  if (int rc = batch_check_args(b, b->off != nullptr, "off", n_out, workspace, workspace_bytes, flags,
-                                flags ? "smx_compose_batch_shared_ex_workspace_bytes"
-                                      : "smx_compose_batch_shared_workspace_bytes"))
-    return rc;
-  return batch_run(b, R_SHARED, R_LARGE_SHARED, n_out, workspace, flags, stream);
+  return batch_run(__func__, b, workspace, workspace_bytes, flags, stream);
 }
 
 extern "C" int smx_compose_batch_shared(const smx_batch_shared* b, void* workspace, size_t workspace_bytes,
@@ -248,82 +323,9 @@ extern "C" int smx_compose_batch_shared(const smx_batch_shared* b, void* workspa
   return smx_compose_batch_shared_ex(b, workspace, workspace_bytes, 0u, stream);
 }
 
-// The pairs form's workspace: the class counts, linfo and rinfo, the three class lists; with
-// SMX_BATCH_LARGE the fourth list and the slices, n_out entries long.
-static size_t pairs_base_bytes(int64_t n_logs, int64_t n_pairs) {
-  return BATCH_HDR + pairs_info_bytes(n_logs, n_pairs) + BATCH_CLASSES * batch_list_bytes(n_pairs);
-}
-
-extern "C" int smx_compose_pairs_workspace_bytes(int64_t n_logs, int64_t n_pairs, int64_t n_out, uint32_t flags,
-                                                 size_t* bytes) {
-  if (flags & ~(uint32_t)SMX_BATCH_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_compose_pairs flag");
-  if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
-  if (n_logs < 0 || n_logs > 0x7fffffffll || n_pairs < 0 || n_pairs > 0x7fffffffll || n_out < 0)
-    return smx_set_error(SMX_E_ARG, "n_logs or n_pairs outside 0 .. 2^31 - 1, or n_out negative");
-  const bool large = (flags & SMX_BATCH_LARGE) != 0;
-  if (large && n_out > 0x7fffffffll) return smx_set_error(SMX_E_ARG, "SMX_BATCH_LARGE: n_out over 2^31 - 1");
-  *bytes = pairs_base_bytes(n_logs, n_pairs) + (large ? batch_large_bytes(n_pairs, n_out) : 0);
-  return SMX_OK;
-}
-
-// k_pairs_offsets and k_pairs_classify, then the three classes' k_compose_batch; with
-// SMX_BATCH_LARGE the fourth list's k_compose_batch_large after them.
 extern "C" int smx_compose_pairs(const struct smx_pairs* b, void* workspace, size_t workspace_bytes, uint32_t flags,
                                  void* stream) {
-  if (flags & ~(uint32_t)SMX_BATCH_LARGE) return smx_set_error(SMX_E_ARG, "unknown smx_compose_pairs flag");
-  const bool large = (flags & SMX_BATCH_LARGE) != 0;
-  if (!b) return smx_set_error(SMX_E_ARG, "null pairs");
-  if (b->n_logs < 0 || b->n_logs > 0x7fffffffll || b->n_pairs < 0 || b->n_pairs > 0x7fffffffll || b->n_total < 0 ||
-      b->n_sym < 0 || b->n_out < 0 || b->grid_cap < 0)
-    return smx_set_error(SMX_E_ARG, "negative size");
-  if (b->n_sym > 0xffffffffll) return smx_set_error(SMX_E_ARG, "n_sym over 2^32 - 1");
-  if (large && (b->n_total > 0x7fffffffll || b->n_out > 0x7fffffffll))
-    return smx_set_error(SMX_E_ARG, "SMX_BATCH_LARGE: n_total or n_out over 2^31 - 1");
-  if (b->n_pairs == 0 || b->n_logs == 0) return SMX_OK;
-  if (!b->log_off || !b->pair_a || !b->pair_b || !b->res_off || !b->conf_off || !b->counts || !b->conflicts)
-    return smx_set_error(SMX_E_ARG, "null log_off / pair_a / pair_b / res_off / conf_off / counts / conflicts");
-  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1))
-    return smx_set_error(SMX_E_ARG, "null column");
-  if (b->n_out > 0 && (!b->order || !b->addr || !b->file || !b->ctx))
-    return smx_set_error(SMX_E_ARG, "null result array");
-  const size_t base = pairs_base_bytes(b->n_logs, b->n_pairs);
-  const size_t need = base + (large ? batch_large_bytes(b->n_pairs, b->n_out) : 0);
-  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < need)
-    return smx_set_error(SMX_E_WORKSPACE,
-                         "workspace too small or not 8-byte aligned (smx_compose_pairs_workspace_bytes)");
-  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
-  try {
-    const int* resident;
-    if (int rc = resident_of(&resident)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t stride = batch_list_bytes(b->n_pairs) / 4;
-    u32* cnt = (u32*)workspace;
-    i32* linfo = (i32*)((char*)workspace + BATCH_HDR);
-    i32* rinfo = (i32*)((char*)linfo + batch_list_bytes(b->n_logs));
-    u32* lists = (u32*)((char*)workspace + BATCH_HDR + pairs_info_bytes(b->n_logs, b->n_pairs));
-    const BatchLargeWs x = large ? batch_large_ws((char*)workspace + base, b->n_pairs, b->n_out) : BatchLargeWs{};
-    const dim3 classify_grid((unsigned)SMX_CEIL_DIV(b->n_pairs, (i64)BATCH_CHUNK));
-    hipLaunchKernelGGL(k_pairs_offsets, dim3(1), dim3(1024), 0, st, *b, cnt, linfo, rinfo);
-    HIP_TRY(hipGetLastError());
-    if (large)
-      hipLaunchKernelGGL(k_pairs_classify<true>, classify_grid, dim3(256), 0, st, *b, cnt, (const i32*)linfo,
-                         (const i32*)rinfo, lists, stride, x.list);
-    else
-      hipLaunchKernelGGL(k_pairs_classify<false>, classify_grid, dim3(256), 0, st, *b, cnt, (const i32*)linfo,
-                         (const i32*)rinfo, lists, stride, (u32*)nullptr);
-    HIP_TRY(hipGetLastError());
-    if (int rc = launch_classes(kBatchKernels<smx_pairs>, kBatchCaps, resident + R_PAIRS, b->n_pairs, b->grid_cap, st,
-                                cnt, lists, stride, *b))
-      return rc;
-    if (large) {
-      hipLaunchKernelGGL(k_compose_batch_large<smx_pairs>, capped_grid(resident[R_LARGE_PAIRS], b->n_pairs, b->grid_cap),
-                         dim3(LARGE_NT), 0, st, *b, (const u32*)(cnt + BATCH_CLASSES), x);
-      HIP_TRY(hipGetLastError());
-    }
-    return SMX_OK;
-  } catch (const std::exception& e) {
-    return smx_set_error(SMX_E_HIP, e.what());
-  }
+  return batch_run(__func__, b, workspace, workspace_bytes, flags, stream);
 }
 
 extern "C" int smx_screen_ex_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs, uint32_t flags,

@@ -72,3 +72,17 @@ def alternating_groups(spec, big, small):
         grp = 2 * (k // period) + ((k % period) >= big)
         soa.ts[lo:lo + m] = soa.ts[0] + grp.astype(np.uint64) * np.uint64(2)
     return soa
+
+
+# Merges of at most 2048 ops for the small plan and the batch: the sizes' edges, ties, shuffled logs.
+SPECS = [
+    synth.LiftSpec(1, 1, 3),
+    synth.LiftSpec(2, 1, 4),
+    synth.LiftSpec(17, 3, 5, ops_per_ms=1),
+    synth.LiftSpec(1000, 100, 6),
+    synth.LiftSpec(1000, 20, 7, shuffle=True),
+    synth.LiftSpec(2000, 30, 8, ops_per_ms=4096, mix=synth.ADVERSARIAL_MIX, rename_overlap=1.0),
+    synth.LiftSpec(2047, 5, 9, ops_per_ms=1, mix=synth.ADVERSARIAL_MIX, divergent=0.5),
+    synth.LiftSpec(2048, 2048, 10, shuffle=True, mix=synth.ADVERSARIAL_MIX),
+    synth.LiftSpec(2048, 1, 12, ops_per_ms=1),
+]

@@ -7,7 +7,7 @@ import numpy as np
 from oracle import oracle
 
 import _cand
-from test_gpu_screen import make_log
+from _screen import make_log
 
 RENAME = _cand.RENAME
 N_LOGS, SPACE = 30, 120

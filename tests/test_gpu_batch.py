@@ -8,43 +8,19 @@ import copy
 import numpy as np
 import pytest
 
-from oracle import oracle
 from semantic_merge_amd import _abi, synth
 from semantic_merge_amd._lib import DeviceBatch, SmxError, compose_soa, compose_soa_many
 from semantic_merge_amd.marshal import marshal
 from semantic_merge_amd.materialize import materialize_conflicts, materialize_ops
 
-from _shapes import pick
+from _batch import check_all, lift, none_moves, ref
+from _shapes import SPECS, pick
 from _util import _eq_soa as _eq, jline, load, to_ops
-from test_gpu_small import SPECS
 
 pytestmark = pytest.mark.gpu
 
 FILL = 0x5A5A5A5A  # what every output word holds before a run that checks the unwritten ones
 MOVE = synth.KIND_RANK["moveDecl"]
-
-
-def lift(n, n_sym, seed, **kw):
-    return synth.lift_soa(synth.lift_logs(synth.LiftSpec(n, n_sym, seed, **kw)))
-
-
-_ref = {}
-
-
-def ref(soa):
-    """oracle.compose(soa), computed once per SoA object."""
-    got = _ref.get(id(soa))
-    if got is None:
-        got = _ref[id(soa)] = (soa, oracle.compose(soa))
-    return got[1]
-
-
-def none_moves(soa, seed, p=0.6):
-    rng = np.random.default_rng(seed)
-    mv = np.flatnonzero(soa.kind == MOVE)
-    soa.v0[mv[rng.random(len(mv)) < p]] = -1
-    soa.v1[mv[rng.random(len(mv)) < p]] = -1
-    return soa
 
 
 @pytest.fixture(scope="module")
@@ -60,13 +36,6 @@ def mixed40():
         out.append(none_moves(soa, i) if i % 5 == 1 else soa)
     assert any(len(ref(s)[4]) for s in out)
     return out
-
-
-def check_all(got, soas, label):
-    assert len(got) == len(soas)
-    for m, (g, s) in enumerate(zip(got, soas)):
-        assert not isinstance(g, int), f"{label}: merge {m} failed with counts {g}"
-        _eq(g, ref(s), f"{label}: merge {m} ({s.n} ops)")
 
 
 def test_golden_in_one_batch():

@@ -16,6 +16,7 @@ from semantic_merge_amd._lib import (DeviceBatch, DeviceBatchShared, compose_soa
                                      session)
 from semantic_merge_amd.marshal import ID_UUID, TS_ISO, SharedSoA
 
+from _batch import check_all, check_unwritten, lift, none_moves, ref
 from _shapes import pick
 from _util import _eq_soa as _eq, jline, to_ops
 
@@ -26,29 +27,6 @@ MOVE = synth.KIND_RANK["moveDecl"]
 RENAME = synth.KIND_RANK["renameSymbol"]
 LARGE = _abi.BATCH_LARGE
 COLS = ("kind", "ts", "oid_hi", "oid_lo", "sym", "v0", "v1")
-
-
-def lift(n, n_sym, seed, **kw):
-    return synth.lift_soa(synth.lift_logs(synth.LiftSpec(n, n_sym, seed, **kw)))
-
-
-_ref = {}
-
-
-def ref(soa):
-    """oracle.compose(soa), computed once per SoA object."""
-    got = _ref.get(id(soa))
-    if got is None:
-        got = _ref[id(soa)] = (soa, oracle.compose(soa))
-    return got[1]
-
-
-def none_moves(soa, seed, p=0.6):
-    rng = np.random.default_rng(seed)
-    mv = np.flatnonzero(soa.kind == MOVE)
-    soa.v0[mv[rng.random(len(mv)) < p]] = -1
-    soa.v1[mv[rng.random(len(mv)) < p]] = -1
-    return soa
 
 
 def split(base, n, n_a):
@@ -64,25 +42,6 @@ def run(soas, **kw):
     db.run()
     raw = db.raw()
     return db, raw, db.results(raw)
-
-
-def check_all(got, soas, label):
-    assert len(got) == len(soas)
-    for m, (g, s) in enumerate(zip(got, soas)):
-        assert not isinstance(g, int), f"{label}: merge {m} failed with counts {g}"
-        _eq(g, ref(s), f"{label}: merge {m} ({s.n} ops, n_a {s.n_a})")
-
-
-def check_unwritten(db, raw, soas, failed=()):
-    """Nothing past a merge's composed ops or conflict pairs, nothing at all for a failed merge."""
-    for m, s in enumerate(soas):
-        o, c = int(db.off[m]), int(db.conf_off[m])
-        cap = int(db.conf_off[m + 1]) - c
-        k, nc = (0, 0) if m in failed else (int(x) for x in raw["counts"][2 * m: 2 * m + 2])
-        for name in ("order", "addr", "file", "ctx"):
-            assert (raw[name][o + k: o + s.n] == FILL).all(), f"merge {m}: {name} written past its {k} ops"
-        assert (raw["conf"][2 * (c + min(nc, cap)): 2 * (c + cap)] == FILL).all(), f"merge {m}: conflicts past its pairs"
-    assert (raw["conf"][2 * int(db.conf_off[-1]):] == FILL).all()
 
 
 @pytest.fixture(scope="module")

@@ -11,9 +11,9 @@ from semantic_merge_amd import _abi, synth
 from semantic_merge_amd._lib import ComposeSession, DeviceCandidates, SmxError, screen_all_soa, screen_soa
 
 import _cand
+from _batch import ADV, branch
+from _screen import empty_log, make_log, with_renames
 from _util import jline, to_ops
-from test_gpu_screen import empty_log, make_log, with_renames
-from test_gpu_shared import ADV, branch
 
 pytestmark = pytest.mark.gpu
 

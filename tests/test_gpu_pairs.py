@@ -14,10 +14,10 @@ from semantic_merge_amd._lib import DeviceBatch, DeviceBatchShared, SmxError, co
 from semantic_merge_amd._session import ComposeSession
 from semantic_merge_amd.marshal import ID_UUID, TS_ISO, SharedSoA
 
+from _batch import ADV, branch, own_logs
 from _pairs import COLS, FILL, check, gap_log, logs_soa, ref, run, same_bytes
 from _shapes import pick
 from _util import _eq_soa as _eq, jline, to_ops
-from test_gpu_shared import ADV, branch, own_logs
 
 pytestmark = pytest.mark.gpu
 

@@ -11,9 +11,9 @@ import pytest
 from semantic_merge_amd import _abi, synth
 from semantic_merge_amd._lib import DeviceBatch, compose_pairs_soa, session
 
+from _batch import ADV, branch, none_moves
 from _pairs import FILL, check, gap_log, logs_soa, ref, run, same_bytes
 from _util import _eq_soa as _eq
-from test_gpu_shared import ADV, branch, none_moves
 
 pytestmark = pytest.mark.gpu
 

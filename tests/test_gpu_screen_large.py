@@ -12,10 +12,10 @@ from semantic_merge_amd import _abi, synth
 from semantic_merge_amd._lib import ComposeSession, screen_soa
 
 import _cand
+from _batch import ADV, branch
+from _screen import (FILL, RENAME, check_all, check_unwritten, empty_log, logs_soa, make_log, ref, renames_ordered,
+                     run, with_renames)
 from _util import jline, to_ops
-from test_gpu_screen import (FILL, RENAME, check_all, check_unwritten, empty_log, logs_soa, make_log, ref,
-                             renames_ordered, run, with_renames)
-from test_gpu_shared import ADV, branch
 
 pytestmark = pytest.mark.gpu
 

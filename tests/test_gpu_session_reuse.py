@@ -8,7 +8,7 @@ from semantic_merge_amd import synth
 from semantic_merge_amd._lib import ComposeSession
 
 import _cand
-from test_gpu_shared import ADV, branch, own_logs, shared_soa
+from _batch import ADV, branch, own_logs, shared_soa
 
 pytestmark = pytest.mark.gpu
 

@@ -12,8 +12,8 @@ import pytest
 from oracle import oracle
 from semantic_merge_amd import _abi, synth
 from semantic_merge_amd._lib import DeviceBatchShared, SmxError, compose_soa_many, compose_soa_shared
-from semantic_merge_amd.marshal import SharedSoA, TS_ISO, ID_UUID
 
+from _batch import ADV, branch, own_logs, shared_soa
 from _shapes import pick
 from _util import _eq_soa as _eq, jline, to_ops
 
@@ -21,39 +21,6 @@ pytestmark = pytest.mark.gpu
 
 FILL = 0x5A5A5A5A  # what every output word holds before a run that checks the unwritten ones
 MOVE = synth.KIND_RANK["moveDecl"]
-COLS = ("kind", "ts", "oid_hi", "oid_lo", "sym", "v0", "v1")
-GAP = {"kind": 0xFF, "sym": 0xFFFFFFFF, "v0": -1, "v1": -1}  # invalid: a kernel that read a gap would report -1
-ADV = dict(mix=synth.ADVERSARIAL_MIX, divergent=0.5, rename_overlap=1.0)
-
-
-def branch(n, n_sym, seed, side, **kw):
-    """One branch log of n ops (side 0: a lift log's A branch, 1: its B branch), as an SoA
-    with the other branch empty."""
-    soa = synth.lift_soa(synth.lift_logs(synth.LiftSpec(2 * n, n_sym, seed, **kw)))
-    a, b = np.ones(soa.n_a, bool), np.ones(soa.n_b, bool)
-    return pick(soa, a, ~b) if side == 0 else pick(soa, ~a, b)
-
-
-def none_moves(soa, seed, p=0.6):
-    rng = np.random.default_rng(seed)
-    mv = np.flatnonzero(soa.kind == MOVE)
-    soa.v0[mv[rng.random(len(mv)) < p]] = -1
-    soa.v1[mv[rng.random(len(mv)) < p]] = -1
-    return soa
-
-
-def shared_soa(shared, owns, n_sym, gap=0):
-    """The SharedSoA of one shared branch log and the own logs, `gap` invalid entries
-    between the shared log and the first own log."""
-    parts = [shared] + list(owns)
-    cols = []
-    for c in COLS:
-        arrs = [np.asarray(getattr(p, c)) for p in parts]
-        if gap:
-            arrs.insert(1, np.full(gap, GAP.get(c, 0), arrs[0].dtype))
-        cols.append(np.concatenate(arrs))
-    off = shared.n + gap + np.concatenate([[0], np.cumsum([o.n for o in owns], dtype=np.int64)]).astype(np.int64)
-    return SharedSoA(shared.n, off, *cols, n_sym, [], TS_ISO, ID_UUID)
 
 
 _ref = {}
@@ -75,18 +42,6 @@ def check_all(got, ssoa, label, shared_is_b=False, skip=()):
             continue
         assert not isinstance(g, int), f"{label}: merge {m} failed with counts {g}"
         _eq(g, ref(ssoa, m, shared_is_b), f"{label}: merge {m}")
-
-
-def own_logs(n_sym, seed0, sizes):
-    """Own logs as test_gpu_batch.py's mixed40: an adversarial mix with divergent renames
-    against the shared log's renames, None-valued moves, a shuffled branch, dense ties."""
-    out = []
-    for i, n in enumerate(sizes):
-        kw = [ADV, dict(ops_per_ms=3), dict(shuffle=True, mix=synth.ADVERSARIAL_MIX),
-              dict(ops_per_ms=4096, mix=synth.ADVERSARIAL_MIX), dict()][i % 5]
-        soa = branch(n, n_sym, seed0 + i, 1, **kw)
-        out.append(none_moves(soa, i) if i % 5 == 1 else soa)
-    return out
 
 
 @pytest.fixture(scope="module", params=[60, 700])

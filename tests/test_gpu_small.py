@@ -8,6 +8,7 @@ from oracle import oracle
 from semantic_merge_amd import synth
 from semantic_merge_amd._lib import DeviceCompose, compose_soa, set_small_limit
 
+from _shapes import SPECS
 from _util import _eq_soa as _eq, assert_case, load
 
 pytestmark = pytest.mark.gpu
@@ -25,19 +26,6 @@ def test_golden_both_plans(plan):
         assert_case(compose_soa, case, f"{plan} {name}")
     for i, case in enumerate(load("compose_cases.json")):
         assert_case(compose_soa, case, f"{plan} case {i}")
-
-
-SPECS = [
-    synth.LiftSpec(1, 1, 3),
-    synth.LiftSpec(2, 1, 4),
-    synth.LiftSpec(17, 3, 5, ops_per_ms=1),
-    synth.LiftSpec(1000, 100, 6),
-    synth.LiftSpec(1000, 20, 7, shuffle=True),
-    synth.LiftSpec(2000, 30, 8, ops_per_ms=4096, mix=synth.ADVERSARIAL_MIX, rename_overlap=1.0),
-    synth.LiftSpec(2047, 5, 9, ops_per_ms=1, mix=synth.ADVERSARIAL_MIX, divergent=0.5),
-    synth.LiftSpec(2048, 2048, 10, shuffle=True, mix=synth.ADVERSARIAL_MIX),
-    synth.LiftSpec(2048, 1, 12, ops_per_ms=1),
-]
 
 
 @pytest.mark.parametrize("spec", SPECS, ids=lambda s: f"{s.n_total}x{s.n_sym}s{s.seed}")
