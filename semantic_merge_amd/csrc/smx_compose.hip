@@ -18,9 +18,11 @@
 //   k_wcount    per-window kind counts + presorted-layout checks
 //   k_wscan     window offsets and kind totals  k_bases   T segment starts
 //   [generic]   radix-sort each branch by (ts, oid) and cut fixed windows
-//   k_window    per window, in LDS: merge A/B parts, multisplit by kind, sort
-//               equal-timestamp groups by id; the moves' final records, the other
-//               ops' (source, symbol) in T order, natural-head DivergentRename flags
+//   k_window    per window, in LDS: the T order (presorted, k_window_f: ops grouped by
+//               (kind, timestamp run), each group ordered by id, no merge; generic,
+//               k_window_g: merge A/B parts, multisplit by kind); the moves' final
+//               records, the other ops' (source, symbol) in T order, natural-head
+//               DivergentRename flags
 //   walk        k_boundary -> candidate scan/compact -> k_replay_q -> max-scan ->
 //               k_cluster -> scan -> k_replay_write (conflict pairs, skip bits,
 //               sorted skip list)
@@ -149,8 +151,8 @@ static Ctx make_ctx(const smx_ops* ops, const smx_compose_out* out, void* ws, co
   return Ctx{ops, out, st, L, (char*)ws, ops->n_a, ops->n_b, ops->n_a + ops->n_b, ops->n_sym, src_a, src_b, tm};
 }
 
-// Diagnostic builds only (tools/window_phases.py): a device buffer for k_window_f
-// phase stamps.
+// Diagnostic builds only (tools/window_phases.py): a device buffer for k_window_f's
+// step stamps (its DBG instances: the shipped order with stamps).
 #if SMX_DIAG
 static void* g_phase_dbg = nullptr;
 static size_t g_phase_dbg_bytes = 0;
@@ -562,14 +564,14 @@ static i64 first_tgt(const Ctx& C) {
 }
 
 // One k_window_f instance over P.W windows; the release instances of one capacity.
-template <int CAP, int NT, bool DBG, bool MAP, bool RUNS>
+template <int CAP, int NT, bool DBG, bool MAP>
 static void launch_window_f(const WinArgs& P, hipStream_t st) {
-  hipLaunchKernelGGL((k_window_f<CAP, NT, DBG, MAP, RUNS>), dim3(P.W), dim3(NT), 0, st, P);
+  hipLaunchKernelGGL((k_window_f<CAP, NT, DBG, MAP>), dim3(P.W), dim3(NT), 0, st, P);
 }
 template <int CAP, int NT>
 static void launch_window_level(const WinArgs& P, hipStream_t st) {
-  if (P.src_map) launch_window_f<CAP, NT, false, true, true>(P, st);
-  else launch_window_f<CAP, NT, false, false, true>(P, st);
+  if (P.src_map) launch_window_f<CAP, NT, false, true>(P, st);
+  else launch_window_f<CAP, NT, false, false>(P, st);
 }
 
 // The presorted windows over the boundaries k_fpart left (W windows).
@@ -590,8 +592,8 @@ static int launch_presorted_windows(const Ctx& C, i64 W, i64 CM, int level) {
 #if SMX_DIAG
   if (g_phase_dbg && !P.src_map && (size_t)W * WF_NSTAMP * 8 <= g_phase_dbg_bytes) {
     P.dbg = (u64*)g_phase_dbg;
-    if (wide) launch_window_f<WF_WIDE_CAP, WF_WIDE_NT, true, false, false>(P, st);
-    else launch_window_f<WF_CAP, WF_NT, true, false, false>(P, st);
+    if (wide) launch_window_f<WF_WIDE_CAP, WF_WIDE_NT, true, false>(P, st);
+    else launch_window_f<WF_CAP, WF_NT, true, false>(P, st);
   } else
 #endif
   if (wide) launch_window_level<WF_WIDE_CAP, WF_WIDE_NT>(P, st);

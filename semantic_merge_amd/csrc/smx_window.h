@@ -4,15 +4,28 @@
 // (semmerge/compose.py:16-21 sorted() per branch + the A-first merge of :51-56).
 // A window is a pair of contiguous ranges, one per branch, such that every op of
 // the window precedes, in (timestamp, id, side, index) order, every op of the
-// next window.  Inside one window (all in LDS):
-//   1. merge the A part and the B part by timestamp (A first on ties)   -> S
-//   2. stable multisplit of S by precedence rank (wave64 ballots)       -> slots
-//   3. equal-(rank, timestamp) groups are contiguous slot ranges; order each by
-//      (id, side, index) with a counting rank over the group
-//   4. T position = base[rank] + (ops of that rank in earlier windows) + local
+// next window.  An op's T position = base[kind] + (ops of that kind in earlier
+// windows) + its place among the window's ops of that kind.
+//
 // The presorted kernel (k_window_f) handles branch logs whose timestamps never
-// decrease (lift.ts emits them in order); k_window_g handles branch logs that the
-// generic path pre-sorted by (timestamp, id), where step 3 is not needed.
+// decrease (lift.ts emits them in order).  Its order is run-grouped: no merge, no
+// multisplit, all in LDS.  Inside a branch part the timestamps never decrease, so the
+// equal-timestamp ops of both parts form one run of the merged order S, which starts
+// at S position spos(v) = #{A ops < v} + #{B ops < v} (A first on ties, compose.py:54).
+// Each run's heads (the first op of its value in a part) find spos by a 64-way search
+// of the other part; the runs' dense index r comes from an occupancy mask over S
+// positions.  An op's group is (kind, r) and the groups laid out kind-major ARE the
+// window's T order of groups (T is ordered by kind, then timestamp): one histogram +
+// scan of KD * R counters gives every group's start, then each group is ordered by
+// (id, side, index) with interpolation buckets on the top 32 bits of the id (one op
+// per bucket on random ids) and a rank inside the bucket, equal 32-bit keys on the full
+// ids.  A window with more than GMAX groups (very many distinct timestamps) fails the
+// plan as a window too large (f_fail 2): the host retries with smaller windows.
+//
+// The generic kernel (k_window_g) is the one that merges: it handles branch logs that
+// the generic path pre-sorted by (timestamp, id), with a merge path over the full keys
+// (A first on ties) and a stable multisplit of the merged order by kind (wave64
+// ballots); no order inside a group is left to find.
 //
 // What a window writes, T-ordered:
 //   moves (T < nMv)     the FINAL composed records: no skip precedes the rename
@@ -204,29 +217,23 @@ __device__ __forceinline__ void win_rename_flags(const WinArgs& P, i64 w, u64 Mb
 #define WF_ITEMS (WF_CAP / WF_NT)
 #define WF_KP ((2 * CH + WF_NT - 1) / WF_NT)  // partial-chunk kinds per lane
 
-// LDS ~34 KB (buffers are reused across phases) so 4 workgroups fit a CU: while
-// some workgroups run their LDS phases, others stream their windows from HBM.
-// DBG: phase timestamps of every window (diagnostics, tools/window_phases.py):
-// lane 0 of wave 0 stores s_memtime after each phase into P.dbg[w * WF_NSTAMP + i].
-#define WF_NSTAMP 24
-// Diagnostic builds: SMX_ABLATE = 100 + N leaves the kernel after phase N (timing of
-// the phases by difference, tools/window_ablate.py); results invalid.
+// LDS ~36 KB (buffers are reused across steps) so 4 workgroups fit a CU: while
+// some workgroups run their LDS steps, others stream their windows from HBM.
+// DBG: step timestamps of every window (diagnostics, tools/window_phases.py):
+// lane 0 of wave 0 stores s_memtime at the start (i = 0) and after step i = 1 .. 14 into
+// P.dbg[w * WF_NSTAMP + i].
+#define WF_NSTAMP 16
+// Diagnostic builds: SMX_ABLATE = 100 + N leaves the kernel after step N = 2 .. 13 (timing
+// of the steps by difference, tools/window_ablate.py); results invalid.  The bit-tested
+// ablations (WF_ABL: 4 = stop before the payload, 16 = load only) are values below 100.
 #define WF_EXIT(N)                                                         \
   do {                                                                     \
     if (SMX_DIAG && P.ablate == 100 + (N)) {                               \
-      if (t == 0 && sord[0] == 0xfffeu && fin[1] == 0xfffeu) P.meta->dup_key = 1; \
+      if (t == 0 && sord[0] == 0xfffeu && rown[1] == 0xfffeu) P.meta->dup_key = 1; \
       return;                                                              \
     }                                                                      \
   } while (0)
-// the run-grouped order's phase exits (diagnostic builds: SMX_ABLATE = 0x10000 + N, a value
-// clear of the bit-tested ablations 1, 2, 4 (N <= 3 only) and 16)
-#define RX_EXIT(N)                                                          \
-  do {                                                                      \
-    if (SMX_DIAG && P.ablate == 0x10000 + (N)) {                            \
-      if (t == 0 && sord[0] == 0xfffeu && fin[1] == 0xfffeu) P.meta->dup_key = 1; \
-      return;                                                               \
-    }                                                                       \
-  } while (0)
+#define WF_ABL(bit) (SMX_DIAG && P.ablate < 100 && (P.ablate & (bit)))
 #define WSTAMP(i)                                                                  \
   do {                                                                             \
     if (DBG && t == 0) P.dbg[w * WF_NSTAMP + (i)] = __builtin_amdgcn_s_memtime(); \
@@ -237,34 +244,33 @@ __device__ __forceinline__ void win_rename_flags(const WinArgs& P, i64 w, u64 Mb
 #ifndef WF_MINB
 #define WF_MINB 8
 #endif
-template <int CAP, int NT, bool DBG, bool MAP, bool RUNS = false>
+template <int CAP, int NT, bool DBG, bool MAP>
 __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(WinArgs P) {
   // CAP ops per window on NT threads: (2048, 512) four windows per CU; (8192, 1024) one
   // window per CU for logs whose equal-timestamp groups need it (config 5)
   constexpr int ITEMS = CAP / NT, NCH = CAP / WAVE, WAVES = NT / WAVE, KP = (2 * CH + NT - 1) / NT;
-  // equal 32-bit rank keys resolved in the rank loop itself (the wide window, whose
-  // 8192-op groups see ~1 such pair in 128 and whose exact re-rank would be quadratic);
-  // the small windows flag them for the window re-rank (fewer registers in the loop)
-  constexpr bool TIEFIX = CAP > WF_CAP;
   static_assert(CAP % NT == 0 && NCH <= 2 * WAVE && CAP <= 65536, "window geometry");
-  __shared__ __attribute__((aligned(16))) u64 sts[CAP];  // element space: timestamps; later slot-space rank keys
-  __shared__ __attribute__((aligned(16))) u16 sord[CAP];  // S order (merge), later the final order
-  __shared__ u16 fin[CAP];        // slot -> element, later rename ranks
-  __shared__ u16 sl[CAP];         // element -> slot, later rank -> slot, later posl
-  __shared__ u8 skind[CAP];
-  __shared__ __attribute__((aligned(16))) u8 skS[CAP];  // kinds in S order, later by slot (steps 7-9)
+  constexpr int OW = CAP / 32;     // occupancy words over S positions
+  // sts: the timestamps by element (steps 1-2); the group counters, then starts (gcnt, steps
+  // 3-6); the members in bucket order (mkey, mel, steps 8-9); the payload by final slot
+  // (st_a, st_b, steps 11-14)
+  __shared__ __attribute__((aligned(16))) u64 sts[CAP];
+  __shared__ __attribute__((aligned(16))) u16 sord[CAP];  // final slot -> element (step 9 on)
+  __shared__ u32 bcnt[CAP / 2];   // bucket counters, then starts, two u16 per word (steps 1-9); then rown
+  __shared__ u16 sp[CAP];         // head element -> S position of its run (steps 2-4); later posl
+  __shared__ __attribute__((aligned(16))) u8 skS[CAP];  // kinds by final slot (step 9 on)
   __shared__ u16 inv[CAP];        // element -> final slot
   __shared__ u64 tbase[SMX_N_KINDS]; // T of a kind's slot x = tbase[kind] + x
-  __shared__ u64 gbits[NCH];       // group-start bits over slots, later candidate ballots
-  __shared__ u16 ccnt[NCH][SMX_N_KINDS];
-  __shared__ u16 rc[NCH][2];
-  __shared__ u32 kbase[SMX_N_KINDS + 1];
-  __shared__ u32 wck[SMX_N_KINDS];
+  __shared__ u64 gbits[NCH];       // run-head ballots per 64-op chunk (steps 2-4), later candidate ballots
+  __shared__ u32 occ[OW];          // bit s: a run starts at S position s (steps 1-4)
+  __shared__ u16 rc[NCH][2];      // per 64 renames: those of A, of B; then their exclusive prefixes
+  __shared__ u32 kbase[SMX_N_KINDS + 1];  // first final slot of each kind
+  __shared__ u32 wck[SMX_N_KINDS];        // the window's ops of each kind
   __shared__ u64 base[SMX_N_KINDS + 1];
   __shared__ u32 woffk[SMX_N_KINDS + 2];  // this window's offsets: kinds, renames of A, of B
   __shared__ u32 wtot[2];                 // the window's renames of A, of B
-  __shared__ u32 vbw[WAVES][3];        // per wave: value widths (addr, file, name)
-  u16* rown = fin;                    // rename rank within its branch (after step 5)
+  __shared__ u32 vbw[WAVES][3];        // per wave: value widths (addr, file, name); later the block scans' scratch
+  u16* rown = reinterpret_cast<u16*>(bcnt);  // rename rank within its branch (step 10 on)
 
   const int t = threadIdx.x;
   const int lane = t & (WAVE - 1);
@@ -376,7 +382,6 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     bad |= ok & ((kr >= SMX_N_KINDS) | (sym_r[i] >= (u64)P.n_sym));
     const u32 k = kr < SMX_N_KINDS ? kr : SMX_N_KINDS - 1;
     sts[e] = ts_r[i];
-    if constexpr (!RUNS) skind[e] = (u8)k;  // (the run-grouped order keeps the kinds in registers)
     const bool mv = ok & (k == KMOVE), rn = ok & (k == KREN);
     const bool ha = v0_r[i] >= 0, hf = v1_r[i] >= 0;
     sym_r[i] = (sym_r[i] & SYM_MASK) | ((mv & ha) ? MS_HAS_A : 0u) | ((mv & hf) ? MS_HAS_F : 0u);
@@ -394,17 +399,16 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     vbw[wv][2] = vb_c;
   }
   if (bad) P.meta->bad_sym = 1;
-  for (int i = t; i < NCH * SMX_N_KINDS; i += NT) (&ccnt[0][0])[i] = 0;
-  if constexpr (RUNS)  // the run-grouped order's bucket counters (fin is next written by step 6)
-    for (int i = t; i < CAP / 2; i += NT) reinterpret_cast<u32*>(fin)[i] = 0u;
+  static_assert(OW <= NT, "one occupancy word per thread");
+  if (t < OW) occ[t] = 0u;
+  for (int i = t; i < CAP / 2; i += NT) bcnt[i] = 0u;
   if (t <= SMX_N_KINDS) base[t] = base_v;
-  if (t < SMX_N_KINDS) wck[t] = 0;
   if (t < SMX_N_KINDS + 2) woffk[t] = woff_x + woff_y;
   if (t == 0) wtot[0] = failed != 0;
   __syncthreads();
-  if (wtot[0]) return;  // (wtot is written again in step 6)
+  if (wtot[0]) return;  // (wtot is written again in step 10)
   WSTAMP(1);
-  if (SMX_DIAG && (P.ablate & 16)) {  // diagnostics: load only (keeps every load live)
+  if (WF_ABL(16)) {  // diagnostics: load only (keeps every load live)
     u32 x = 0;
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) x += sym_r[i] + (u32)v0_r[i] + (u32)v1_r[i] + (u32)hi_r[i];
@@ -422,47 +426,18 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
   }
 
   const int nch = (sz + WAVE - 1) / WAVE;
-  auto group_of = [&](int p, int* gs_o, int* ge_o) {
-    const int bit = p & 63;
-    int wi = p >> 6;
-    u64 word = gbits[wi] & (bit == 63 ? ~0ull : ((1ull << (bit + 1)) - 1));
-    while (word == 0) word = gbits[--wi];
-    *gs_o = wi * 64 + 63 - __clzll(word);
-    wi = p >> 6;
-    word = bit == 63 ? 0ull : (gbits[wi] & ~((1ull << (bit + 1)) - 1));
-    while (word == 0 && ++wi < nch) word = gbits[wi];
-    const int ge = word ? wi * 64 + __ffsll((unsigned long long)word) - 1 : sz;
-    *ge_o = ge < sz ? ge : sz;
-  };
-  bool btie = false;  // two equal 32-bit keys in one group (steps 2-5: the exact re-rank below)
-  // ---- Run-grouped order (RUNS): no merge, no multisplit.  Inside a branch part the
-  // timestamps never decrease, so the equal-timestamp ops of both parts form one run of
-  // the merged order S, which starts at S position spos(v) = #{A ops < v} + #{B ops < v}
-  // (A first on ties, compose.py:54).  Each run's heads (the first op of its value in a
-  // part) find spos by a 64-way search of the other part; the runs' dense index r comes
-  // from an occupancy mask over S positions.  An op's group is (kind, r) and the
-  // groups laid out kind-major ARE the window's T order of groups (T is ordered by kind,
-  // then timestamp): one histogram + scan of KD * R counters gives every group's start,
-  // then each group is ordered by (id, side, index) with interpolation buckets (one op
-  // per bucket on random ids) and a rank inside the bucket, equal 32-bit keys on the
-  // full ids.  A window with more than GMAX groups (very many distinct timestamps) fails
-  // the plan as a window too large (f_fail 2): the host retries with smaller windows.
-  constexpr bool runs_ok = RUNS;
-  if constexpr (RUNS) {
-    constexpr int OW = CAP / 32;     // occupancy words over S positions
+  // steps 2-9: the window's order (the module comment); their LDS views and registers
+  // end with the scope
+  {
     constexpr int GMAX = 4 * CAP;    // group counters (u16, in sts once the timestamps are dead)
-    u32* occ = reinterpret_cast<u32*>(&ccnt[0][0]);  // (zeroed with ccnt before the load barrier)
-    static_assert(sizeof(ccnt) >= OW * sizeof(u32), "occupancy words inside ccnt");
-    __shared__ u16 occpre[OW];
+    __shared__ u16 occpre[OW];       // set bits before each occupancy word
     __shared__ u16 lasth[NCH];       // last head at or before the end of each 64-op chunk
     __shared__ u32 rinfo[2];         // groups fit, R
-    u16* sp = sl;                    // S position of each head's run (element space)
     u32* gcnt = reinterpret_cast<u32*>(sts);             // group counters, two u16 per word
     static_assert(GMAX / 2 * sizeof(u32) <= sizeof(sts), "group counters inside sts");
-    u32* bcnt = reinterpret_cast<u32*>(fin);             // bucket counters, two u16 per word (zeroed before the load barrier)
     u32* mkey = reinterpret_cast<u32*>(sts);             // bucket order: 32-bit keys (after the group starts are dead)
     u16* mel = reinterpret_cast<u16*>(reinterpret_cast<u32*>(sts) + CAP);  // ... and elements
-    // a. run heads, the order check, each head's run position
+    // 2. run heads, the order check, each head's run position
     bool dec = false;
     if (t == 0) {
       dec = (a0 > 0 && na > 0 && prev_a > sts[0]) || (b0 > 0 && nb > 0 && prev_b > sts[na]);
@@ -516,8 +491,9 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       if (t == 0) atomicOr((unsigned long long*)&P.meta->f_fail, 1ull);
       return;
     }
-    RX_EXIT(1);
-    // b. (wave 0) the last head of each chunk, the runs' dense index, the group count
+    WSTAMP(2);
+    WF_EXIT(2);
+    // 3. (wave 0) the last head of each chunk, the runs' dense index, the group count
     const u32 kpres = __builtin_amdgcn_readfirstlane(kmask_r);
     const int KD = __popc(kpres);
     const int kbits_r = 32 - __clz((int)(max(KD, 1) - 1));  // bits of a dense kind
@@ -556,10 +532,11 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       if (t == 0) atomicOr((unsigned long long*)&P.meta->f_fail, 2ull);
       return;
     }
-    RX_EXIT(2);
+    WSTAMP(3);
+    WF_EXIT(3);
     {
       const u32 R = rinfo[1];
-      // c. each op's run (its head: in its chunk, else the last head of the earlier
+      // 4. each op's run (its head: in its chunk, else the last head of the earlier
       //    chunks), group g = dense kind * R + run, counted
       const u64 lem = lanemask_lt() | (1ull << lane);
       u32 g_r[ITEMS];
@@ -599,8 +576,9 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
         }
       }
       __syncthreads();
-      RX_EXIT(3);
-      // d. group starts: exclusive scan of the KD * R counters (kind-major = T order), in
+      WSTAMP(4);
+      WF_EXIT(4);
+      // 5. group starts: exclusive scan of the KD * R counters (kind-major = T order), in
       //    passes of 4 * NT counters (one pass on config 3's windows: 6 kinds x 14 runs)
       const int GS = KD * (int)R;
       {
@@ -631,8 +609,9 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
         }
         kbase[t] = s;
       }
-      RX_EXIT(4);
-      // e. interpolation bucket inside the group: b = gs + (ge - gs) * key / 2^32
+      WSTAMP(5);
+      WF_EXIT(5);
+      // 6. interpolation bucket inside the group: b = gs + (ge - gs) * key / 2^32
       u32 b_r[ITEMS], ar_r[ITEMS];
 #pragma unroll
       for (int i = 0; i < ITEMS; ++i) {
@@ -645,8 +624,9 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
         ar_r[i] = (atomicAdd(&bcnt[b >> 1], 1u << (16 * (b & 1))) >> (16 * (b & 1))) & 0xffffu;
       }
       __syncthreads();
-      RX_EXIT(5);
-      // f. bucket starts
+      WSTAMP(6);
+      WF_EXIT(6);
+      // 7. bucket starts
       {
         constexpr int WPT = CAP / (2 * NT);
         u32 cw[WPT], sum = 0;
@@ -668,8 +648,9 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       auto bstart = [&](u32 b) -> u32 {
         return b < (u32)CAP ? (bcnt[b >> 1] >> (16 * (b & 1))) & 0xffffu : (u32)sz;
       };
-      RX_EXIT(6);
-      // g. members in bucket order: key and element
+      WSTAMP(7);
+      WF_EXIT(7);
+      // 8. members in bucket order: key and element
       u32 slot_r[ITEMS];
 #pragma unroll
       for (int i = 0; i < ITEMS; ++i) {
@@ -681,8 +662,9 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
         mel[s] = (u16)(t + NT * i);
       }
       __syncthreads();
-      RX_EXIT(7);
-      // h. rank inside the bucket on (key, full id, side, index); the final order
+      WSTAMP(8);
+      WF_EXIT(8);
+      // 9. rank inside the bucket on (key, full id, side, index); the final order
       //    (per-lane loops: one op per bucket on average; a wave-uniform loop over the
       //    ITEMS buckets together spilled registers)
 #pragma unroll
@@ -725,419 +707,29 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
         skS[f] = (u8)(k_r[i] < SMX_N_KINDS ? k_r[i] : SMX_N_KINDS - 1);
       }
       __syncthreads();
-      RX_EXIT(8);
+      WSTAMP(9);
+      WF_EXIT(9);
     }
   }
-  if constexpr (!RUNS) {  // steps 2-5: merge, multisplit, group order
-  // 2. merge A part [0,na) with B part [na,sz) by timestamp, A first on ties
-  //    (compose.py:54): merge path, ITEMS outputs per lane, with the kinds
-  //    copied into S order.  Presorted-layout check: every adjacent pair of each
-  //    branch log is non-decreasing (the pair straddling a window start is checked
-  //    here too); it shares the merge's barrier and a window that fails it discards
-  //    the merge.
-  bool dec = false;
-  if (t == 0) {
-    dec = (a0 > 0 && na > 0 && prev_a > sts[0]) || (b0 > 0 && nb > 0 && prev_b > sts[na]);
-    win_publish_widths(P.meta, &vbw[0][0], WAVES, vcur);
-  }
-#pragma unroll
-  for (int i = 0; i < ITEMS; ++i) {
-    const int e = t + NT * i;
-    if (e >= sz) continue;
-    if (!(SMX_DIAG && (P.ablate & 1)) && e != 0 && e != na && sts[e - 1] > ts_r[i]) dec = true;
-  }
-  {
-    const int d0 = t * ITEMS < sz ? t * ITEMS : sz;
-    const int d1 = d0 + ITEMS < sz ? d0 + ITEMS : sz;
-    int lo = d0 - nb > 0 ? d0 - nb : 0, hi = d0 < na ? d0 : na;
-    // (a fixed count of predicated halving steps measured slower: window 1.225 -> 1.270 ms,
-    //  profiles/r03_x/ab_merge_search_fixed_steps.txt)
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (sts[mid] <= sts[na + d0 - 1 - mid]) lo = mid + 1;
-      else hi = mid;
-    }
-    int ia = lo, ib = d0 - lo;
-    // ITEMS outputs, predicated (a thread past sz stores nothing)
-#pragma unroll
-    for (int u = 0; u < ITEMS; ++u) {
-      const int d = d0 + u;
-      const u64 ta = sts[ia < na ? ia : 0], tb = sts[na + (ib < nb ? ib : 0)];
-      const bool take_a = ia < na && (ib >= nb || ta <= tb);
-      const int e = take_a ? ia : na + ib;
-      ia += take_a ? 1 : 0;
-      ib += take_a ? 0 : 1;
-      if (d < d1) {
-        sord[d] = (u16)e;
-        skS[d] = skind[e];
-      }
-    }
-  }
-  if (__syncthreads_or(dec)) {
-    if (t == 0) atomicOr((unsigned long long*)&P.meta->f_fail, 1ull);
-    return;
-  }
-  WSTAMP(3);
-  WF_EXIT(2);
-
-  // 3. stable multisplit of S by rank (wave ballots); element, kind and rank stay in
-  //    registers for the scatter (m = t + NT * j is chunk wv + WAVES * j)
-  int me[ITEMS];
-  u32 mkr[ITEMS];  // kind | rank << 8
-#pragma unroll
-  for (int j = 0; j < ITEMS; ++j) {
-    const int m = t + NT * j;
-    me[j] = m < sz ? sord[m] : 0;
-    mkr[j] = m < sz ? skS[m] : 0u;
-  }
-  const u64 ltm = lanemask_lt();
-  // the ballots run over the dense index of the kinds present in the merge (k_khist's
-  // kind masks): 6 kinds take 3 ballots instead of 5
-  const u32 kpres = __builtin_amdgcn_readfirstlane(kmask_r);
-  const int kbits = 32 - __clz((int)(max(__popc(kpres), 1u) - 1u));
-#pragma unroll
-  for (int j = 0; j < ITEMS; ++j) {
-    const int m = t + NT * j;
-    const int c = wv + WAVES * j;
-    const bool valid = m < sz;
-    const u32 k = mkr[j];
-    const u64 peers = wave_peers_n((u32)__popc(kpres & ((1u << k) - 1u)), valid, kbits);
-    const u32 r = __popcll(peers & ltm);
-    mkr[j] = k | (r << 8);
-    if (valid && r == 0) {
-      ccnt[c][k] = (u16)__popcll(peers);
-      atomicAdd(&wck[k], (u32)__popcll(peers));
-    }
-  }
-  __syncthreads();
-  WSTAMP(4);
-  WF_EXIT(3);
-  for (int k = wv; k < SMX_N_KINDS; k += WAVES) {
-    u32 carry = 0;
-#pragma unroll
-    for (int c0 = 0; c0 < NCH; c0 += WAVE) {  // (one pass when NCH <= 64)
-      const int c = c0 + lane;
-      const u32 x = c < nch ? ccnt[c][k] : 0u;
-      const u32 inc = wave_incl_sum(x);
-      if (c < nch) ccnt[c][k] = (u16)(carry + inc - x);
-      if (NCH > WAVE) carry += (u32)__builtin_amdgcn_readlane((int)inc, WAVE - 1);
-    }
-  }
-  if (wv == WAVES - 1) {  // (kinds 7 and 15 only on this wave)
-    const u32 x = lane < SMX_N_KINDS ? wck[lane] : 0u;
-    const u32 inc = wave_incl_sum(x);
-    if (lane < SMX_N_KINDS) kbase[lane] = inc - x;
-    if (lane == SMX_N_KINDS - 1) kbase[SMX_N_KINDS] = inc;
-  }
-  __syncthreads();
-  WSTAMP(6);
-  WF_EXIT(4);
-#pragma unroll
-  for (int j = 0; j < ITEMS; ++j) {
-    const int m = t + NT * j;
-    if (m < sz) {
-      const u32 k = mkr[j] & 0xffu;
-      const int p = kbase[k] + ccnt[wv + WAVES * j][k] + (mkr[j] >> 8);
-      fin[p] = (u16)me[j];
-      sl[me[j]] = (u16)p;
-      skS[p] = (u8)k;  // (skS was read in the prologue, before two barriers)
-    }
-  }
-  __syncthreads();
-  WSTAMP(7);
-  WF_EXIT(5);
-
-  // 4. group-start bits (a group = equal (rank, timestamp), contiguous in slots),
-  //    then the timestamps are dead and their buffer takes the slot-space oid prefix
-#pragma unroll
-  for (int j = 0; j < ITEMS; ++j) {
-    const int p = t + NT * j;
-    bool f = false;
-    if (p < sz) {
-      const int e = fin[p];
-      f = (p == (int)kbase[skS[p]]) || (sts[fin[p - 1]] != sts[e]);  // (skS: kinds by slot)
-    }
-    const u64 b = __ballot(f);
-    if (lane == 0 && (p >> 6) < NCH) gbits[p >> 6] = b;
-  }
-  __syncthreads();
-  WSTAMP(8);
-  WF_EXIT(6);
-  // slot-space rank keys: the top 32 bits of oid_hi; sl is reset to "no slot" for
-  // the rank phase's collision check
-  u32* pkey = (u32*)sts;
-#pragma unroll
-  for (int i = 0; i < ITEMS; ++i) {
-    const int e = t + NT * i;
-    if (e < sz) {
-      const int p = sl[e];
-      pkey[p] = hi_r[i];
-      sl[e] = 0xffffu;
-    }
-  }
-  // step 5's bucket counters (the upper half of sts: the timestamps are dead)
-  for (int i = t; i < CAP / 2; i += NT) reinterpret_cast<u32*>(sts)[CAP + i] = 0u;
-  __syncthreads();
-  WSTAMP(9);
-  WF_EXIT(7);
-
-  // 5. order each group by (oid, side, index): interpolation buckets over the group on
-  //    the 32-bit keys, then a rank inside each bucket.  Two keys of a group that are
-  //    equal (about one window in 10^4 on random ids; every duplicate id) are flagged
-  //    (btie): such a window is re-ranked exactly on (oid_hi, oid_lo, slot) -- slot
-  //    order is (side, index) order inside a group (the wide window resolves them in
-  //    the rank loop itself: TIEFIX).
-  // the group bounds of a wave's 64 consecutive slots from one read of every
-  // group-start word (nch <= 32) and lane broadcasts: no dependent LDS chain
-  // (NCH > 64: a second word per lane, gw1 / gnz1 for chunks 64..127)
-  const u64 gw = lane < nch ? gbits[lane] : 0ull;
-  const u64 gnz = __ballot(gw != 0);
-  const u64 gw1 = NCH > WAVE && WAVE + lane < nch ? gbits[(WAVE + lane) % NCH] : 0ull;
-  const u64 gnz1 = NCH > WAVE ? __ballot(gw1 != 0) : 0ull;
-  auto bcast64 = [](u64 v, int l) -> u64 {
-    return (u64)(u32)__builtin_amdgcn_readlane((int)(u32)v, l) |
-           ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), l) << 32);
-  };
-  // group-start word i (wave-uniform i < NCH), with the whole wave active
-  auto gword = [&](int i) -> u64 {
-    if (NCH <= WAVE) return bcast64(gw, i);
-    const u64 a = bcast64(gw, i & (WAVE - 1)), b = bcast64(gw1, i & (WAVE - 1));
-    return i < WAVE ? a : b;
-  };
-  const u64 le_mask = lanemask_lt() | (1ull << lane);
-  // interpolation buckets over slot space: slot p of group [gs, ge) goes to bucket
-  // gs + (ge - gs) * key / 2^32 (one op per bucket on random ids); 16-bit counters,
-  // two per word, in the upper half of sts (free until step 7)
-  u32* bcnt = reinterpret_cast<u32*>(sts) + CAP;
-  // the top 16 bits of each key in bucket order (the last quarter of sts): the rank
-  // loop compares them without the slot -> key chain, the full key only on a tie
-  u16* bk16 = reinterpret_cast<u16*>(reinterpret_cast<u32*>(sts) + CAP + CAP / 2);
-  u32 own_r[ITEMS];
-  u32 bk_r[ITEMS];
-  u32 kp_r[ITEMS];
-  u32 ar_r[ITEMS];  // arrival rank inside the bucket (the count atomic's return value)
-#pragma unroll
-  for (int j = 0; j < ITEMS; ++j) bk_r[j] = 0xffffffffu, kp_r[j] = 0u;
-#pragma unroll
-  for (int j = 0; j < ITEMS; ++j) {
-    const int wi = __builtin_amdgcn_readfirstlane((NT * j) / WAVE + wv);  // this wave's slot chunk
-    if (wi >= nch) break;  // wave-uniform
-    const int p = wi * WAVE + lane;
-    // Group bounds, branch-free: every lane broadcast (v_readlane) runs with the whole
-    // wave active.  (Lane reads inside the lanes' divergent branches mis-ordered groups
-    // in some builds: a register's value in lanes outside the branch is not defined.)
-    // The last group start before the chunk and the first one after it are scalar.
-    const u64 W = gword(wi);
-    int wp, wn;
-    bool has_next;
-    if (NCH <= WAVE) {
-      const u64 prevm = gnz & ((1ull << wi) - 1);  // (slot 0 always starts a group)
-      wp = prevm ? 63 - __clzll(prevm) : 0;
-      const u64 nxtm = wi + 1 < WAVE ? gnz & ~((2ull << wi) - 1) : 0ull;
-      has_next = nxtm != 0;
-      wn = nxtm ? __ffsll((unsigned long long)nxtm) - 1 : 0;
-    } else {
-      // the last non-empty word before wi and the first after it, over 128 words
-      const int wl = wi & (WAVE - 1);
-      const u64 below0 = wi < WAVE ? gnz & ((1ull << wl) - 1) : gnz;
-      const u64 below1 = wi < WAVE ? 0ull : gnz1 & ((1ull << wl) - 1);
-      wp = below1 ? WAVE + 63 - __clzll(below1) : (below0 ? 63 - __clzll(below0) : 0);
-      const u64 above0 = wi < WAVE ? (wl + 1 < WAVE ? gnz & ~((2ull << wl) - 1) : 0ull) : 0ull;
-      const u64 above1 = wi < WAVE ? gnz1 : (wl + 1 < WAVE ? gnz1 & ~((2ull << wl) - 1) : 0ull);
-      has_next = (above0 | above1) != 0;
-      wn = above0 ? __ffsll((unsigned long long)above0) - 1
-                  : (above1 ? WAVE + __ffsll((unsigned long long)above1) - 1 : 0);
-    }
-    const int prevS = wp * WAVE + 63 - __clzll(gword(wp) | 1ull);
-    const u64 Wn = gword(wn);
-    const int nextS = has_next ? wn * WAVE + __ffsll((unsigned long long)(Wn | (1ull << 63))) - 1 : sz;
-    const u64 below = W & le_mask, above = W & ~le_mask;
-    const int gs = below ? wi * WAVE + 63 - __clzll(below | 1ull) : prevS;
-    int ge = above ? wi * WAVE + __ffsll((unsigned long long)(above | (1ull << 63))) - 1 : nextS;
-    ge = ge < sz ? ge : sz;
-    if (p < sz) {
-      const u32 kp = pkey[p];
-      const u32 b = (u32)gs + (u32)(((u64)(u32)(ge - gs) * kp) >> 32);
-      kp_r[j] = kp;
-      bk_r[j] = b;
-      ar_r[j] = (atomicAdd(&bcnt[b >> 1], 1u << (16 * (b & 1))) >> (16 * (b & 1))) & 0xffffu;
-    }
-  }
-  {
-    __syncthreads();
-    // exclusive scan of the CAP counters: CAP / NT per thread (two 16-bit ones per word)
-    constexpr int WPT = CAP / (2 * NT);
-    u32 cw[WPT], sum = 0;
-#pragma unroll
-    for (int i = 0; i < WPT; ++i) {
-      cw[i] = bcnt[WPT * t + i];
-      sum += (cw[i] & 0xffffu) + (cw[i] >> 16);
-    }
-    u32 tot;
-    u32 run = block_excl_scan<OpSum, u32, WAVES>(sum, &vbw[0][0], &tot);  // (vbw is dead after step 2)
-#pragma unroll
-    for (int i = 0; i < WPT; ++i) {
-      const u32 c0 = cw[i] & 0xffffu, c1 = cw[i] >> 16;
-      bcnt[WPT * t + i] = run | ((run + c0) << 16);
-      run += c0 + c1;
-    }
-    __syncthreads();
-    // scatter the slots into their buckets (sl: bucket position -> slot); the counters
-    // stay the bucket starts (position = start + arrival rank, no second atomic)
-    u32 lo_r[ITEMS];
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-      const u32 b = bk_r[j];
-      lo_r[j] = 0;
-      if (b == 0xffffffffu) continue;
-      const u32 sh = 16 * (b & 1);
-      lo_r[j] = (bcnt[b >> 1] >> sh) & 0xffffu;
-      const u32 pos = lo_r[j] + ar_r[j];
-      sl[pos] = (u16)((NT * j) / WAVE * WAVE + wv * WAVE + lane);
-      own_r[j] = pos;
-      bk16[pos] = (u16)(kp_r[j] >> 16);
-    }
-    __syncthreads();
-    // rank inside the bucket on the 32-bit key
-    int rr[ITEMS];
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-      const u32 b = bk_r[j];
-      rr[j] = -1;
-      if (b == 0xffffffffu) continue;
-      // bucket [start(b), start(b + 1)); the starts are an exclusive scan over every
-      // bucket of the window (buckets past the last slot start at the total)
-      const u32 lo = lo_r[j];
-      const u32 e = b + 1 < (u32)CAP ? (bcnt[(b + 1) >> 1] >> (16 * ((b + 1) & 1))) & 0xffffu : (u32)sz;
-      const u32 kp = kp_r[j];
-      u32 c = 0, eq = 1;
-      const u32 k16 = kp >> 16, own = own_r[j];
-      for (u32 q = lo; q < e; ++q) {
-        const u32 x = bk16[q];
-        if (q == own) continue;
-        if (x != k16) {
-          c += x < k16;
-        } else {  // equal top halves: the full keys (rare)
-          const u32 k = pkey[sl[q]];
-          if (!TIEFIX || k != kp) {
-            c += k < kp;
-            eq += k == kp;
-          } else {
-            // equal 32-bit keys (duplicate ids; ~1 pair in 2^33 per group on random
-            // ids): the full ids, then slot order -- (side, index) order in a group
-            const int pm = (NT * j) / WAVE * WAVE + wv * WAVE + lane, po = sl[q];
-            const int em = fin[pm], eo = fin[po];
-            const i64 jm = em < na ? a0 + em : bld + em, jo = eo < na ? a0 + eo : bld + eo;
-            const u64 hm = P.khi[jm], ho = P.khi[jo], lm = P.klo[jm], lo2 = P.klo[jo];
-            c += ho < hm || (ho == hm && (lo2 < lm || (lo2 == lm && po < pm)));
-          }
-        }
-      }
-      btie |= eq > 1;
-      rr[j] = (int)(lo + c);
-      if (!DBG) {
-        // the final order at once: nothing in this loop reads sord or inv, and the
-        // rank -> slot map is not needed after step 5 (the exact re-rank rebuilds it)
-        const int e = fin[(NT * j) / WAVE * WAVE + wv * WAVE + lane];
-        sord[rr[j]] = (u16)e;
-        inv[e] = (u16)rr[j];
-      }
-    }
-    if (DBG) {
-      __syncthreads();
-#pragma unroll
-      for (int j = 0; j < ITEMS; ++j) {
-        if (rr[j] < 0) continue;
-        const int p = (NT * j) / WAVE * WAVE + wv * WAVE + lane;
-        const int e = fin[p];
-        sord[rr[j]] = (u16)e;
-        sl[rr[j]] = (u16)p;  // sl maps rank -> slot (the diagnostic order check)
-        inv[e] = (u16)rr[j];
-      }
-    }
-  }
-  __syncthreads();
-  if (DBG) {  // diagnostics: the group order against the slot-space keys (dbg words 5, 17, 18)
-    for (int r = t + 1; r < sz; r += NT) {
-      const bool start = (gbits[r >> 6] >> (r & 63)) & 1ull;
-      if (!start && pkey[sl[r - 1]] > pkey[sl[r]]) atomicAdd((unsigned long long*)&P.dbg[w * WF_NSTAMP + 5], 1ull);
-      if (!start && sts[0] == 0x12345ull) P.meta->dup_key = 3;  // (keeps sts live)
-    }
-    for (int r = t; r < sz; r += NT) {
-      const int p0 = sl[r];
-      if (p0 >= sz) atomicAdd((unsigned long long*)&P.dbg[w * WF_NSTAMP + 17], 1ull);
-      else if (fin[p0] != sord[r]) atomicAdd((unsigned long long*)&P.dbg[w * WF_NSTAMP + 18], 1ull);
-    }
-  }
-  WSTAMP(10);
-  WF_EXIT(8);
-  }  // (!RUNS)
-  // 6. renames: rank among the window's renames of the same branch (final order).
-  //    Computed in the collision-check phase into registers (rown aliases fin, which
-  //    the exact re-rank still reads) and stored once no tie is known; redone after a
-  //    (rare) exact re-rank.
+  // 10. renames: rank among the window's renames of the same branch (final order), the
+  //     renames per branch of each 64 (rc) and, on wave 0, rc's exclusive scan.  (rown
+  //     takes the bucket counters' place: step 9 read them last, before its barrier.)
   const int R0 = kbase[KREN], RN = wck[KREN];
   const int nrc = (RN + WAVE - 1) / WAVE;
-  constexpr int RQ = (NCH + WAVES - 1) / WAVES;  // rename chunks per wave
-  u32 rown_r[RQ];
-  auto rename_ranks = [&](bool store) {
-#pragma unroll
-    for (int q = 0; q < RQ; ++q) {
-      const int c = wv + q * WAVES;
-      rown_r[q] = 0;
-      if (c >= nrc) continue;  // wave-uniform
-      const int x = c * WAVE + lane;
-      const bool valid = x < RN;
-      const int e = valid ? sord[R0 + x] : 0;
-      const bool sb = valid && e >= na;
-      const u64 bm = __ballot(sb), vm = __ballot(valid);
-      const u64 lt = lanemask_lt();
-      rown_r[q] = (u32)(sb ? __popcll(bm & lt) : __popcll(vm & ~bm & lt));
-      if (store && valid) rown[x] = (u16)rown_r[q];
-      if (lane == 0) {
-        rc[c][0] = (u16)__popcll(vm & ~bm);
-        rc[c][1] = (u16)__popcll(bm);
-      }
-    }
-  };
-  rename_ranks(false);
-  const bool any_tie = __syncthreads_or(btie);
-  WSTAMP(21);
-  if (any_tie) {
-    // exact ranks from the full ids (global memory; rare)
-    for (int p = t; p < sz; p += NT) {
-      int gs, ge;
-      group_of(p, &gs, &ge);
-      const int ex = fin[p];
-      const i64 jx = ex < na ? a0 + ex : bld + ex;
-      const u64 hx = P.khi[jx], lx = P.klo[jx];
-      int c = 0;
-      for (int q = gs; q < ge; ++q) {
-        if (q == p) continue;
-        const int ey = fin[q];
-        const i64 jy = ey < na ? a0 + ey : bld + ey;
-        const u64 hy = P.khi[jy], ly = P.klo[jy];
-        c += hy < hx || (hy == hx && (ly < lx || (ly == lx && q < p)));
-      }
-      sl[gs + c] = (u16)p;
-    }
-    __syncthreads();
-    for (int r = t; r < sz; r += NT) {
-      const int e = fin[sl[r]];
-      sord[r] = (u16)e;
-      inv[e] = (u16)r;
-    }
-    __syncthreads();
-    rename_ranks(true);
-    __syncthreads();
-  } else {
-#pragma unroll
-    for (int q = 0; q < RQ; ++q) {  // fin is dead now: the ranks go to rown
-      const int x = (wv + q * WAVES) * WAVE + lane;
-      if (wv + q * WAVES < nrc && x < RN) rown[x] = (u16)rown_r[q];
+  for (int c = wv; c < nrc; c += WAVES) {
+    const int x = c * WAVE + lane;
+    const bool valid = x < RN;
+    const int e = valid ? sord[R0 + x] : 0;
+    const bool sb = valid && e >= na;
+    const u64 bm = __ballot(sb), vm = __ballot(valid);
+    const u64 lt = lanemask_lt();
+    if (valid) rown[x] = (u16)(sb ? __popcll(bm & lt) : __popcll(vm & ~bm & lt));
+    if (lane == 0) {
+      rc[c][0] = (u16)__popcll(vm & ~bm);
+      rc[c][1] = (u16)__popcll(bm);
     }
   }
-  WSTAMP(11);
+  __syncthreads();
   if (wv == 0) {
     u32 c0s = 0, c1s = 0;  // carries over 64-chunk passes
 #pragma unroll
@@ -1160,15 +752,15 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
   }
   if (none_mv) atomicAdd((unsigned long long*)&P.meta->n_move_none, (unsigned long long)none_mv);
   __syncthreads();
-  WSTAMP(12);
-  WF_EXIT(9);
+  WSTAMP(10);
+  WF_EXIT(10);
 
-  // 7. payload by element, round 1: sym (| the move's has-value bits) and v0; the
-  //    position of each rename in its branch's list (posl)
-  if (SMX_DIAG && (P.ablate & 4)) return;
+  // 11. payload by element, round 1: sym (| the move's has-value bits) and v0; the
+  //     position of each rename in its branch's list (posl)
+  if (WF_ABL(4)) return;
   u32* st_a = (u32*)sts;             // [CAP] sym | flags
   i32* st_b = (i32*)sts + CAP;   // [CAP] v0, then v1
-  u16* posl = sl;
+  u16* posl = sp;                    // (the run positions are dead since step 4)
   // by final slot: each element's owner stores its payload at inv[element]
   int xi[ITEMS];
 #pragma unroll
@@ -1192,10 +784,9 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     P.wren[2 * w + 1] = woffk[CNT_REN_A];
   }
   __syncthreads();
-  WSTAMP(13);
-  WF_EXIT(10);
-  RX_EXIT(9);
-  // 8. natural-head DivergentRename flags -> candidate slots; window exports
+  WSTAMP(11);
+  WF_EXIT(11);
+  // 12. natural-head DivergentRename flags -> candidate slots; window exports
   win_rename_flags<NT, NCH>(
       P, w, woffk[KREN], RN, cntA, cntB, posl, gbits,
       [&](int x, int* s, int* own) {
@@ -1206,12 +797,11 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
       [&](int x) -> uint2 {
         return make_uint2(st_a[R0 + x] & SYM_MASK, (u32)st_b[R0 + x]);
       });
-  WSTAMP(14);
-  WF_EXIT(11);
-  RX_EXIT(10);
+  WSTAMP(12);
+  WF_EXIT(12);
 
-  // 9. T-ordered records in final order (consecutive lanes -> consecutive T inside
-  //    each kind: coalesced)
+  // 13. T-ordered records in final order (consecutive lanes -> consecutive T inside
+  //     each kind: coalesced)
   const u64 nall = (u64)(P.na + P.nb);
   const u64 nmv = base[KREN];
   // four consecutive slots per thread (CAP = 4 * NT): one LDS read of each array,
@@ -1279,9 +869,9 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
     }
   }
   __syncthreads();
-  WSTAMP(15);
-  WF_EXIT(12);
-  // round 2: v1 -> the move's newFile, the rename's chain value
+  WSTAMP(13);
+  WF_EXIT(13);
+  // 14. round 2: v1 -> the move's newFile, the rename's chain value
 #pragma unroll
   for (int i = 0; i < ITEMS; ++i)
     if (xi[i] < CAP && k_r[i] <= KREN) st_b[xi[i]] = v1_r[i];
@@ -1308,7 +898,7 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
   }
   if (DBG) {
     __syncthreads();
-    WSTAMP(16);
+    WSTAMP(14);
   }
 }
 

@@ -329,9 +329,10 @@ def test_compose_json_matches_dropin():
 @pytest.mark.parametrize("frac,dup", [(0.3, False), (1.0, True)])
 def test_gpu_presorted_id_prefix_ties(frac, dup):
     """Ops whose ids share their top 32 bits (and, with dup, whole ids) inside equal-
-    (kind, timestamp) groups: the presorted window's 32-bit group rank collides and the
-    window re-ranks exactly on the full ids -- with the renames' ranks computed around
-    it (a window with ties and renames)."""
+    (kind, timestamp) groups: they fall into one interpolation bucket of their group with
+    equal 32-bit keys, and the presorted window's rank inside the bucket (its step 9)
+    orders them on the full ids, then (side, index) -- in windows that also hold renames,
+    whose ranks are taken from that order."""
     soa = synth.lift_soa(synth.lift_logs(synth.LiftSpec(300_000, 3_000, 21)))
     rng = np.random.default_rng(5)
     sel = rng.random(soa.n) < frac

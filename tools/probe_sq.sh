@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ / TA / TCP counter passes over K compose merges (tools/compose_runs.py, kernel trace
-# only, one rocprofv3 run per counter group) and the window-phase ablations of a
-# diagnostic build.  Run on the GPU box from the repo root:
+# only, one rocprofv3 run per counter group) and the window kernel's step exits in a
+# diagnostic build (tools/window_ablate.py).  Run on the GPU box from the repo root:
 #   bash tools/probe_sq.sh OUTDIR [groups...]      groups: sq1 sq2 ta list ablate
 set -o pipefail
 R=$PWD

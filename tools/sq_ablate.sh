@@ -1,6 +1,7 @@
 #!/bin/bash
-# SQ instruction counters of k_window_f per phase exit (diagnostic build, SMX_ABLATE):
-#   bash tools/sq_ablate.sh OUTDIR LIB "16 121 122 ... 0"
+# SQ instruction counters of k_window_f per step exit (diagnostic build, SMX_ABLATE: 16 = load
+# only, 100 + N = leave after step N = 2 .. 13 of smx_window.h, 0 = the whole kernel):
+#   bash tools/sq_ablate.sh OUTDIR LIB "16 102 103 ... 113 0"
 # one rocprofv3 --pmc pass per value, 2 merges of a 20M-op config-3-shaped log each
 set -o pipefail
 R=$PWD

@@ -1,8 +1,8 @@
 """Window-kernel ablation (diagnostic build, SMX_LIB=<-DSMX_DIAG=1 build>): time
 k_window_f variants in ONE process, interleaved rounds (cdna_hip_programming.md §5.4
-rule 24).  SMX_ABLATE = 16: load only; 100 + N: leave after phase N (smx_window.h
-WF_EXIT), so phase N costs exitN - exit(N-1).  Results of ablated runs are invalid by
-design; only the window stage time is read."""
+rule 24).  SMX_ABLATE = 16: load only (step 1); 100 + N: leave after step N = 2 .. 13
+(smx_window.h WF_EXIT), so step N costs exitN - exit(N-1) and step 14 base - exit13.
+Results of ablated runs are invalid by design; only the window stage time is read."""
 import os
 import sys
 
@@ -20,10 +20,10 @@ def main():
     soa = synth.lift_soa(synth.lift_logs(spec))
     dc = _lib.DeviceCompose(soa)
     lib = _lib.lib()
-    names = {2: "merge", 3: "ksplit", 4: "kscan", 5: "kscatter", 6: "gbits", 7: "pkey", 8: "bucket",
-             9: "renrank", 10: "posl", 11: "flags", 12: "out1"}
-    variants = [("base", {}), ("loadonly", {"SMX_ABLATE": "16"})] + \
-        [(f"exit{k:02d}_{v}", {"SMX_ABLATE": str(100 + k)}) for k, v in names.items()]
+    names = {2: "heads", 3: "runindex", 4: "groupcount", 5: "groupscan", 6: "buckets", 7: "bucketscan",
+             8: "members", 9: "rank", 10: "renrank", 11: "posl", 12: "flags", 13: "out1"}
+    variants = [("loadonly", {"SMX_ABLATE": "16"})] + \
+        [(f"exit{k:02d}_{v}", {"SMX_ABLATE": str(100 + k)}) for k, v in names.items()] + [("base", {})]
     res = {k: [] for k, _ in variants}
     for rnd in range(4):
         for name, env in variants:
@@ -43,7 +43,7 @@ def main():
             res[name].append(ms / max(calls, 1))
             tot = sum(v[0] for v in st.values()) / 5
             if rnd == 3:
-                print(f"{name:10s} window {np.median(res[name]):.3f} ms  (min {min(res[name]):.3f})"
+                print(f"{name:17s} window {np.median(res[name]):.3f} ms  (min {min(res[name]):.3f})"
                       f"  all-stages {tot:.3f} ms", flush=True)
 
 

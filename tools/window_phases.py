@@ -1,6 +1,8 @@
-"""Per-phase latency of k_window_f (diagnostic build path k_window_f<true>): lane 0 of
-each workgroup stamps s_memtime after every barrier; this prints the mean cycles of
-each phase per window, and the window-kernel time with and without stamping."""
+"""Per-step latency of k_window_f (diagnostic build, SMX_LIB=<-DSMX_DIAG=1 build>: the
+k_window_f<CAP, NT, true, false> instances, the shipped order with stamps): lane 0 of each
+workgroup stamps s_memtime at its start and after every step (smx_window.h, WSTAMP); this
+prints the mean cycles of each step per window, and the window-kernel time with and without
+stamping.  usage: window_phases.py [n_ops] [config]"""
 import ctypes
 import os
 import sys
@@ -9,12 +11,11 @@ import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-NST = 24
-NAMES = {0: "start", 1: "load", 3: "check+merge", 4: "msplit", 6: "ccnt-scan",
-         7: "scatter", 8: "gbits", 9: "keys", 10: "rank", 21: "tiechk+renrank",
-         11: "tiefix", 12: "rc-scan", 13: "stage1+posl", 14: "flags+cand", 15: "write1",
-         16: "stage2+write2"}
-ORDER = [0, 1, 3, 4, 6, 7, 8, 9, 10, 21, 11, 12, 13, 14, 15, 16]
+NST = 16  # WF_NSTAMP
+# stamp i is taken after step i of smx_window.h (0: the window's start)
+NAMES = ["start", "load", "heads", "run-index", "group-count", "group-scan", "buckets", "bucket-scan",
+         "members", "rank", "renrank", "stage1+posl", "flags+cand", "write1", "stage2+write2"]
+LAST = len(NAMES) - 1
 
 
 def main():
@@ -29,15 +30,15 @@ def main():
     W = n // 256 + 16
     buf = torch.zeros(W * NST, dtype=torch.int64, device="cuda")
 
-    def timed(reps=5):
+    def timed(reps=5):  # the normal and the wide windows' stage (a log runs one of them to the end)
         lib.smx_reset_stage_times()
         lib.smx_set_profiling(1)
         for _ in range(reps):
             dc.run()
         torch.cuda.synchronize()
         lib.smx_set_profiling(0)
-        ms, calls = _lib.stage_times()["window"]
-        return ms / max(calls, 1)
+        st = _lib.stage_times()
+        return (st["window"][0] + st["window_wide"][0]) / reps
 
     dc.run()
     print(f"window plain   {timed():.3f} ms  (median of 3: {sorted(timed() for _ in range(3))[1]:.3f})")
@@ -53,17 +54,17 @@ def main():
     torch.cuda.synchronize()
     lib.smx_debug_phase_buffer(None, ctypes.c_size_t(0))
     a = buf.cpu().numpy().reshape(-1, NST)
-    a = a[a[:, 16] != 0]
+    a = a[a[:, LAST] != 0][:, :LAST + 1]  # (a window of a failed plan leaves before its last stamp)
     print(f"{len(a)} windows stamped")
-    tot = (a[:, 16] - a[:, 0]).mean()
-    prev = 0
-    for i in ORDER[1:]:
-        d = (a[:, i] - a[:, prev]).mean()
-        print(f"  {NAMES[i]:10s} {d:9.0f} cyc  {100 * d / tot:5.1f}%")
-        prev = i
-    print(f"  {'total':10s} {tot:9.0f} cyc per window (lane-0 view)")
+    ok = (a != 0).all(axis=1) & (np.diff(a, axis=1) >= 0).all(axis=1)
+    print(f"stamps non-zero and non-decreasing in step order: {int(ok.sum())} of {len(a)} windows")
+    tot = (a[:, LAST] - a[:, 0]).mean()
+    for i in range(1, LAST + 1):
+        d = (a[:, i] - a[:, i - 1]).mean()
+        print(f"  {i:2d} {NAMES[i]:13s} {d:9.0f} cyc  {100 * d / tot:5.1f}%")
+    print(f"  {'total':16s} {tot:9.0f} cyc per window (lane-0 view)")
     st = np.sort(a[:, 0])
-    print(f"  window start span {(st[-1] - st[0]):.0f} cyc; concurrent ~ {tot * len(a) / (a[:, 16].max() - st[0]):.0f} windows")
+    print(f"  window start span {(st[-1] - st[0]):.0f} cyc; concurrent ~ {tot * len(a) / (a[:, LAST].max() - st[0]):.0f} windows")
 
 
 if __name__ == "__main__":
