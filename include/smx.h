@@ -16,6 +16,8 @@
  *                    looks at first), for many pairs of logs, from the logs' renames
  *   smx_rga_replay <- semmerge/crdt.py:23-57  RGA.insert/move/delete/materialize,
  *                    batched over many independent lists
+ *   smx_rga_replay_onto <- the same, for many event streams replayed onto base lists that
+ *                    are stored once (RGA._fold's shape, many branches per base list)
  *
  * Plain C types only.  All device pointers are HIP device (or managed) memory
  * owned by the caller; the library never allocates: temporary space comes from a
@@ -723,6 +725,58 @@ int smx_rga_replay(const smx_rga_ops* ops, const smx_rga_out* out, void* workspa
 #define SMX_RGA_GROUPED 1u
 int smx_rga_replay_ex(const smx_rga_ops* ops, const smx_rga_out* out, void* workspace,
                       size_t workspace_bytes, uint32_t flags, void* stream);
+
+/*
+ * RGA replay of many jobs onto base lists stored once (a merge queue, a rebase, a
+ * three-way list reconcile: the same base list takes many branches' events).  The events
+ * of job j are the events of base job_base[j] followed by the job's own events, in stream
+ * order, and the job's results are exactly those of smx_rga_replay on that concatenated
+ * stream as one list, in both output modes -- but a base's events are stored, copied and
+ * read from one place however many jobs name it.
+ *   base_off  [n_bases + 1]: base b's events are columns [base_off[b], base_off[b + 1])
+ *   own_off   [n_jobs + 1]:  job j's own events are columns [own_off[j], own_off[j + 1])
+ *   job_base  [n_jobs]:      a base index < n_bases, or SMX_NONE for a job without a base
+ *   op .. opid_lo            the event columns of smx_rga_ops, n_total entries each; values,
+ *                            anchors and authors form one id domain for the whole call (an
+ *                            own move or delete reaches a base element of the same value id)
+ * The bases lie before the own events: base_off[n_bases] <= own_off[0].  The creation index
+ * that breaks ties between equal keys is the column index, so a base's elements come before
+ * a job's own and, among own events, column order decides.  A base named by no job is never
+ * read; jobs may name their bases in any order; a base or an own range may be empty.
+ * Output: smx_rga_out with one "list" per job: out_offsets has n_jobs + 1 entries,
+ * out_value / out_src / out_tomb have capacity n_out (at least the sum over the jobs of
+ * their base's and their own events), out_src[k] is the COLUMN index of the event that
+ * created element k (a base's or an own one), counts[0] the total.
+ * Stream-ordered on `stream`; ends, as smx_rga_replay does, with the read-back of one
+ * error word and a stream wait: SMX_E_ARG for an op > 2 among a job's events, an offset that
+ * is negative, decreasing or past n_total, bases that do not lie before the own events, a
+ * job_base outside [-1, n_bases), or job lengths that sum to more than n_out (all found on
+ * the device before a column is read out of bounds).  Sizes that are negative, n_total or
+ * n_out above 2^30 - 1, a null pointer with a non-zero size and a workspace that is too
+ * small or not 16-byte aligned come back (SMX_E_ARG / SMX_E_WORKSPACE) before any HIP call.
+ * n_jobs = 0 writes out_offsets[0] = 0 and counts[0] = 0.  One workspace serves any
+ * sequence of calls, smx_rga_replay's included when it is large enough for each.
+ */
+typedef struct smx_rga_onto {
+  int64_t n_total; /* events in the columns */
+  int64_t n_bases;
+  int64_t n_jobs;
+  int64_t n_out;
+  const int64_t* base_off;
+  const int64_t* own_off;
+  const int32_t* job_base;
+  const uint8_t* op;
+  const uint32_t* value;
+  const uint32_t* anchor;
+  const int64_t* t;
+  const uint32_t* author;
+  const uint64_t* opid_hi;
+  const uint64_t* opid_lo;
+} smx_rga_onto;
+
+int smx_rga_replay_onto_workspace_bytes(int64_t n_jobs, int64_t n_out, size_t* bytes);
+int smx_rga_replay_onto(const smx_rga_onto* onto, const smx_rga_out* out, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 const char* smx_last_error(void);
 const char* smx_version(void);

@@ -5,7 +5,9 @@ argument meaning are unchanged; ``RGA`` records its event stream and
 ``materialize()`` replays it through ``smx_rga_replay`` (include/smx.h); ``RGA.list``
 (the reference's state, crdt.py:26-27) replays it in the library's list mode, which
 keeps the tombstoned elements.
-:func:`replay` is the batched entry point: many independent lists in one launch.
+:func:`replay` is the batched entry point: many independent lists in one launch;
+:func:`replay_onto` replays many event streams onto base lists that are stored once
+(``smx_rga_replay_onto``).
 
 Exact parallel restatement used by the device: the fate
 of every element depends only on the events of its (list, value); survivors
@@ -72,7 +74,10 @@ def _rank(xs: Sequence[Any]) -> np.ndarray:
     return np.fromiter((table[x] for x in xs), np.uint32, len(xs))
 
 
-def marshal_streams(streams: Sequence[Sequence[Event]]) -> RgaBatch:
+def _event_columns(streams: Sequence[Sequence[Event]]):
+    """The event columns of `streams`, one after another, in one id domain: (list ids, op,
+    value, anchor, t, author, opid_hi, opid_lo, value objects).  Values are interned by one
+    _EqClasses; anchors, authors and a non-int t are ranked over all the events."""
     lids, ops, vals, anchors, ts, authors, opids, objs = [], [], [], [], [], [], [], []
     eq = _EqClasses()
     for lid, stream in enumerate(streams):
@@ -95,9 +100,104 @@ def marshal_streams(streams: Sequence[Sequence[Event]]) -> RgaBatch:
     tarr = np.fromiter(ts, np.int64, n) if all(
         type(x) is int and -2 ** 63 <= x < 2 ** 63 for x in ts) else _rank(ts).astype(np.int64)
     _, hi, lo = _encode_ids(opids) if n else (0, np.zeros(0, np.uint64), np.zeros(0, np.uint64))
-    return RgaBatch(len(streams), np.asarray(lids, np.uint32), np.asarray(ops, np.uint8),
-                    np.asarray(vals, np.uint32), _rank(anchors), tarr, _rank(authors),
-                    hi, lo, objs)
+    return (np.asarray(lids, np.uint32), np.asarray(ops, np.uint8), np.asarray(vals, np.uint32),
+            _rank(anchors), tarr, _rank(authors), hi, lo, objs)
+
+
+def marshal_streams(streams: Sequence[Sequence[Event]]) -> RgaBatch:
+    return RgaBatch(len(streams), *_event_columns(streams))
+
+
+@dataclass
+class RgaOntoBatch:
+    """Host image of ``smx_rga_onto``: every base's events once, then the jobs' own events."""
+
+    n_bases: int
+    n_jobs: int
+    base_off: np.ndarray       # i64 [n_bases + 1]
+    own_off: np.ndarray        # i64 [n_jobs + 1]
+    job_base: np.ndarray       # i32 [n_jobs], -1 (SMX_NONE): no base
+    op: np.ndarray
+    value: np.ndarray
+    anchor: np.ndarray
+    t: np.ndarray
+    author: np.ndarray
+    opid_hi: np.ndarray
+    opid_lo: np.ndarray
+    values: List[Any]          # column index -> value object
+
+    @property
+    def n(self) -> int:
+        return len(self.op)
+
+    @property
+    def job_len(self) -> np.ndarray:
+        """Events per job: its base's and its own."""
+        base_len = np.diff(self.base_off)
+        b = self.job_base
+        return np.where(b >= 0, base_len[np.maximum(b, 0)] if self.n_bases else 0, 0) + np.diff(self.own_off)
+
+    @property
+    def n_out(self) -> int:
+        return int(self.job_len.sum())
+
+
+Job = Tuple[Any, Sequence[Event]]  # (base index or None, own events)
+
+
+def marshal_onto(bases: Sequence[Sequence[Event]], jobs: Sequence[Job]) -> RgaOntoBatch:
+    """The columns of ``smx_rga_replay_onto``: each base marshalled once, the jobs' own
+    streams after them, all in one id domain (a value, anchor or author of a base and of an
+    own stream gets one id, so an own move or delete reaches the base's elements)."""
+    nb, nj = len(bases), len(jobs)
+    job_base = np.full(nj, -1, np.int32)
+    for j, (b, _) in enumerate(jobs):
+        if b is not None:
+            if not 0 <= int(b) < nb:
+                raise IndexError(f"job {j}: base {b} of {nb}")
+            job_base[j] = int(b)
+    streams = list(bases) + [own for _, own in jobs]
+    lid, *cols = _event_columns(streams)
+    off = np.zeros(nb + nj + 1, np.int64)
+    np.cumsum(np.bincount(lid, minlength=nb + nj), out=off[1:])
+    return RgaOntoBatch(nb, nj, off[:nb + 1].copy(), off[nb:].copy(), job_base, *cols)
+
+
+def job_columns(batch: RgaOntoBatch) -> Tuple[np.ndarray, np.ndarray]:
+    """The jobs' events spelled out: (column index of every event, job by job -- its base's,
+    then its own; the jobs' starts in that array, n_jobs + 1)."""
+    starts = np.concatenate([[0], np.cumsum(batch.job_len)]).astype(np.int64)
+    parts = []
+    for j in range(batch.n_jobs):
+        b = int(batch.job_base[j])
+        if b >= 0:
+            parts.append(np.arange(batch.base_off[b], batch.base_off[b + 1], dtype=np.int64))
+        parts.append(np.arange(batch.own_off[j], batch.own_off[j + 1], dtype=np.int64))
+    return (np.concatenate(parts) if parts else np.zeros(0, np.int64)), starts
+
+
+def replay_onto(bases: Sequence[Sequence[Event]], jobs: Sequence[Job]) -> List[List[Any]]:
+    """Materialize, for every job (base index or None, own events), the list that its base's
+    events followed by its own build -- ``replay([bases[b] + own ...])`` with every base
+    marshalled, copied and stored once."""
+    from ._lib import rga_replay_onto_device  # the HIP library; raises if missing
+    batch = marshal_onto(bases, jobs)
+    _, src, offsets = rga_replay_onto_device(batch)
+    srcl = src.tolist()
+    offl = offsets.tolist()
+    return [[batch.values[s] for s in srcl[offl[i]:offl[i + 1]]] for i in range(len(jobs))]
+
+
+def replay_lists_onto(bases: Sequence[Sequence[Event]], jobs: Sequence[Job]) -> List[List[Elem]]:
+    """Every job's final list state, as :func:`replay_lists` returns it for its base's events
+    followed by its own."""
+    from ._lib import rga_replay_onto_device  # the HIP library; raises if missing
+    batch = marshal_onto(bases, jobs)
+    _, src, offsets, tomb = rga_replay_onto_device(batch, tombstones=True)
+    events = [ev for stream in bases for ev in stream] + [ev for _, own in jobs for ev in own]
+    srcl, tl, offl = src.tolist(), tomb.tolist(), offsets.tolist()
+    return [[Elem(events[s][1], events[s][2], bool(tb)) for s, tb in
+             zip(srcl[offl[i]:offl[i + 1]], tl[offl[i]:offl[i + 1]])] for i in range(len(jobs))]
 
 
 def replay(streams: Sequence[Sequence[Event]]) -> List[List[Any]]:

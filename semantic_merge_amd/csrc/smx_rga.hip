@@ -15,12 +15,15 @@
 // persistent, in LDS): value groups by hashing, one sequential replay per group,
 // survivors ordered by (anchor, t, author, opid, index) -> compaction, each list's
 // output offset summed by its own wave from per-chunk survivor sums.
+// smx_rga_replay_onto (at the end, smx_rga_onto.h): the same list kernels over jobs, each a
+// base's events followed by its own, read in place from bases that are stored once.
 #include <algorithm>
 #include <chrono>
 #include <string>
 
 #include "smx_scan.h"
 #include "smx_rga_part.h"
+#include "smx_rga_onto.h"
 #include "smx_wave_sort.h"
 #include "smx_rga_list.h"
 #include "smx_rga_out.h"
@@ -33,12 +36,15 @@ static bool o_ok(const smx_rga_ops* o) {
 }
 
 struct RgaLayout { size_t off[16], total; };
-enum { R_REC, R_REC2, R_KEYS, R_KEYS2, R_RHIST, R_TV, R_TS, R_BST, R_GP, R_DEF2, R_PART, R_LSTART, R_SCNT, R_SOFF, R_N };
+enum { R_REC, R_REC2, R_KEYS, R_KEYS2, R_RHIST, R_TV, R_TS, R_BST, R_GP, R_DEF2, R_PART, R_LSTART, R_SCNT, R_SOFF, R_JOBS, R_N };
 // R_PART in u32 words: scan_excl's SCAN_NB partials (8 bytes each), then 16 status words (the
-// first 8 zeroed per call): the error word, scan_excl's total, the counts of deferred lists.
-enum { RP_ERR = SCAN_NB * 2, RP_TOTALS = RP_ERR + 2, RP_NDEF = RP_ERR + 4, RP_NDEF_BIG = RP_NDEF + 1, RP_WORDS = RP_ERR + 16 };
+// first 8 zeroed per call): the error word, scan_excl's total, the counts of deferred lists;
+// smx_rga_replay_onto zeroes all 16: the jobs' total length, 64 bits (k_rga_onto_jobs).
+enum { RP_ERR = SCAN_NB * 2, RP_TOTALS = RP_ERR + 2, RP_NDEF = RP_ERR + 4, RP_NDEF_BIG = RP_NDEF + 1,
+       RP_ONTO_SUM = RP_ERR + 8, RP_WORDS = RP_ERR + 16 };
 
-static RgaLayout rga_layout(i64 n, i64 nl) {
+// onto (smx_rga_replay_onto): n = n_out, nl = n_jobs; no partition buffers, the jobs' descriptors.
+static RgaLayout rga_layout(i64 n, i64 nl, bool onto = false) {
   const i64 nn = n > 0 ? n : 1;
   size_t sz[R_N];
   sz[R_REC] = sz[R_REC2] = (size_t)nn * RGA_REC * 8;
@@ -50,6 +56,11 @@ static RgaLayout rga_layout(i64 n, i64 nl) {
   sz[R_LSTART] = sz[R_SOFF] = sz[R_DEF2] = (size_t)(nl + 1) * 4;
   // scnt: RGA_CS_MAX chunk sums, then the counts padded to whole 256-list chunks
   sz[R_SCNT] = (size_t)(RGA_CS_MAX + SMX_CEIL_DIV(nl + 1, (i64)RGA_CS_LISTS) * RGA_CS_LISTS) * 4;
+  sz[R_JOBS] = 0;
+  if (onto) {
+    sz[R_REC2] = sz[R_KEYS] = sz[R_KEYS2] = sz[R_RHIST] = 0;
+    sz[R_JOBS] = (size_t)(nl + 1) * 16;
+  }
   RgaLayout L;
   L.total = 0;
   for (int i = 0; i < R_N; ++i) {
@@ -71,6 +82,8 @@ struct RgaWs {
   i32* err;                    // RGA_E_* bits (the gate the list and output kernels read)
   u32 *totals, *ndef, *ndef_big;  // scan_excl's total; deferred lists (ndef: spare), those for k_rga_big
   u32 *lstart, *csum, *scnt, *soff;  // list starts; 256-list survivor sums, just before the counts; output offsets
+  uint4* jobs;                   // smx_rga_replay_onto: the jobs' source descriptors (OntoSrc)
+  unsigned long long* onto_sum;  // and their total length
 };
 
 static RgaWs rga_carve(void* ws, const RgaLayout& L, i64 n) {
@@ -87,6 +100,7 @@ static RgaWs rga_carve(void* ws, const RgaLayout& L, i64 n) {
   w.part = at(R_PART), w.err = (i32*)(w.part + RP_ERR);
   w.totals = w.part + RP_TOTALS, w.ndef = w.part + RP_NDEF, w.ndef_big = w.part + RP_NDEF_BIG;
   w.lstart = at(R_LSTART), w.csum = at(R_SCNT), w.scnt = w.csum + RGA_CS_MAX, w.soff = at(R_SOFF);
+  w.jobs = (uint4*)at(R_JOBS), w.onto_sum = (unsigned long long*)(w.part + RP_ONTO_SUM);
   return w;
 }
 
@@ -141,6 +155,40 @@ static void rga_pass(const smx_rga_ops& o, const RgaWs& w, const u32* kin, const
                      w.rhist, w.err, (u32)nblk);
 }
 
+// The device's CU count, once: the persistent grids are sized by it.
+static int rga_device_init() {
+  if (g_rr_grid == 0) {  // persistent scatter workgroups
+    int dev = 0, cus = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    g_cus = cus > 0 ? cus : 256;
+    g_rr_grid = g_cus * RR_PER_CU;
+  }
+  return SMX_OK;
+}
+
+// k_rga_wave's persistent grid for nl lists
+static u32 rga_wave_grid(i64 nl) {
+  i64 wg = SMX_CEIL_DIV(nl, (i64)RW_WAVES);
+  if (RW_PER_CU > 0 && wg > (i64)g_cus * RW_PER_CU) wg = (i64)g_cus * RW_PER_CU;
+  return (u32)wg;
+}
+
+// The output stage: the lists' survivors from their slices (tmp_v / tmp_s at lstart) to the output.
+static int rga_out_stage(const RgaWs& w, i64 nl, const smx_rga_out* out, hipStream_t st) {
+  if (nl <= RGA_FUSED_MAX) {  // each list's wave finds its own offset
+    hipLaunchKernelGGL(k_rga_out_fused, dim3(SMX_CEIL_DIV(nl, (i64)(BLOCK / WAVE * RGA_OUT_LPW))), dim3(BLOCK), 0, st,
+                       w.tmp_v, w.tmp_s, w.lstart, w.scnt, nl, *out, w.err);
+  } else {
+    HIP_TRY((scan_excl<OpSum, u32, u32>(w.scnt, w.soff, nl, nullptr, w.part, w.totals, st)));
+    hipLaunchKernelGGL(k_rga_out, dim3(SMX_CEIL_DIV(nl, (i64)(BLOCK / WAVE))), dim3(BLOCK), 0, st, w.tmp_v, w.tmp_s,
+                       w.lstart, w.scnt, w.soff, nl, *out, w.err);
+    hipLaunchKernelGGL(k_rga_fin, dim3(1), dim3(1), 0, st, w.totals, nl, *out, w.err);
+  }
+  HIP_TRY(hipGetLastError());
+  return SMX_OK;
+}
+
 static int rga_impl(const smx_rga_ops* ops, const smx_rga_out* out, void* ws, size_t wsb, hipStream_t st,
                     bool grouped) {
   const i64 n = ops->n_ops, nl = ops->n_lists;
@@ -161,13 +209,7 @@ static int rga_impl(const smx_rga_ops* ops, const smx_rga_out* out, void* ws, si
   const smx_rga_ops o = *ops;
   const int grid = (int)(SMX_CEIL_DIV(n, (i64)BLOCK) < 8192 ? SMX_CEIL_DIV(n, (i64)BLOCK) : 8192);
   HIP_TRY(hipMemsetAsync(w.err, 0, 32, st));
-  if (g_rr_grid == 0) {  // persistent scatter workgroups
-    int dev = 0, cus = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    g_cus = cus > 0 ? cus : 256;
-    g_rr_grid = g_cus * RR_PER_CU;
-  }
+  if (int rc = rga_device_init()) return rc;
   int npass = 1;  // partition passes, 8 bits of the list id each
   while (npass < 4 && ((u64)(nl - 1) >> (8 * npass)) != 0) ++npass;
   if (grouped) {  // the caller's events come list by list: no partition, the list kernels read the columns in place
@@ -187,28 +229,17 @@ static int rga_impl(const smx_rga_ops* ops, const smx_rga_out* out, void* ws, si
   }
 
   const int tomb = out->out_tomb != nullptr;
-  i64 wg = SMX_CEIL_DIV(nl, (i64)RW_WAVES);
-  if (RW_PER_CU > 0 && wg > (i64)g_cus * RW_PER_CU) wg = (i64)g_cus * RW_PER_CU;
-  hipLaunchKernelGGL(grouped ? k_rga_wave<true> : k_rga_wave<false>, dim3((u32)wg), dim3(WAVE * RW_WAVES), 0, st, o,
+  hipLaunchKernelGGL(grouped ? k_rga_wave<true> : k_rga_wave<false>, dim3(rga_wave_grid(nl)), dim3(WAVE * RW_WAVES), 0, st, o,
                      w.rec, w.lstart, n, nl, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err);
   // lists of more than RW_CAP events (a few, if any).  (On a second stream beside
   // k_rga_wave they measured no faster: their workgroups trail k_rga_wave's, and the
   // join costs ~14 us, round 4.)
-  hipLaunchKernelGGL(k_rga_wave2, dim3(64), dim3(WAVE * RW_WAVES), 0, st, o, w.rec, w.lstart, n, nl, w.def2,
+  hipLaunchKernelGGL(k_rga_wave2<false>, dim3(64), dim3(WAVE * RW_WAVES), 0, st, o, w.rec, w.lstart, n, nl, w.def2,
                      w.ndef_big, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err, (int)grouped);
-  hipLaunchKernelGGL(k_rga_big, dim3(RGA_BIG_GRID), dim3(1024), 0, st, o, w.rec, w.lstart, n, nl, w.def2, w.ndef_big,
+  hipLaunchKernelGGL(k_rga_big<false>, dim3(RGA_BIG_GRID), dim3(1024), 0, st, o, w.rec, w.lstart, n, nl, w.def2, w.ndef_big,
                      w.bst, w.gp, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err);
 
-  if (nl <= RGA_FUSED_MAX) {  // each list's wave finds its own offset
-    hipLaunchKernelGGL(k_rga_out_fused, dim3(SMX_CEIL_DIV(nl, (i64)(BLOCK / WAVE * RGA_OUT_LPW))), dim3(BLOCK), 0, st,
-                       w.tmp_v, w.tmp_s, w.lstart, w.scnt, nl, *out, w.err);
-  } else {
-    HIP_TRY((scan_excl<OpSum, u32, u32>(w.scnt, w.soff, nl, nullptr, w.part, w.totals, st)));
-    hipLaunchKernelGGL(k_rga_out, dim3(SMX_CEIL_DIV(nl, (i64)(BLOCK / WAVE))), dim3(BLOCK), 0, st, w.tmp_v, w.tmp_s,
-                       w.lstart, w.scnt, w.soff, nl, *out, w.err);
-    hipLaunchKernelGGL(k_rga_fin, dim3(1), dim3(1), 0, st, w.totals, nl, *out, w.err);
-  }
-  HIP_TRY(hipGetLastError());
+  if (int rc = rga_out_stage(w, nl, out, st)) return rc;
   i32 herr = 0;
   HIP_TRY(hipMemcpyAsync(&herr, w.err, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(rga_stream_wait(st));
@@ -228,4 +259,75 @@ extern "C" int smx_rga_replay_ex(const smx_rga_ops* ops, const smx_rga_out* out,
 extern "C" int smx_rga_replay(const smx_rga_ops* ops, const smx_rga_out* out, void* ws, size_t wsb,
                               void* stream) {
   return smx_rga_replay_ex(ops, out, ws, wsb, 0u, stream);
+}
+
+// ---------------------------------------------------------------------------
+// smx_rga_replay_onto: many jobs, each a base's events followed by its own, over bases
+// stored once (smx_rga_onto.h).  The pre-pass gives each job its length and slice; the
+// list kernels' ONTO instantiations read a job's events from the two column ranges; the
+// output stage is the replay's own, one "list" per job.
+static RgaLayout rga_onto_layout(i64 n_jobs, i64 n_out) { return rga_layout(n_out, n_jobs, true); }
+
+extern "C" int smx_rga_replay_onto_workspace_bytes(int64_t n_jobs, int64_t n_out, size_t* bytes) {
+  if (!bytes || n_jobs < 0 || n_out < 0 || n_jobs >= (i64)0x7fffffff || n_out > (i64)RGA_IDX_MASK)
+    return smx_set_error(SMX_E_ARG, "bad sizes");
+  *bytes = rga_onto_layout(n_jobs, n_out).total;
+  return SMX_OK;
+}
+
+extern "C" int smx_rga_replay_onto(const smx_rga_onto* onto, const smx_rga_out* out, void* ws, size_t wsb,
+                                   void* stream) {
+  if (!onto) return smx_set_error(SMX_E_ARG, "null smx_rga_onto");
+  const smx_rga_onto& q = *onto;
+  const i64 nj = q.n_jobs;
+  if (q.n_total < 0 || q.n_bases < 0 || nj < 0 || q.n_out < 0) return smx_set_error(SMX_E_ARG, "negative size");
+  if (q.n_total > (i64)RGA_IDX_MASK) return smx_set_error(SMX_E_ARG, "n_total too large");
+  if (q.n_out > (i64)RGA_IDX_MASK) return smx_set_error(SMX_E_ARG, "n_out too large");
+  if (q.n_bases >= (i64)0x7fffffff || nj >= (i64)0x7fffffff) return smx_set_error(SMX_E_ARG, "too many bases or jobs");
+  if (!out || !out->out_offsets || !out->counts) return smx_set_error(SMX_E_ARG, "null output");
+  if (q.n_out > 0 && (!out->out_value || !out->out_src)) return smx_set_error(SMX_E_ARG, "null output");
+  if (!q.base_off || !q.own_off || (nj > 0 && !q.job_base)) return smx_set_error(SMX_E_ARG, "null offsets or job_base");
+  if (q.n_total > 0 && !(q.op && q.value && q.anchor && q.t && q.author && q.opid_hi && q.opid_lo))
+    return smx_set_error(SMX_E_ARG, "null input pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const RgaLayout L = rga_onto_layout(nj, q.n_out);
+  if (nj > 0) {
+    if (!ws || wsb < L.total)
+      return smx_set_error(SMX_E_WORKSPACE, ("workspace too small: need " + std::to_string(L.total)).c_str());
+    if (reinterpret_cast<uintptr_t>(ws) & 15) return smx_set_error(SMX_E_WORKSPACE, "workspace not 16-byte aligned");
+  }
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  if (nj == 0) {
+    HIP_TRY(hipMemsetAsync(out->out_offsets, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(out->counts, 0, 8, st));
+    return SMX_OK;
+  }
+  const RgaWs w = rga_carve(ws, L, q.n_out > 0 ? q.n_out : 1);
+  // the columns as the list kernels take them; in place of the list ids, the jobs' descriptors
+  const smx_rga_ops o = {q.n_total, nj, (const u32*)w.jobs, q.op, q.value, q.anchor, q.t, q.author, q.opid_hi, q.opid_lo};
+  const RgaOntoJobs jq = {q.n_total, q.n_bases, nj, q.n_out, q.base_off, q.own_off, q.job_base};
+  HIP_TRY(hipMemsetAsync(w.err, 0, 64, st));
+  if (int rc = rga_device_init()) return rc;
+  const i64 top = (q.n_bases > nj ? q.n_bases : nj) + 1;
+  const int grid = (int)(SMX_CEIL_DIV(top, (i64)BLOCK) < 2048 ? SMX_CEIL_DIV(top, (i64)BLOCK) : 2048);
+  u32* len = w.soff;  // (the output stage's scan writes soff later)
+  hipLaunchKernelGGL(k_rga_onto_jobs, dim3(grid), dim3(BLOCK), 0, st, jq, len, w.jobs, w.csum, w.onto_sum, w.err);
+  HIP_TRY((scan_excl<OpSum, u32, u32>(len, w.lstart, nj + 1, nullptr, w.part, w.totals, st)));
+  hipLaunchKernelGGL(k_rga_onto_fit, dim3(1), dim3(1), 0, st, w.onto_sum, q.n_out, w.err);
+
+  const int tomb = out->out_tomb != nullptr;
+  const i64 n = q.n_total;
+  hipLaunchKernelGGL((k_rga_wave<true, true>), dim3(rga_wave_grid(nj)), dim3(WAVE * RW_WAVES), 0, st, o, w.rec, w.lstart,
+                     n, nj, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err);
+  hipLaunchKernelGGL(k_rga_wave2<true>, dim3(64), dim3(WAVE * RW_WAVES), 0, st, o, w.rec, w.lstart, n, nj, w.def2,
+                     w.ndef_big, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err, 1);
+  hipLaunchKernelGGL(k_rga_big<true>, dim3(RGA_BIG_GRID), dim3(1024), 0, st, o, w.rec, w.lstart, n, nj, w.def2,
+                     w.ndef_big, w.bst, w.gp, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err);
+  if (int rc = rga_out_stage(w, nj, out, st)) return rc;
+  i32 herr = 0;
+  HIP_TRY(hipMemcpyAsync(&herr, w.err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(rga_stream_wait(st));
+  if (herr & RGA_E_INPUT)
+    return smx_set_error(SMX_E_ARG, "invalid input: an op > 2, a bad offset or job_base, or more events than n_out");
+  return SMX_OK;
 }
