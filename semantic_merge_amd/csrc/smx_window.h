@@ -217,7 +217,8 @@ __device__ __forceinline__ void win_rename_flags(const WinArgs& P, i64 w, u64 Mb
 #define WF_ITEMS (WF_CAP / WF_NT)
 #define WF_KP ((2 * CH + WF_NT - 1) / WF_NT)  // partial-chunk kinds per lane
 
-// LDS ~36 KB (buffers are reused across steps) so 4 workgroups fit a CU: while
+// LDS 40,640 B (buffers are reused across steps; four workgroups fit a CU up to 40,960 B
+// each, and the bucket counters take a word each: DESIGN.md §5) so 4 workgroups fit a CU: while
 // some workgroups run their LDS steps, others stream their windows from HBM.
 // DBG: step timestamps of every window (diagnostics, tools/window_phases.py):
 // lane 0 of wave 0 stores s_memtime at the start (i = 0) and after step i = 1 .. 14 into
@@ -256,7 +257,7 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
   // (st_a, st_b, steps 11-14)
   __shared__ __attribute__((aligned(16))) u64 sts[CAP];
   __shared__ __attribute__((aligned(16))) u16 sord[CAP];  // final slot -> element (step 9 on)
-  __shared__ u32 bcnt[CAP / 2];   // bucket counters, then starts, two u16 per word (steps 1-9); then rown
+  __shared__ __attribute__((aligned(16))) u32 bcnt[CAP];  // bucket counters, then starts, one per word (steps 1-9); then rown
   __shared__ u16 sp[CAP];         // head element -> S position of its run (steps 2-4); later posl
   __shared__ __attribute__((aligned(16))) u8 skS[CAP];  // kinds by final slot (step 9 on)
   __shared__ u16 inv[CAP];        // element -> final slot
@@ -401,7 +402,10 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
   if (bad) P.meta->bad_sym = 1;
   static_assert(OW <= NT, "one occupancy word per thread");
   if (t < OW) occ[t] = 0u;
-  for (int i = t; i < CAP / 2; i += NT) bcnt[i] = 0u;
+  {
+    typedef u32 __attribute__((ext_vector_type(4))) z4;
+    for (int i = t; i < CAP / 4; i += NT) reinterpret_cast<z4*>(bcnt)[i] = z4{0u, 0u, 0u, 0u};
+  }
   if (t <= SMX_N_KINDS) base[t] = base_v;
   if (t < SMX_N_KINDS + 2) woffk[t] = woff_x + woff_y;
   if (t == 0) wtot[0] = failed != 0;
@@ -621,33 +625,30 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
         const u32 gs = gstart((int)g_r[i]), ge = gstart((int)g_r[i] + 1);
         const u32 b = gs + (u32)(((u64)(ge - gs) * hi_r[i]) >> 32);
         b_r[i] = b;
-        ar_r[i] = (atomicAdd(&bcnt[b >> 1], 1u << (16 * (b & 1))) >> (16 * (b & 1))) & 0xffffu;
+        ar_r[i] = atomicAdd(&bcnt[b], 1u);
       }
       __syncthreads();
       WSTAMP(6);
       WF_EXIT(6);
       // 7. bucket starts
       {
-        constexpr int WPT = CAP / (2 * NT);
+        constexpr int WPT = CAP / NT;
         u32 cw[WPT], sum = 0;
 #pragma unroll
         for (int i = 0; i < WPT; ++i) {
           cw[i] = bcnt[WPT * t + i];
-          sum += (cw[i] & 0xffffu) + (cw[i] >> 16);
+          sum += cw[i];
         }
         u32 tot;
         u32 run = block_excl_scan<OpSum, u32, WAVES>(sum, &vbw[0][0], &tot);
 #pragma unroll
         for (int i = 0; i < WPT; ++i) {
-          const u32 c0 = cw[i] & 0xffffu, c1 = cw[i] >> 16;
-          bcnt[WPT * t + i] = run | ((run + c0) << 16);
-          run += c0 + c1;
+          bcnt[WPT * t + i] = run;
+          run += cw[i];
         }
       }
       __syncthreads();
-      auto bstart = [&](u32 b) -> u32 {
-        return b < (u32)CAP ? (bcnt[b >> 1] >> (16 * (b & 1))) & 0xffffu : (u32)sz;
-      };
+      auto bstart = [&](u32 b) -> u32 { return b < (u32)CAP ? bcnt[b] : (u32)sz; };
       WSTAMP(7);
       WF_EXIT(7);
       // 8. members in bucket order: key and element
@@ -674,7 +675,7 @@ __global__ void __launch_bounds__(NT, CAP > WF_CAP ? 4 : WF_MINB) k_window_f(Win
         const int e = t + NT * i;
         const u32 b1 = b + 1 < (u32)CAP ? b + 1 : (u32)CAP - 1;  // (branch-free bucket bounds)
         const u32 lo = slot_r[i] - ar_r[i];  // (the bucket's start: this op's slot less its arrival rank)
-        const u32 hw = (bcnt[b1 >> 1] >> (16 * (b1 & 1))) & 0xffffu;
+        const u32 hw = bcnt[b1];
         const u32 hi = b + 1 < (u32)CAP ? hw : (u32)sz, kp = hi_r[i];
         u32 c = 0;
         bool tie = false;
