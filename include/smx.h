@@ -12,6 +12,9 @@
  *                    stored once
  *   smx_compose_pairs <- the same, for pairs (i, j) over logs stored once, laid out as
  *                    smx_screen takes them
+ *   smx_compose_train <- that loop in a loop: a merge train over such logs, each log
+ *                    composed against what landed before it, conflicting logs put off
+ *                    (what semmerge/__main__.py:65-69 does to one merge, per step)
  *   smx_screen    <- the conflict list of the same loop alone (what semmerge/__main__.py
  *                    looks at first), for many pairs of logs, from the logs' renames
  *   smx_rga_replay <- semmerge/crdt.py:23-57  RGA.insert/move/delete/materialize,
@@ -534,6 +537,81 @@ int smx_compose_pairs_workspace_bytes(int64_t n_logs, int64_t n_pairs, int64_t n
  * for these flags, or not 8-byte aligned) are reported before any HIP call; n_pairs = 0 or
  * n_logs = 0 returns SMX_OK and launches nothing. */
 int smx_compose_pairs(const struct smx_pairs* p, void* workspace, size_t workspace_bytes, uint32_t flags, void* stream);
+
+/*
+ * Merge trains over logs stored once: each log composed against what landed before it
+ * (DESIGN.md §21).  The logs are laid out as smx_screen / smx_pairs take them.  Train r is the
+ * logs train_log[train_off[r] .. train_off[r+1]), in that order; step g = train_off[r] + s is
+ * its s-th log.  A log may be in any number of trains, and more than once in one.
+ *
+ * The accumulator of a train starts empty.  Step g composes (accumulator as A, log as B)
+ * exactly as smx_compose would on those two logs.  With zero conflicts the step lands: the
+ * accumulator becomes the composed log -- the columns that marshalling the composed ops would
+ * give: the source ops' columns in composed order, a move's v0 replaced by the step's addr[k]
+ * where that is not SMX_NONE and its v1 by file[k] alike -- except where file[k] is empty_str,
+ * the id of the empty string: marshalling reads a move's file as `newFile or file`, so an empty
+ * newFile falls through to the op's own `file`, and v1 becomes v1_alt[src] (the id of
+ * str(params["file"]), or SMX_NONE without one).  With empty_str = SMX_NONE (no empty string
+ * among the ids) v1_alt is not read and may be NULL.  Any other step (conflicts, -1, -2
+ * below) leaves the accumulator as it was, and the train goes on with its next log.
+ *
+ * Every accumulator entry carries its source column index (log_off[l] + i: it names log and
+ * op) and its accumulated addr / file / ctx: per field the last value that was not SMX_NONE
+ * over the steps it went through.  Applied to a clone of the source op they give the op that
+ * materialising step after step gives.
+ *
+ *   results      per train r, counts[2r] entries of src / addr / file / ctx from res_off[r]: the
+ *                final accumulator; the region [res_off[r], res_off[r+1]) has room for the sum
+ *                of the lengths of the train's logs at least; counts[2r+1]: the steps that landed
+ *   step_counts  [2g]: the accumulator's length after step g, whatever happened;
+ *                [2g+1]: >= 0 the step's conflicts (0: it landed);
+ *                        -1 a log index outside [0, n_logs), a log invalid under smx_screen's
+ *                           log_off rules, or an op with kind >= 18 or sym >= n_sym in it;
+ *                        -2 accumulator plus log exceed 2048 ops
+ *   conflicts    per step g the first conf_off[g+1] - conf_off[g] records at conflicts[4 *
+ *                conf_off[g]], the full number in step_counts[2g+1], nothing past the capacity
+ *                (a negative or decreasing conf_off gives the step none).  A record is four
+ *                int32: the A op's column index, the B op's column index, and the addr and the
+ *                file the A op carried when the step began.
+ *
+ * A train whose train_off or res_off entries are negative, below an earlier entry, decreasing
+ * or past n_steps / n_out, or whose region is too small, reports counts -1, -1 and writes
+ * nothing else.  Failed trains and steps never touch their neighbours.
+ *
+ * Stream-ordered as smx_compose_batch: five launches whatever the data, no host
+ * synchronisation, no allocation, no read-back; the call clears the workspace state it needs,
+ * so one workspace serves any sequence of calls.  One workgroup runs a train's steps one after
+ * another.  flags must be 0.
+ */
+typedef struct smx_train {
+  int64_t n_logs, n_total, n_trains, n_steps, n_sym, n_out;
+  const int64_t* log_off;                 /* device [n_logs+1], as smx_screen */
+  const uint8_t* kind; const uint64_t* ts, *oid_hi, *oid_lo;
+  const uint32_t* sym; const int32_t* v0, *v1;     /* as smx_ops, n_total entries, one id domain for all logs */
+  const int32_t* v1_alt;                  /* n_total entries, read for moves only: see above; NULL with empty_str < 0 */
+  const int64_t* train_off;               /* device [n_trains+1], into train_log */
+  const int32_t* train_log;               /* device [n_steps]: log indices */
+  const int64_t* res_off;                 /* device [n_trains+1]: train r's results at [res_off[r], res_off[r+1]) */
+  int32_t* src, *addr, *file, *ctx;       /* n_out entries */
+  int32_t* conflicts; const int64_t* conf_off;     /* 4 int32 per record; conf_off [n_steps+1], in records */
+  int64_t* counts;                        /* [2*n_trains]: final accumulator length, landed steps */
+  int64_t* step_counts;                   /* [2*n_steps]: accumulator length after the step, its outcome */
+  int32_t grid_cap;                       /* as smx_batch */
+  int32_t empty_str;                      /* the id of the empty string in the v1 / file domain, or SMX_NONE */
+} smx_train;
+/* Workspace (8-byte aligned), linear in its arguments: 4 bytes per log, 36 per train and 89 per
+ * entry of n_out (n_logs, n_trains, n_steps, n_out in 0 .. 2^31 - 1; flags 0). */
+int smx_compose_train_workspace_bytes(int64_t n_logs, int64_t n_trains, int64_t n_steps, int64_t n_out,
+                                      uint32_t flags, size_t* bytes);
+/* SMX_E_ARG (a non-zero flag; then a null struct, negative sizes, n_logs, n_trains, n_steps,
+ * n_total or n_out over 2^31 - 1, grid_cap < 0, empty_str < -1, n_sym > 2^32 - 1; a null v1_alt
+ * with empty_str >= 0 and n_total > 0; a null train_off / res_off /
+ * counts, a null log_off with n_logs > 0, a null train_log / conf_off / step_counts /
+ * conflicts with n_steps > 0, a null column with n_total > 0, a null result array with
+ * n_out > 0) and SMX_E_WORKSPACE (too small, or not 8-byte aligned) are reported before any HIP
+ * call; n_trains = 0 returns SMX_OK and launches nothing. */
+int smx_compose_train(const struct smx_train* t, void* workspace, size_t workspace_bytes, uint32_t flags,
+                      void* stream);
 
 /*
  * Sharded single merge: one process per GPU, shard r of G.

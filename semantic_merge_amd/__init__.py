@@ -3,7 +3,7 @@ from .ops import Op, Target  # noqa: F401
 from .conflict import Conflict  # noqa: F401
 
 __all__ = ["Op", "Target", "Conflict", "compose_oplogs", "compose_many", "compose_against",
-           "compose_pairs", "screen_conflicts", "screen_all"]
+           "compose_pairs", "compose_train", "screen_conflicts", "screen_all"]
 
 
 def __getattr__(name):
@@ -20,6 +20,9 @@ def __getattr__(name):
     if name == "compose_pairs":
         from .compose import compose_pairs
         return compose_pairs
+    if name == "compose_train":
+        from .compose import compose_train
+        return compose_train
     if name == "screen_conflicts":
         from .compose import screen_conflicts
         return screen_conflicts

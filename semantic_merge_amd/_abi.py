@@ -156,6 +156,39 @@ class SmxPairs(C.Structure):
     ]
 
 
+class SmxTrain(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_int64),
+        ("n_total", C.c_int64),
+        ("n_trains", C.c_int64),
+        ("n_steps", C.c_int64),
+        ("n_sym", C.c_int64),
+        ("n_out", C.c_int64),
+        ("log_off", C.c_void_p),
+        ("kind", C.c_void_p),
+        ("ts", C.c_void_p),
+        ("oid_hi", C.c_void_p),
+        ("oid_lo", C.c_void_p),
+        ("sym", C.c_void_p),
+        ("v0", C.c_void_p),
+        ("v1", C.c_void_p),
+        ("v1_alt", C.c_void_p),
+        ("train_off", C.c_void_p),
+        ("train_log", C.c_void_p),
+        ("res_off", C.c_void_p),
+        ("src", C.c_void_p),
+        ("addr", C.c_void_p),
+        ("file", C.c_void_p),
+        ("ctx", C.c_void_p),
+        ("conflicts", C.c_void_p),
+        ("conf_off", C.c_void_p),
+        ("counts", C.c_void_p),
+        ("step_counts", C.c_void_p),
+        ("grid_cap", C.c_int32),
+        ("empty_str", C.c_int32),
+    ]
+
+
 CAND_MAX_LOGS = 16384        # logs per smx_screen_candidates call (include/smx.h SMX_CAND_MAX_LOGS)
 SCREEN_MAX_RENAMES = 2048     # renames per pair of smx_screen, both logs together (more: counts -2)
 SCREEN_CLASSES = (128, 512, 2048)  # its size classes, in renames (csrc/smx_screen.h)
@@ -268,6 +301,8 @@ EXPORTS = (
     "smx_compose_batch_shared_ex",
     "smx_compose_pairs_workspace_bytes",
     "smx_compose_pairs",
+    "smx_compose_train_workspace_bytes",
+    "smx_compose_train",
     "smx_screen_workspace_bytes",
     "smx_screen",
     "smx_screen_ex_workspace_bytes",
@@ -335,6 +370,12 @@ def declare(lib: C.CDLL) -> C.CDLL:
         lib.smx_compose_pairs_workspace_bytes.restype = C.c_int
         lib.smx_compose_pairs.argtypes = [C.POINTER(SmxPairs), C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
         lib.smx_compose_pairs.restype = C.c_int
+    if hasattr(lib, "smx_compose_train"):  # (older builds, e.g. A/B baselines, lack it)
+        lib.smx_compose_train_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32,
+                                                          C.POINTER(C.c_size_t)]
+        lib.smx_compose_train_workspace_bytes.restype = C.c_int
+        lib.smx_compose_train.argtypes = [C.POINTER(SmxTrain), C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+        lib.smx_compose_train.restype = C.c_int
     if hasattr(lib, "smx_screen"):  # (older builds, e.g. A/B baselines, lack it)
         lib.smx_screen_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]
         lib.smx_screen_workspace_bytes.restype = C.c_int

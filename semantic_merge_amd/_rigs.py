@@ -326,6 +326,93 @@ class DevicePairs(_DeviceMany):
         return int(self.res_off[m])
 
 
+class DeviceTrains(_DeviceMany):
+    """Device-resident inputs, outputs and workspace for repeated smx_compose_train calls on a
+    LogsSoA and a list of trains, each a list of log indices (tests, tools/train_probe.py).  The
+    optional arguments reach the corners of the C ABI (include/smx.h smx_train):
+    conflict_caps per-step capacities in conflict records (default: the step's log's length,
+                  which always suffices);
+    grid_cap      smx_train.grid_cap;
+    log_off       the offsets passed instead of the LogsSoA's own;
+    train_off     the offsets into the steps passed instead of the trains' own;
+    res_off       the result offsets passed (default: the sum of its logs' lengths per train, one
+                  after another; a log index outside the logs counts as empty);
+    n_sym, n_total, n_steps, n_out  passed instead of the real ones;
+    v1_alt, empty_str  smx_train's two (default: none, SMX_NONE);
+    fill          every output word (results, conflict records, counts, step counts) starts as
+                  this value, and CONF_GUARD such words follow the last regions."""
+
+    _OUT = ("src", "addr", "file", "ctx", "conf", "counts", "step_counts")
+
+    def __init__(self, lsoa, trains, device: str = "cuda", conflict_caps=None, grid_cap: int = 0, log_off=None,
+                 train_off=None, res_off=None, n_sym: Optional[int] = None, n_total: Optional[int] = None,
+                 n_steps: Optional[int] = None, n_out: Optional[int] = None, fill: Optional[int] = None,
+                 v1_alt=None, empty_str: int = -1) -> None:
+        self._open(device)
+        torch, dev = self.torch, self.device
+        self.lsoa = lsoa
+        self._alt = None if v1_alt is None else self._up(np.asarray(v1_alt, np.int32))
+        L = self.n_logs = lsoa.n_logs
+        self.trains = [[int(l) for l in tr] for tr in trains]
+        R = self.n_trains = len(self.trains)
+        self.train_log = np.asarray([l for tr in self.trains for l in tr], np.int32)
+        S = self.n_steps = len(self.train_log)
+        own_off = np.concatenate([[0], np.cumsum([len(tr) for tr in self.trains], dtype=np.int64)]).astype(np.int64)
+        self.train_off = np.asarray(own_off if train_off is None else train_off, np.int64).reshape(R + 1)
+        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
+        tot = self.n_total = int(lsoa.n_total)
+        lens = np.diff(np.asarray(lsoa.log_off, np.int64))
+        ok = (self.train_log >= 0) & (self.train_log < L)
+        self.step_len = np.where(ok, lens[np.where(ok, self.train_log, 0)], 0) if L else np.zeros(S, np.int64)
+        if res_off is None:
+            csum = np.concatenate([[0], np.cumsum(self.step_len, dtype=np.int64)])
+            res_off = np.concatenate([[0], np.cumsum(csum[own_off[1:]] - csum[own_off[:-1]], dtype=np.int64)])
+        self.res_off = np.asarray(res_off, np.int64).reshape(R + 1)
+        self.n_out = max(int(self.res_off.max()), 0) if R else 0
+        self.n_sym = int(lsoa.n_sym) if n_sym is None else n_sym
+        self._upload_cols([lsoa])
+        self.conf_off = np.zeros(S + 1, np.int64)
+        np.cumsum(self.step_len if conflict_caps is None else conflict_caps, out=self.conf_off[1:])
+        f = 0 if fill is None else fill
+        for name in self._OUT[:4]:
+            setattr(self, name, torch.full((self.n_out + self.CONF_GUARD,), f, dtype=torch.int32, device=dev))
+        self.conf = torch.full((4 * int(self.conf_off[-1]) + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        self.counts = torch.full((2 * R + self.CONF_GUARD,), f, dtype=torch.int64, device=dev)
+        self.step_counts = torch.full((2 * S + self.CONF_GUARD,), f, dtype=torch.int64, device=dev)
+        self._workspace(lib().smx_compose_train_workspace_bytes, L, R, S, self.n_out, 0)
+        self._idx = [self._up(self.log_off), self._up(self.train_off), self._up(self.train_log),
+                     self._up(self.res_off), self._up(self.conf_off)]
+        self._call = lambda arg, ws, nbytes, st: lib().smx_compose_train(arg, ws, nbytes, 0, st)
+        self._arg = _abi.SmxTrain(L, tot if n_total is None else n_total, R, S if n_steps is None else n_steps,
+                                  self.n_sym, self.n_out if n_out is None else n_out, self._idx[0].data_ptr(),
+                                  *[t.data_ptr() for t in self._in], _ptr(self._alt), self._idx[1].data_ptr(),
+                                  self._idx[2].data_ptr(), self._idx[3].data_ptr(), self.src.data_ptr(),
+                                  self.addr.data_ptr(), self.file.data_ptr(), self.ctx.data_ptr(),
+                                  self.conf.data_ptr(), self._idx[4].data_ptr(), self.counts.data_ptr(),
+                                  self.step_counts.data_ptr(), grid_cap, empty_str)
+
+    def results(self, raw: Optional[dict] = None):
+        """Per train -1 for one that failed, else (src, addr, file, ctx, landed, steps): the final
+        accumulator trimmed to its count, the steps that landed, and per step (accumulator length
+        after it, outcome, its conflict records as an (n, 4) array trimmed to its capacity)."""
+        r = self.raw() if raw is None else raw
+        out = []
+        for t, tr in enumerate(self.trains):
+            k, landed = int(r["counts"][2 * t]), int(r["counts"][2 * t + 1])
+            if k < 0:
+                out.append(k)
+                continue
+            steps = []
+            for g in range(int(self.train_off[t]), int(self.train_off[t + 1])):
+                acc, oc = int(r["step_counts"][2 * g]), int(r["step_counts"][2 * g + 1])
+                c = int(self.conf_off[g])
+                nc = min(max(oc, 0), int(self.conf_off[g + 1]) - c)
+                steps.append((acc, oc, r["conf"][4 * c: 4 * (c + nc)].reshape(nc, 4)))
+            o = int(self.res_off[t])
+            out.append(tuple(r[x][o: o + k] for x in self._OUT[:4]) + (landed, steps))
+        return out
+
+
 class DeviceScreen(_DeviceMany):
     """Device-resident inputs, outputs and workspace for repeated smx_screen calls on a
     LogsSoA and a list of (i, j) pairs (tests, tools/screen_probe.py).  The optional

@@ -576,6 +576,79 @@ class ComposeSession:
             self._compose_routed(res, routed, [lsoa.pair(int(pairs[p, 0]), int(pairs[p, 1])) for p in routed], "pair")
         return res
 
+    # -- merge trains over logs stored once (smx_compose_train) --------------------------------
+
+    def compose_trains(self, lsoa, trains, v1_alt=None, empty_str: int = -1):
+        """Per train of `trains` (lists of log indices over a LogsSoA) what smx_compose_train leaves:
+        (src, addr, file, ctx, landed, steps) -- the final accumulator (column indices and the
+        accumulated addr / file / ctx), the number of steps that landed, and per step
+        (accumulator length after it, outcome, its conflict records as an (n, 4) array).  The
+        columns, every log once, are staged as they are: one host-to-device copy, one
+        smx_compose_train, one copy back, one stream sync, whatever the number of trains and
+        steps.  A step of outcome -2 (accumulator plus log over BATCH_MAX_OPS ops) is reported as
+        it is: the caller finishes that train elsewhere.  Invalid input raises SmxError naming the
+        train.  v1_alt, empty_str: smx_train's two (marshal.move_file_alt).  The results are
+        copies.  `last` holds the call's legs and "in_bytes"."""
+        t0 = time.perf_counter()
+        trains = [np.asarray(tr, np.int32).reshape(-1) for tr in trains]
+        R, L, tot = len(trains), lsoa.n_logs, int(lsoa.n_total)
+        self.last = _last(("in_bytes",))
+        if R == 0:
+            return []
+        train_log = np.ascontiguousarray(np.concatenate(trains)) if R else np.zeros(0, np.int32)
+        S = len(train_log)
+        for r, tr in enumerate(trains):
+            if len(tr) and (int(tr.min()) < 0 or int(tr.max()) >= L):
+                raise SmxError(-1, f"train {r}: a log index outside [0, {L})")
+        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
+        lens = log_off[1:] - log_off[:-1]
+        if int(log_off[0]) < 0 or (lens < 0).any() or int(log_off[-1]) > tot:
+            raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
+        step_len = lens[train_log] if S else np.zeros(0, np.int64)
+        train_off = np.concatenate([[0], np.cumsum([len(tr) for tr in trains], dtype=np.int64)]).astype(np.int64)
+        csum = np.concatenate([[0], np.cumsum(step_len, dtype=np.int64)])
+        res_off = np.concatenate([[0], np.cumsum(csum[train_off[1:]] - csum[train_off[:-1]], dtype=np.int64)])
+        conf_off = csum.astype(np.int64)  # (a step has at most as many conflicts as its log has ops)
+        n_out, n_conf = int(res_off[-1]), int(conf_off[-1])
+        alt = np.zeros(tot, np.int32) if v1_alt is None else np.ascontiguousarray(v1_alt, dtype=np.int32)
+        lay = self._compose_layout(tot, [("v1_alt", tot * 4), ("log_off", (L + 1) * 8), ("train_off", (R + 1) * 8),
+                                         ("train_log", S * 4), ("res_off", (R + 1) * 8), ("conf_off", (S + 1) * 8)],
+                                   n_out, 16 * n_conf, 0)
+        lay["step_counts"] = lay["counts"] + _al(16 * R)
+        lay["out_bytes"] = lay["step_counts"] + 16 * S
+        q = lay["q"]
+        t1, t2 = self._staged_call(
+            self.main, lib().smx_compose_train_workspace_bytes, (L, R, S, n_out, 0), lay,
+            [(getattr(lsoa, name), lay[name], tot * dt.itemsize) for name, dt, _ in OP_COLS],
+            (("v1_alt", alt), ("log_off", log_off), ("train_off", train_off), ("train_log", train_log),
+             ("res_off", res_off), ("conf_off", conf_off)),
+            lambda d0, o0: _abi.SmxTrain(L, tot, R, S, int(lsoa.n_sym), n_out, d0 + lay["log_off"],
+                                         *[d0 + lay[name] for name, _, _ in OP_COLS], d0 + lay["v1_alt"],
+                                         d0 + lay["train_off"], d0 + lay["train_log"], d0 + lay["res_off"],
+                                         o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"], d0 + lay["conf_off"],
+                                         o0 + lay["counts"], o0 + lay["step_counts"], 0, int(empty_str)),
+            lambda arg, ws, nbytes, st: lib().smx_compose_train(arg, ws, nbytes, 0, st))
+        hout = self.main.hout
+        counts = hout[lay["counts"]: lay["counts"] + 16 * R].view(np.int64).tolist()
+        sc = hout[lay["step_counts"]: lay["step_counts"] + 16 * S].view(np.int64).tolist()
+        conf = hout[lay["conf"]: lay["conf"] + 16 * n_conf].view(np.int32).reshape(-1, 4)
+        res = []
+        for r in range(R):
+            k, landed = counts[2 * r], counts[2 * r + 1]
+            if k < 0:
+                raise SmxError(-1, f"train {r}: invalid input")
+            steps = []
+            for g in range(int(train_off[r]), int(train_off[r + 1])):
+                oc, c = sc[2 * g + 1], int(conf_off[g])
+                if oc == -1:
+                    raise SmxError(-1, f"train {r}, step {g - int(train_off[r])}: invalid input: sym >= n_sym or kind >= 18")
+                steps.append((sc[2 * g], oc, conf[c: c + max(oc, 0)].copy()))
+            o = int(res_off[r])
+            res.append(tuple(hout[f * q + 4 * o: f * q + 4 * (o + k)].view(np.int32).copy() for f in range(4))
+                       + (landed, steps))
+        self.last = _last(pack_s=t1 - t0, device_s=t2 - t1, unpack_s=time.perf_counter() - t2, in_bytes=lay["in_bytes"])
+        return res
+
     # -- conflict screen (smx_screen): many pairs of logs stored once, conflicts only ---------
 
     @staticmethod
@@ -820,6 +893,11 @@ def compose_soa_shared(ssoa, shared_is_b: bool = False, device: str = "cuda", la
 def compose_pairs_soa(lsoa, pairs, device: str = "cuda", large: bool = False, large_max: Optional[int] = None):
     """ComposeSession.compose_pairs on the thread's free session: the (i, j) of `pairs` over a LogsSoA in one batch."""
     return _free_session(device).compose_pairs(lsoa, pairs, large=large, large_max=large_max)
+
+
+def compose_trains_soa(lsoa, trains, device: str = "cuda", v1_alt=None, empty_str: int = -1):
+    """ComposeSession.compose_trains on the thread's free session: the trains over a LogsSoA in one call."""
+    return _free_session(device).compose_trains(lsoa, trains, v1_alt=v1_alt, empty_str=empty_str)
 
 
 def screen_soa(lsoa, pairs, device: str = "cuda", large: bool = False):

@@ -19,7 +19,7 @@ import numpy as np
 
 from ._abi import BATCH_MAX_OPS
 from ._session import ComposeSession, dropin_session
-from .marshal import marshal_logs, marshal_native, marshal_shared
+from .marshal import marshal_logs, marshal_native, marshal_shared, move_file_alt
 from .materialize import conflict_factory, materialize_conflicts, materialize_ops_native
 
 
@@ -133,6 +133,62 @@ def compose_pairs(logs: Sequence[Sequence[Any]], pairs: Optional[Sequence[Tuple[
             k = np.concatenate([kind[off[i]: off[i + 1]], kind[off[j]: off[j + 1]]])
             res.append((materialize_ops_native(both, k, lsoa.strings, order, addr, file, ctx),
                         materialize_conflicts(both, cpairs)))
+    return res
+
+
+def _train_on_host(logs: Sequence[Sequence[Any]], train: Sequence[int]) -> Tuple[List[Any], List[List[Any]]]:
+    """One train as the host loop over compose_oplogs with eviction (any size)."""
+    acc: List[Any] = []
+    steps: List[List[Any]] = []
+    for l in train:
+        out, conf = compose_oplogs(acc, logs[l])
+        steps.append(conf)
+        if not conf:
+            acc = out
+    return acc, steps
+
+
+def compose_train(logs: Sequence[Sequence[Any]],
+                  trains: Optional[Sequence[Sequence[int]]] = None) -> List[Tuple[List[Any], List[List[Any]]]]:
+    """Merge trains over logs given once.  A train takes its logs in order: each is composed
+    against what landed before it, ``compose_oplogs(acc, log)``; a log that conflicts is put
+    off the train (as ``semmerge`` exits before applying anything) and the next one goes on
+    against what landed; else the composed ops become ``acc``.  ``trains``: lists of log
+    indices (a log may be in many trains, and more than once in one); ``None``: one train of
+    all the logs in order.  Per train the result is ``(ops, steps)``: the ops the last landed
+    step leaves, and per step its conflicts (an empty list: the step landed) -- equal to that
+    host loop.  Every log is marshalled and copied to the GPU once and all the trains run in one
+    call (one copy in, one smx_compose_train, one copy back, one sync); the ops are materialised
+    once per train.  A train whose accumulator and next log exceed 2048 ops runs as the host
+    loop instead.  An index outside the logs raises ``IndexError``.  Inputs are never mutated."""
+    ops = [list(x) for x in logs]
+    if trains is None:
+        trains = [list(range(len(ops)))]
+    trains = [[int(l) for l in tr] for tr in trains]
+    for r, tr in enumerate(trains):
+        for l in tr:
+            if not 0 <= l < len(ops):
+                raise IndexError(f"train {r}: log {l} outside the {len(ops)} logs")
+    if not trains:
+        return []
+    make = conflict_factory()
+    res: List[Any] = []
+    with dropin_session() as sess:
+        lsoa = marshal_logs(ops)
+        flat = [o for x in ops for o in x]
+        alt, empty = move_file_alt(flat, lsoa.kind, lsoa.strings)
+        found = sess.compose_trains(lsoa, trains, v1_alt=alt, empty_str=empty)
+    for tr, (src, addr, file, ctx, _, steps) in zip(trains, found):
+        if any(oc == -2 for _, oc, _ in steps):
+            res.append(_train_on_host(ops, tr))
+            continue
+        out = materialize_ops_native(flat, lsoa.kind, lsoa.strings, src, addr, file, ctx)
+        conf = []
+        for _, _, recs in steps:
+            a = materialize_ops_native(flat, lsoa.kind, lsoa.strings, recs[:, 0], recs[:, 2], recs[:, 3],
+                                       np.full(len(recs), -1, np.int32)) if len(recs) else []
+            conf.append([make(x, flat[b]) for x, b in zip(a, recs[:, 1].tolist())])
+        res.append((out, conf))
     return res
 
 

@@ -2,7 +2,8 @@
 // smx_compose_batch_shared with their _ex forms and smx_compose_pairs (kernels in smx_batch.h
 // and smx_batch_large.h) and smx_screen /
 // smx_screen_ex (kernels in smx_screen.h), and smx_screen_candidates (kernels in smx_cand.h,
-// DESIGN.md §14), which has a shape of its own: a sort and a bit matrix, no size classes.
+// DESIGN.md §14), which has a shape of its own: a sort and a bit matrix, no size classes; and
+// smx_compose_train (kernels in smx_train.h), the class launch over trains.
 //
 // All three have one shape: a pre-pass sorts the items (merges, pairs) into three size
 // classes, then one kernel per class runs its list on a grid capped by what the device
@@ -19,6 +20,7 @@
 #include "smx_batch_large.h"
 #include "smx_screen.h"
 #include "smx_cand.h"
+#include "smx_train.h"
 
 // The kernels with a residency-capped grid, and the threads of a workgroup of each.
 enum {
@@ -32,7 +34,8 @@ enum {
   R_LARGE_SHARED = 13,
   R_PAIRS = 14,
   R_LARGE_PAIRS = 17,
-  R_N = 18
+  R_TRAIN = 18,
+  R_N = 21
 };
 template <typename B>
 using BatchKernel = void (*)(B, const u32*, const u32*);
@@ -43,6 +46,9 @@ static constexpr BatchKernel<B> kBatchKernels[BATCH_CLASSES] = {
 typedef void (*ScreenKernel)(ScreenArgs, ScreenWs, const u32*, const u32*);
 static constexpr ScreenKernel kScreenKernels[SCREEN_CLASSES] = {
     k_screen_pairs<screen_class_cap(0)>, k_screen_pairs<screen_class_cap(1)>, k_screen_pairs<screen_class_cap(2)>};
+typedef void (*TrainKernel)(smx_train, TrainWs, const u32*, const u32*);
+static constexpr TrainKernel kTrainKernels[BATCH_CLASSES] = {
+    k_compose_train<batch_class_cap(0)>, k_compose_train<batch_class_cap(1)>, k_compose_train<batch_class_cap(2)>};
 static constexpr int kBatchCaps[BATCH_CLASSES] = {batch_class_cap(0), batch_class_cap(1), batch_class_cap(2)};
 static constexpr int kScreenCaps[SCREEN_CLASSES] = {screen_class_cap(0), screen_class_cap(1), screen_class_cap(2)};
 
@@ -65,7 +71,8 @@ static int resident_of(const int** out) {
       fn[R_BATCH + c] = (const void*)kBatchKernels<smx_batch>[c];
       fn[R_SHARED + c] = (const void*)kBatchKernels<smx_batch_shared>[c];
       fn[R_PAIRS + c] = (const void*)kBatchKernels<smx_pairs>[c];
-      threads[R_BATCH + c] = threads[R_SHARED + c] = threads[R_PAIRS + c] = kBatchCaps[c] / 2;
+      fn[R_TRAIN + c] = (const void*)kTrainKernels[c];
+      threads[R_BATCH + c] = threads[R_SHARED + c] = threads[R_PAIRS + c] = threads[R_TRAIN + c] = kBatchCaps[c] / 2;
     }
     fn[R_EXTRACT] = (const void*)k_screen_extract;
     threads[R_EXTRACT] = SCREEN_T1;
@@ -326,6 +333,60 @@ extern "C" int smx_compose_batch_shared(const smx_batch_shared* b, void* workspa
 extern "C" int smx_compose_pairs(const struct smx_pairs* b, void* workspace, size_t workspace_bytes, uint32_t flags,
                                  void* stream) {
   return batch_run(__func__, b, workspace, workspace_bytes, flags, stream);
+}
+
+extern "C" int smx_compose_train_workspace_bytes(int64_t n_logs, int64_t n_trains, int64_t n_steps, int64_t n_out,
+                                                 uint32_t flags, size_t* bytes) {
+  if (flags) return smx_set_error(SMX_E_ARG, "unknown smx_compose_train flag");
+  if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
+  if (n_logs < 0 || n_logs > 0x7fffffffll || n_trains < 0 || n_trains > 0x7fffffffll || n_steps < 0 ||
+      n_steps > 0x7fffffffll || n_out < 0 || n_out > 0x7fffffffll)
+    return smx_set_error(SMX_E_ARG, "n_logs, n_trains, n_steps or n_out outside 0 .. 2^31 - 1");
+  *bytes = train_ws_bytes(n_logs, n_trains, n_out);
+  return SMX_OK;
+}
+
+// The checks; then the pre-pass (k_train_offsets, k_train_classify) and the three classes'
+// k_compose_train.
+extern "C" int smx_compose_train(const struct smx_train* b, void* workspace, size_t workspace_bytes, uint32_t flags,
+                                 void* stream) {
+  if (flags) return smx_set_error(SMX_E_ARG, "unknown smx_compose_train flag");
+  if (!b) return smx_set_error(SMX_E_ARG, "null train struct");
+  if (b->n_logs < 0 || b->n_total < 0 || b->n_trains < 0 || b->n_steps < 0 || b->n_sym < 0 || b->n_out < 0 ||
+      b->grid_cap < 0 || b->empty_str < SMX_NONE)
+    return smx_set_error(SMX_E_ARG, "negative size, or empty_str below SMX_NONE");
+  if (b->n_sym > 0xffffffffll) return smx_set_error(SMX_E_ARG, "n_sym over 2^32 - 1");
+  if (b->n_logs > 0x7fffffffll || b->n_trains > 0x7fffffffll || b->n_steps > 0x7fffffffll)
+    return smx_set_error(SMX_E_ARG, "n_logs, n_trains or n_steps over 2^31 - 1");
+  if (b->n_total > 0x7fffffffll || b->n_out > 0x7fffffffll)
+    return smx_set_error(SMX_E_ARG, "n_total or n_out over 2^31 - 1");
+  if (b->n_trains == 0) return SMX_OK;
+  if (!b->train_off || !b->res_off || !b->counts) return smx_set_error(SMX_E_ARG, "null train_off / res_off / counts");
+  if (b->n_logs > 0 && !b->log_off) return smx_set_error(SMX_E_ARG, "null log_off");
+  if (b->n_steps > 0 && (!b->train_log || !b->conf_off || !b->step_counts || !b->conflicts))
+    return smx_set_error(SMX_E_ARG, "null train_log / conf_off / step_counts / conflicts");
+  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1))
+    return smx_set_error(SMX_E_ARG, "null column");
+  if (b->n_total > 0 && b->empty_str >= 0 && !b->v1_alt) return smx_set_error(SMX_E_ARG, "null v1_alt with empty_str set");
+  if (b->n_out > 0 && (!b->src || !b->addr || !b->file || !b->ctx)) return smx_set_error(SMX_E_ARG, "null result array");
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < train_ws_bytes(b->n_logs, b->n_trains, b->n_out))
+    return smx_set_error(SMX_E_WORKSPACE,
+                         "workspace too small or not 8-byte aligned (smx_compose_train_workspace_bytes)");
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  try {
+    const int* resident;
+    if (int rc = resident_of(&resident)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const TrainWs w = train_ws(workspace, b->n_logs, b->n_trains, b->n_out);
+    hipLaunchKernelGGL(k_train_offsets, dim3(1), dim3(1024), 0, st, *b, w);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_train_classify, dim3((unsigned)SMX_CEIL_DIV(b->n_trains, (i64)256)), dim3(256), 0, st, *b, w);
+    HIP_TRY(hipGetLastError());
+    return launch_classes(kTrainKernels, kBatchCaps, resident + R_TRAIN, b->n_trains, b->grid_cap, st, w.cnt, w.lists,
+                          w.stride, *b, w);
+  } catch (const std::exception& e) {
+    return smx_set_error(SMX_E_HIP, e.what());
+  }
 }
 
 extern "C" int smx_screen_ex_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_pairs, uint32_t flags,

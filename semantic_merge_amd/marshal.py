@@ -385,3 +385,26 @@ def marshal_logs(logs: Sequence[Sequence[Any]], cols: Optional[dict] = None) -> 
     s = marshal_shared((), logs, cols)
     return LogsSoA(s.off, s.kind, s.ts, s.oid_hi, s.oid_lo, s.sym, s.v0, s.v1, s.n_sym, s.strings,
                    s.ts_mode, s.id_mode)
+
+
+def move_file_alt(ops: Sequence[Any], kind: np.ndarray, strings: List[str]):
+    """(v1_alt, empty_str) of include/smx.h's smx_train over `ops` in column order.  A move's v1
+    is the id of ``str(newFile or file)``: once a train's step has given the move an empty
+    newFile, marshalling it again falls through to its own ``file``.  v1_alt holds that value
+    per move (the id of ``str(params["file"])``, -1 for None or none; strings that are new are
+    appended to `strings`), and empty_str is the id of "" (-1: not among the strings, and no
+    step can give it)."""
+    alt = np.full(len(ops), -1, np.int32)
+    if "" not in strings:
+        return alt, -1
+    ids = {s: i for i, s in enumerate(strings)}
+    for k in np.flatnonzero(np.asarray(kind) == KIND_MOVE).tolist():
+        f = ops[k].params.get("file")
+        if f is not None:
+            f = str(f)
+            got = ids.get(f)
+            if got is None:
+                got = ids[f] = len(strings)
+                strings.append(f)
+            alt[k] = got
+    return alt, ids[""]
