@@ -17,6 +17,8 @@
  *                    (what semmerge/__main__.py:65-69 does to one merge, per step)
  *   smx_screen    <- the conflict list of the same loop alone (what semmerge/__main__.py
  *                    looks at first), for many pairs of logs, from the logs' renames
+ *   smx_screen_train <- the conflict lists of smx_compose_train's steps alone, from the
+ *                    logs' renames, for trains of any size
  *   smx_rga_replay <- semmerge/crdt.py:23-57  RGA.insert/move/delete/materialize,
  *                    batched over many independent lists
  *   smx_rga_replay_onto <- the same, for many event streams replayed onto base lists that
@@ -612,6 +614,74 @@ int smx_compose_train_workspace_bytes(int64_t n_logs, int64_t n_trains, int64_t 
  * call; n_trains = 0 returns SMX_OK and launches nothing. */
 int smx_compose_train(const struct smx_train* t, void* workspace, size_t workspace_bytes, uint32_t flags,
                       void* stream);
+
+/*
+ * Conflict screen of merge trains: which steps of smx_compose_train's trains have
+ * DivergentRename conflicts, and which ones, from the logs' renames alone.
+ * The logs and the trains are laid out as smx_train takes them, the columns as smx_screen
+ * takes them (no v1, no n_sym).  A pair's conflict list is a function of the two logs' renames
+ * (smx_screen above), and a step that lands leaves every rename's timestamp, id, symbol and
+ * newName as they were.  So, as far as conflicts go, a train's accumulator is a sorted list of
+ * rename records: a step is smx_screen's walk of that list (A) against the log's sorted renames
+ * (B), and a step without conflicts merges the two stably, A first on equal (ts, oid_hi,
+ * oid_lo).  Nothing is composed, and no size is refused: there is no -2.
+ *
+ * For every valid train and step g, step_counts[2g+1] and the written records equal what
+ * smx_compose_train reports for that step wherever it reports a count: the number of conflicts,
+ * and per conflict the first two words of its record -- the A op's column index and the B op's
+ * column index, in the reference's order.
+ *
+ *   step_counts  [2g]: the renames in the accumulator after step g, whatever happened;
+ *                [2g+1]: >= 0 the step's conflicts (0: it landed; a log without renames
+ *                        lands and leaves the accumulator's renames as they were);
+ *                        -1 a log index outside [0, n_logs), a log invalid under smx_screen's
+ *                           log_off rules, or an op with kind >= 18 in it: the accumulator
+ *                           stays and the train goes on with its next log
+ *   conflicts    per step g the first conf_off[g+1] - conf_off[g] records at conflicts[2 *
+ *                conf_off[g]], two int32 each, the full number in step_counts[2g+1], nothing at
+ *                or past the step's region (a negative or decreasing conf_off gives the step
+ *                none).  conflicts and conf_off both NULL: capacity 0 everywhere (counts only).
+ *   counts       [2r]: the renames in train r's final accumulator; [2r+1]: the steps that landed
+ *   acc_off      train r may hold acc_off[r+1] - acc_off[r] renames: at least the sum of the
+ *                rename counts of its steps' valid logs (a log counted once per step)
+ *
+ * A train whose train_off or acc_off entries are negative, below an earlier entry, decreasing
+ * or past n_steps / n_acc, or whose region is smaller than that sum (checked on the device from
+ * the extracted counts), reports counts -1, -1 and writes nothing else.  Failed trains and steps
+ * never touch their neighbours.
+ *
+ * Stream-ordered as smx_compose_train: seven launches whatever the data, no host
+ * synchronisation, no allocation, no read-back; the call clears the workspace state it needs,
+ * so one workspace serves any sequence of calls, smx_screen_ex's among them where it is large
+ * enough.  Every log's renames are extracted and sorted once, as with SMX_SCREEN_LARGE; one
+ * workgroup runs a train's steps one after another, a step of more than 2048 renames in rounds.
+ * flags must be 0.
+ */
+struct smx_screen_train {
+  int64_t n_logs, n_total, n_trains, n_steps, n_acc;
+  const int64_t* log_off;                 /* device [n_logs+1], as smx_screen */
+  const uint8_t* kind; const uint64_t* ts, *oid_hi, *oid_lo;
+  const uint32_t* sym; const int32_t* v0;          /* as smx_screen: n_total entries, no v1, no n_sym */
+  const int64_t* train_off;               /* device [n_trains+1], into train_log, as smx_train */
+  const int32_t* train_log;               /* device [n_steps]: log indices */
+  const int64_t* acc_off;                 /* device [n_trains+1]: train r's room in renames, entries up to n_acc */
+  int32_t* conflicts; const int64_t* conf_off;     /* 2 int32 per record; conf_off [n_steps+1], in records;
+                                                      both NULL: counts only */
+  int64_t* counts;                        /* [2*n_trains]: renames in the final accumulator, landed steps */
+  int64_t* step_counts;                   /* [2*n_steps]: the accumulator's renames after the step, its outcome */
+  int32_t grid_cap;                       /* as smx_batch; also caps the per-log launches */
+};
+/* Workspace (8-byte aligned), monotone in its arguments: 4 bytes per log, 20 per train, 44 per
+ * op and 72 per entry of n_acc (all five sizes in 0 .. 2^31 - 1; n_steps is not stored; flags 0). */
+int smx_screen_train_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_trains, int64_t n_steps,
+                                     int64_t n_acc, uint32_t flags, size_t* bytes);
+/* SMX_E_ARG (a non-zero flag; then a null struct, negative sizes, a size over 2^31 - 1,
+ * grid_cap < 0, exactly one of conflicts / conf_off null; a null train_off / acc_off / counts, a
+ * null log_off with n_logs > 0, a null train_log / step_counts with n_steps > 0, a null column
+ * with n_total > 0) and SMX_E_WORKSPACE (too small, or not 8-byte aligned) are reported before
+ * any HIP call; n_trains = 0 returns SMX_OK and launches nothing. */
+int smx_screen_train(const struct smx_screen_train* t, void* workspace, size_t workspace_bytes, uint32_t flags,
+                     void* stream);
 
 /*
  * Sharded single merge: one process per GPU, shard r of G.

@@ -3,7 +3,7 @@ from .ops import Op, Target  # noqa: F401
 from .conflict import Conflict  # noqa: F401
 
 __all__ = ["Op", "Target", "Conflict", "compose_oplogs", "compose_many", "compose_against",
-           "compose_pairs", "compose_train", "screen_conflicts", "screen_all"]
+           "compose_pairs", "compose_train", "screen_conflicts", "screen_all", "screen_train"]
 
 
 def __getattr__(name):
@@ -29,4 +29,7 @@ def __getattr__(name):
     if name == "screen_all":
         from .compose import screen_all
         return screen_all
+    if name == "screen_train":
+        from .compose import screen_train
+        return screen_train
     raise AttributeError(name)

@@ -190,10 +190,11 @@ def rga_replay_onto_device(batch, device: str = "cuda", tombstones: bool = False
 # (bench.py, the tests and the tools import them from _lib); resolved on first use, because
 # both modules import this one.
 _MOVED = {**dict.fromkeys(("ComposeSession", "session", "dropin_session", "compose_soa", "compose_soa_many",
-                          "compose_soa_shared", "compose_pairs_soa", "compose_trains_soa", "screen_soa", "screen_all_soa"),
+                          "compose_soa_shared", "compose_pairs_soa", "compose_trains_soa", "screen_soa", "screen_all_soa",
+                          "screen_trains_soa"),
                           "_session"),
           **dict.fromkeys(("DeviceCompose", "DeviceBatch", "DeviceBatchShared", "DevicePairs", "DeviceTrains", "DeviceScreen",
-                           "DeviceCandidates"), "_rigs")}
+                           "DeviceScreenTrains", "DeviceCandidates"), "_rigs")}
 
 
 def __getattr__(name: str):

@@ -463,6 +463,89 @@ class DeviceScreen(_DeviceMany):
                                    0 if self.null_conf else self._idx[3].data_ptr(), self.counts.data_ptr(), grid_cap)
 
 
+class DeviceScreenTrains(_DeviceMany):
+    """Device-resident inputs, outputs and workspace for repeated smx_screen_train calls on a
+    LogsSoA and a list of trains, each a list of log indices (tests, tools/screen_train_probe.py).
+    The optional arguments reach the corners of the C ABI (include/smx.h smx_screen_train):
+    conf_caps     per-step capacities in conflict records (default: the renames of the step's
+                  log, which always suffices); "null": conflicts and conf_off are NULL;
+    grid_cap      smx_screen_train.grid_cap;
+    log_off       the offsets passed instead of the LogsSoA's own;
+    train_off     the offsets into the steps passed instead of the trains' own;
+    acc_off       the accumulator offsets passed (default: the sum of its logs' rename counts per
+                  train, one after another; a log index outside the logs counts as empty);
+    n_total, n_steps, n_acc  passed instead of the real ones;
+    fill          every output word (conflict records, counts, step counts) starts as this value,
+                  and CONF_GUARD such words follow the last regions."""
+
+    _OUT = ("conf", "counts", "step_counts")
+
+    def __init__(self, lsoa, trains, device: str = "cuda", conf_caps=None, grid_cap: int = 0, log_off=None,
+                 train_off=None, acc_off=None, n_total: Optional[int] = None, n_steps: Optional[int] = None,
+                 n_acc: Optional[int] = None, fill: Optional[int] = None) -> None:
+        self._open(device)
+        torch, dev = self.torch, self.device
+        self.lsoa = lsoa
+        L = self.n_logs = lsoa.n_logs
+        self.trains = [[int(l) for l in tr] for tr in trains]
+        R = self.n_trains = len(self.trains)
+        self.train_log = np.asarray([l for tr in self.trains for l in tr], np.int32)
+        S = self.n_steps = len(self.train_log)
+        own_off = np.concatenate([[0], np.cumsum([len(tr) for tr in self.trains], dtype=np.int64)]).astype(np.int64)
+        self.train_off = np.asarray(own_off if train_off is None else train_off, np.int64).reshape(R + 1)
+        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
+        tot = self.n_total = int(lsoa.n_total)
+        ren = _rename_counts(lsoa.kind, lsoa.log_off)
+        ok = (self.train_log >= 0) & (self.train_log < L)
+        self.step_ren = np.where(ok, ren[np.where(ok, self.train_log, 0)], 0).astype(np.int64) if L \
+            else np.zeros(S, np.int64)
+        if acc_off is None:
+            csum = np.concatenate([[0], np.cumsum(self.step_ren, dtype=np.int64)])
+            acc_off = np.concatenate([[0], np.cumsum(csum[own_off[1:]] - csum[own_off[:-1]], dtype=np.int64)])
+        self.acc_off = np.asarray(acc_off, np.int64).reshape(R + 1)
+        self.n_acc = max(int(self.acc_off.max()), 0) if R else 0
+        self.null_conf = isinstance(conf_caps, str) and conf_caps == "null"
+        self._upload_cols([lsoa], SCREEN_COLS)
+        self.conf_off = np.zeros(S + 1, np.int64)
+        if not self.null_conf:
+            np.cumsum(self.step_ren if conf_caps is None else conf_caps, out=self.conf_off[1:])
+        f = 0 if fill is None else fill
+        self.conf = torch.full((2 * int(self.conf_off[-1]) + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        self.counts = torch.full((2 * R + self.CONF_GUARD,), f, dtype=torch.int64, device=dev)
+        self.step_counts = torch.full((2 * S + self.CONF_GUARD,), f, dtype=torch.int64, device=dev)
+        n_acc = self.n_acc if n_acc is None else n_acc
+        self._workspace(lib().smx_screen_train_workspace_bytes, L, tot, R, S, max(n_acc, self.n_acc, 0), 0)
+        self._idx = [self._up(self.log_off), self._up(self.train_off), self._up(self.train_log),
+                     self._up(self.acc_off), self._up(self.conf_off)]
+        self._call = lambda arg, ws, nbytes, st: lib().smx_screen_train(arg, ws, nbytes, 0, st)
+        self._arg = _abi.SmxScreenTrain(L, tot if n_total is None else n_total, R, S if n_steps is None else n_steps,
+                                        n_acc, self._idx[0].data_ptr(), *[_ptr(t) for t in self._in],
+                                        self._idx[1].data_ptr(), _ptr(self._idx[2]), self._idx[3].data_ptr(),
+                                        0 if self.null_conf else self.conf.data_ptr(),
+                                        0 if self.null_conf else self._idx[4].data_ptr(), self.counts.data_ptr(),
+                                        self.step_counts.data_ptr(), grid_cap)
+
+    def results(self, raw: Optional[dict] = None):
+        """Per train its failing count (-1), else (n_renames, landed, steps): the renames in the
+        final accumulator, the steps that landed, and per step (the accumulator's renames after
+        it, outcome, its conflict records as an (n, 2) array trimmed to its capacity)."""
+        r = self.raw() if raw is None else raw
+        out = []
+        for t in range(self.n_trains):
+            k, landed = int(r["counts"][2 * t]), int(r["counts"][2 * t + 1])
+            if k < 0:
+                out.append(k)
+                continue
+            steps = []
+            for g in range(int(self.train_off[t]), int(self.train_off[t + 1])):
+                acc, oc = int(r["step_counts"][2 * g]), int(r["step_counts"][2 * g + 1])
+                c = int(self.conf_off[g])
+                nc = min(max(oc, 0), int(self.conf_off[g + 1]) - c)
+                steps.append((acc, oc, r["conf"][2 * c: 2 * (c + nc)].reshape(nc, 2)))
+            out.append((k, landed, steps))
+        return out
+
+
 class DeviceCandidates(_DeviceMany):
     """Device-resident inputs, outputs and workspace for repeated smx_screen_candidates calls
     on a LogsSoA (tests, tools/cand_probe.py).  The optional arguments reach the corners of

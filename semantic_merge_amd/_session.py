@@ -722,6 +722,72 @@ class ComposeSession:
         self._route_pairs(res, routed, lsoa, pairs)
         return res
 
+    # -- the screen of merge trains (smx_screen_train): the steps' conflicts from renames alone --
+
+    def screen_trains(self, lsoa, trains):
+        """Per train of `trains` (lists of log indices over a LogsSoA) what smx_screen_train leaves:
+        (n_renames, landed, steps) -- the renames in the final accumulator, the number of steps that
+        landed, and per step (the accumulator's renames after it, outcome, its conflicts as an
+        (n, 2) int32 array of (A column index, B column index)).  The outcomes and the pairs are
+        smx_compose_train's for the same trains, whatever the sizes: no step is sent back.  One
+        host-to-device copy of the six columns (33 bytes per op, each log once), one
+        smx_screen_train, one copy back, one stream sync.  Invalid input raises SmxError naming
+        the train.  The results are copies.  `last` holds the call's legs, "in_bytes" and "out_bytes"."""
+        t0 = time.perf_counter()
+        trains = [np.asarray(tr, np.int32).reshape(-1) for tr in trains]
+        R, L, tot = len(trains), lsoa.n_logs, int(lsoa.n_total)
+        self.last = _last(("in_bytes", "out_bytes"))
+        if R == 0:
+            return []
+        train_log = np.ascontiguousarray(np.concatenate(trains))
+        S = len(train_log)
+        for r, tr in enumerate(trains):
+            if len(tr) and (int(tr.min()) < 0 or int(tr.max()) >= L):
+                raise SmxError(-1, f"train {r}: a log index outside [0, {L})")
+        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
+        if int(log_off[0]) < 0 or (log_off[1:] < log_off[:-1]).any() or int(log_off[-1]) > tot:
+            raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
+        ren = _rename_counts(lsoa.kind, log_off)
+        step_ren = ren[train_log] if S else np.zeros(0, np.int64)
+        train_off = np.concatenate([[0], np.cumsum([len(tr) for tr in trains], dtype=np.int64)]).astype(np.int64)
+        conf_off = np.concatenate([[0], np.cumsum(step_ren, dtype=np.int64)])  # (at most one conflict per rename of B)
+        acc_off = np.concatenate([[0], np.cumsum(conf_off[train_off[1:]] - conf_off[train_off[:-1]], dtype=np.int64)])
+        n_acc, n_conf = int(acc_off[-1]), int(conf_off[-1])
+        lay = self._layout(tot, [(name, tot * dt.itemsize) for name, dt, _ in SCREEN_COLS]
+                           + [("log_off", (L + 1) * 8), ("train_off", (R + 1) * 8), ("train_log", S * 4),
+                              ("acc_off", (R + 1) * 8), ("conf_off", (S + 1) * 8)], 0, 8 * n_conf, 16 * R)
+        lay["step_counts"] = lay["counts"] + _al(16 * R)
+        lay["out_bytes"] = lay["step_counts"] + 16 * S
+        t1, t2 = self._staged_call(
+            self.main, lib().smx_screen_train_workspace_bytes, (L, tot, R, S, n_acc, 0), lay,
+            [(getattr(lsoa, name), lay[name], tot * dt.itemsize) for name, dt, _ in SCREEN_COLS],
+            (("log_off", log_off), ("train_off", train_off), ("train_log", train_log), ("acc_off", acc_off),
+             ("conf_off", conf_off)),
+            lambda d0, o0: _abi.SmxScreenTrain(L, tot, R, S, n_acc, d0 + lay["log_off"],
+                                               *[d0 + lay[name] for name, _, _ in SCREEN_COLS],
+                                               d0 + lay["train_off"], d0 + lay["train_log"], d0 + lay["acc_off"],
+                                               o0 + lay["conf"], d0 + lay["conf_off"], o0 + lay["counts"],
+                                               o0 + lay["step_counts"], 0),
+            lambda arg, ws, nbytes, st: lib().smx_screen_train(arg, ws, nbytes, 0, st))
+        hout = self.main.hout
+        counts = hout[lay["counts"]: lay["counts"] + 16 * R].view(np.int64).tolist()
+        sc = hout[lay["step_counts"]: lay["step_counts"] + 16 * S].view(np.int64).tolist()
+        conf = hout[lay["conf"]: lay["conf"] + 8 * n_conf].view(np.int32).reshape(-1, 2)
+        res = []
+        for r in range(R):
+            if counts[2 * r] < 0:
+                raise SmxError(-1, f"train {r}: invalid input")
+            steps = []
+            for g in range(int(train_off[r]), int(train_off[r + 1])):
+                oc, c = sc[2 * g + 1], int(conf_off[g])
+                if oc < 0:
+                    raise SmxError(-1, f"train {r}, step {g - int(train_off[r])}: invalid input: kind >= 18")
+                steps.append((sc[2 * g], oc, conf[c: c + oc].copy()))
+            res.append((counts[2 * r], counts[2 * r + 1], steps))
+        self.last = _last(pack_s=t1 - t0, device_s=t2 - t1, unpack_s=time.perf_counter() - t2,
+                          in_bytes=lay["in_bytes"], out_bytes=lay["out_bytes"])
+        return res
+
     # -- candidate pairs (smx_screen_candidates) and the screen of all of them ----------------
 
     @staticmethod
@@ -908,3 +974,8 @@ def screen_soa(lsoa, pairs, device: str = "cuda", large: bool = False):
 def screen_all_soa(lsoa, device: str = "cuda", large: bool = False):
     """ComposeSession.screen_all on the thread's free session: (pairs, [conflict_pairs])."""
     return _free_session(device).screen_all(lsoa, large=large)
+
+
+def screen_trains_soa(lsoa, trains, device: str = "cuda"):
+    """ComposeSession.screen_trains on the thread's free session: the trains' steps screened in one call."""
+    return _free_session(device).screen_trains(lsoa, trains)

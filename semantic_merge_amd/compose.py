@@ -192,6 +192,43 @@ def compose_train(logs: Sequence[Sequence[Any]],
     return res
 
 
+def screen_train(logs: Sequence[Sequence[Any]], trains: Optional[Sequence[Sequence[int]]] = None
+                 ) -> List[List[List[Tuple[Tuple[int, int], Tuple[int, int]]]]]:
+    """Which logs fall off a merge train, and over which ops, without composing anything: per
+    train of ``compose_train(logs, trains)``, per step, the conflicts of that step as
+    ``((log_a, index_a), (log_b, index_b))`` -- the positions in ``logs`` of the two ops of every
+    conflict, in the reference's order; an empty list means the step landed.  ``trains``: lists
+    of log indices (a log may be in many trains, and more than once in one); ``None``: one train
+    of all the logs in order.  The answer comes from the logs' renames alone (one copy in, one
+    smx_screen_train, one copy back, one sync), so trains of any size are served in the one
+    call: no size is refused and no host loop stands behind it.  ``opA`` of the reference's
+    ``Conflict`` is the accumulated clone, whose ``params`` and ``addressId`` a move chain may
+    have changed; that clone comes from ``compose_train``, and this call names the ops only.  An
+    index outside the logs raises ``IndexError``.  Inputs are never mutated."""
+    ops = [list(x) for x in logs]
+    if trains is None:
+        trains = [list(range(len(ops)))]
+    trains = [[int(l) for l in tr] for tr in trains]
+    for r, tr in enumerate(trains):
+        for l in tr:
+            if not 0 <= l < len(ops):
+                raise IndexError(f"train {r}: log {l} outside the {len(ops)} logs")
+    if not trains:
+        return []
+    with dropin_session() as sess:
+        # marshalled straight into the session's pinned staging columns
+        lsoa = marshal_logs(ops, sess.staging_logs(sum(len(x) for x in ops), len(ops), 0))
+        found = sess.screen_trains(lsoa, trains)
+    off = np.asarray(lsoa.log_off, np.int64)
+
+    def where(cols):
+        log = np.searchsorted(off, cols, "right") - 1
+        return list(zip(log.tolist(), (cols - off[log]).tolist()))
+
+    return [[list(zip(where(recs[:, 0].astype(np.int64)), where(recs[:, 1].astype(np.int64)))) for _, _, recs in steps]
+            for _, _, steps in found]
+
+
 def screen_conflicts(logs: Sequence[Sequence[Any]],
                      pairs: Optional[Sequence[Tuple[int, int]]] = None, large: bool = False) -> List[List[Any]]:
     """``[compose_oplogs(logs[i], logs[j])[1] for i, j in pairs]`` -- the DivergentRename

@@ -3,7 +3,8 @@
 // and smx_batch_large.h) and smx_screen /
 // smx_screen_ex (kernels in smx_screen.h), and smx_screen_candidates (kernels in smx_cand.h,
 // DESIGN.md §14), which has a shape of its own: a sort and a bit matrix, no size classes; and
-// smx_compose_train (kernels in smx_train.h), the class launch over trains.
+// smx_compose_train (kernels in smx_train.h), the class launch over trains, and
+// smx_screen_train (kernels in smx_screen_train.h), the screen's over trains.
 //
 // All three have one shape: a pre-pass sorts the items (merges, pairs) into three size
 // classes, then one kernel per class runs its list on a grid capped by what the device
@@ -21,6 +22,7 @@
 #include "smx_screen.h"
 #include "smx_cand.h"
 #include "smx_train.h"
+#include "smx_screen_train.h"
 
 // The kernels with a residency-capped grid, and the threads of a workgroup of each.
 enum {
@@ -35,7 +37,8 @@ enum {
   R_PAIRS = 14,
   R_LARGE_PAIRS = 17,
   R_TRAIN = 18,
-  R_N = 21
+  R_SCREEN_TRAIN = 21,
+  R_N = 24
 };
 template <typename B>
 using BatchKernel = void (*)(B, const u32*, const u32*);
@@ -49,6 +52,9 @@ static constexpr ScreenKernel kScreenKernels[SCREEN_CLASSES] = {
 typedef void (*TrainKernel)(smx_train, TrainWs, const u32*, const u32*);
 static constexpr TrainKernel kTrainKernels[BATCH_CLASSES] = {
     k_compose_train<batch_class_cap(0)>, k_compose_train<batch_class_cap(1)>, k_compose_train<batch_class_cap(2)>};
+typedef void (*ScreenTrainKernel)(ScreenTrainArgs, ScreenWs, const u32*, const u32*);
+static constexpr ScreenTrainKernel kScreenTrainKernels[SCREEN_CLASSES] = {
+    k_screen_train<screen_class_cap(0)>, k_screen_train<screen_class_cap(1)>, k_screen_train<screen_class_cap(2)>};
 static constexpr int kBatchCaps[BATCH_CLASSES] = {batch_class_cap(0), batch_class_cap(1), batch_class_cap(2)};
 static constexpr int kScreenCaps[SCREEN_CLASSES] = {screen_class_cap(0), screen_class_cap(1), screen_class_cap(2)};
 
@@ -78,7 +84,8 @@ static int resident_of(const int** out) {
     threads[R_EXTRACT] = SCREEN_T1;
     for (int c = 0; c < SCREEN_CLASSES; ++c) {
       fn[R_SCREEN + c] = (const void*)kScreenKernels[c];
-      threads[R_SCREEN + c] = kScreenCaps[c] / 2;
+      fn[R_SCREEN_TRAIN + c] = (const void*)kScreenTrainKernels[c];
+      threads[R_SCREEN + c] = threads[R_SCREEN_TRAIN + c] = kScreenCaps[c] / 2;
     }
     fn[R_EXTRACT_LARGE] = (const void*)k_screen_extract_large;
     threads[R_EXTRACT_LARGE] = SCREEN_TL;
@@ -384,6 +391,73 @@ extern "C" int smx_compose_train(const struct smx_train* b, void* workspace, siz
     HIP_TRY(hipGetLastError());
     return launch_classes(kTrainKernels, kBatchCaps, resident + R_TRAIN, b->n_trains, b->grid_cap, st, w.cnt, w.lists,
                           w.stride, *b, w);
+  } catch (const std::exception& e) {
+    return smx_set_error(SMX_E_HIP, e.what());
+  }
+}
+
+extern "C" int smx_screen_train_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_trains, int64_t n_steps,
+                                                int64_t n_acc, uint32_t flags, size_t* bytes) {
+  if (flags) return smx_set_error(SMX_E_ARG, "unknown smx_screen_train flag");
+  if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
+  for (int64_t v : {n_logs, n_total, n_trains, n_steps, n_acc})
+    if (v < 0 || v > 0x7fffffffll)
+      return smx_set_error(SMX_E_ARG, "n_logs, n_total, n_trains, n_steps or n_acc outside 0 .. 2^31 - 1");
+  *bytes = screen_train_ws_bytes(n_logs, n_total, n_trains, n_acc);
+  return SMX_OK;
+}
+
+// min(resident, items) workgroups as capped_grid, and one where there is no item: the per-log
+// launches of a call whose trains name no log.
+static dim3 capped_grid_min1(int resident, i64 items, i64 grid_cap) {
+  return capped_grid(resident, items > 0 ? items : 1, grid_cap);
+}
+
+// The checks; then the pre-pass (k_screen_train_offsets), the screen's two extraction kernels
+// over every log, k_screen_train_classify and the three classes' k_screen_train.
+extern "C" int smx_screen_train(const struct smx_screen_train* b, void* workspace, size_t workspace_bytes,
+                                uint32_t flags, void* stream) {
+  if (flags) return smx_set_error(SMX_E_ARG, "unknown smx_screen_train flag");
+  if (!b) return smx_set_error(SMX_E_ARG, "null screen train struct");
+  if (b->n_logs < 0 || b->n_total < 0 || b->n_trains < 0 || b->n_steps < 0 || b->n_acc < 0 || b->grid_cap < 0)
+    return smx_set_error(SMX_E_ARG, "negative size");
+  if (b->n_logs > 0x7fffffffll || b->n_total > 0x7fffffffll || b->n_trains > 0x7fffffffll ||
+      b->n_steps > 0x7fffffffll || b->n_acc > 0x7fffffffll)
+    return smx_set_error(SMX_E_ARG, "n_logs, n_total, n_trains, n_steps or n_acc over 2^31 - 1");
+  if ((b->conflicts == nullptr) != (b->conf_off == nullptr))
+    return smx_set_error(SMX_E_ARG, "conflicts and conf_off are both null or both set");
+  if (b->n_trains == 0) return SMX_OK;
+  if (!b->train_off || !b->acc_off || !b->counts) return smx_set_error(SMX_E_ARG, "null train_off / acc_off / counts");
+  if (b->n_logs > 0 && !b->log_off) return smx_set_error(SMX_E_ARG, "null log_off");
+  if (b->n_steps > 0 && (!b->train_log || !b->step_counts))
+    return smx_set_error(SMX_E_ARG, "null train_log / step_counts");
+  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0))
+    return smx_set_error(SMX_E_ARG, "null column");
+  if (!workspace || ((uintptr_t)workspace & 7) ||
+      workspace_bytes < screen_train_ws_bytes(b->n_logs, b->n_total, b->n_trains, b->n_acc))
+    return smx_set_error(SMX_E_WORKSPACE,
+                         "workspace too small or not 8-byte aligned (smx_screen_train_workspace_bytes)");
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  try {
+    const int* resident;
+    if (int rc = resident_of(&resident)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const ScreenWs w = screen_ws(workspace, b->n_logs, screen_train_records(b->n_total, b->n_acc), b->n_trains);
+    const ScreenTrainWs y = screen_train_ws(workspace, b->n_logs, b->n_total, b->n_trains, b->n_acc);
+    const ScreenArgs s = screen_train_logs(*b);
+    hipLaunchKernelGGL(k_screen_train_offsets, dim3(1), dim3(1024), 0, st, *b, w, y);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_extract, capped_grid_min1(resident[R_EXTRACT], b->n_logs, b->grid_cap), dim3(SCREEN_T1),
+                       0, st, s, w);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_extract_large, capped_grid_min1(resident[R_EXTRACT_LARGE], b->n_logs, b->grid_cap),
+                       dim3(SCREEN_TL), 0, st, s, w, y.x);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_train_classify, dim3((unsigned)SMX_CEIL_DIV(b->n_trains, (i64)256)), dim3(256), 0, st,
+                       *b, w, y);
+    HIP_TRY(hipGetLastError());
+    return launch_classes(kScreenTrainKernels, kScreenCaps, resident + R_SCREEN_TRAIN, b->n_trains, b->grid_cap, st,
+                          w.cnt, w.lists, w.list_stride, *b, w);
   } catch (const std::exception& e) {
     return smx_set_error(SMX_E_HIP, e.what());
   }
