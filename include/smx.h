@@ -15,6 +15,9 @@
  *   smx_compose_train <- that loop in a loop: a merge train over such logs, each log
  *                    composed against what landed before it, conflicting logs put off
  *                    (what semmerge/__main__.py:65-69 does to one merge, per step)
+ *   smx_train_stage, smx_train_land <- one step of that loop for trains of any size: the
+ *                    materialise, marshal and copy between two compose_oplogs calls, as two
+ *                    gathers on either side of smx_compose
  *   smx_screen    <- the conflict list of the same loop alone (what semmerge/__main__.py
  *                    looks at first), for many pairs of logs, from the logs' renames
  *   smx_screen_train <- the conflict lists of smx_compose_train's steps alone, from the
@@ -614,6 +617,87 @@ int smx_compose_train_workspace_bytes(int64_t n_logs, int64_t n_trains, int64_t 
  * call; n_trains = 0 returns SMX_OK and launches nothing. */
 int smx_compose_train(const struct smx_train* t, void* workspace, size_t workspace_bytes, uint32_t flags,
                       void* stream);
+
+/*
+ * One step of a merge train of any size, as two calls on either side of smx_compose (DESIGN.md
+ * §23).  smx_compose_train runs a train inside one workgroup and reports -2 for a step over
+ * 2048 ops.  What leads from one compose to the next is a gather, and smx_compose composes a
+ * merge of any size, so such a train is a host loop over columns that stay on the device:
+ *
+ *   smx_train_stage   the step's input columns, from the accumulator and the next log
+ *   smx_compose       on the staged columns: an smx_ops with n_a = n_acc, n_b = log_n, b_gap = 0
+ *   smx_train_land    the result folded into the accumulator, or its conflicts as records
+ *
+ * The struct describes one step of one train.  Every pointer is device memory that the caller
+ * owns; there is no workspace and nothing is allocated.  The accumulator is what smx_train's is:
+ * per entry the op's column index (src) and its accumulated addr / file / ctx.
+ *
+ * smx_train_stage writes staged entry e, for e in [0, n_acc + log_n), by the rule of
+ * smx_compose_train's steps.  For e < n_acc: the columns of op acc_src[e]; a move's v0 is
+ * acc_addr[e] where that is not SMX_NONE; a move's v1 is acc_file[e] where that is not SMX_NONE,
+ * and v1_alt[acc_src[e]] where acc_file[e] == empty_str.  For e >= n_acc: the columns of op
+ * log_lo + e - n_acc as they are.  It sets status[0]: 0 for a well-formed step; -1 when an op
+ * of the step has kind >= 18 or sym >= n_sym, or an acc_src[e] lies outside [0, n_total).  Such
+ * an acc_src[e] is not read through: the staged entry gets kind 0xFF and sym 0xFFFFFFFF, which
+ * smx_compose refuses, and its other columns are left as they were.
+ *
+ * smx_train_land reads counts and status[0] on the device:
+ *   counts[0] < 0 or status[0] != 0   status[1] = -1; nothing else is written
+ *   counts[1] > 0   the step does not land: status[1] = counts[1], status[2] = n_acc, and the
+ *                   first min(counts[1], conflict_cap, record_cap) records are written, nothing
+ *                   at or past record_cap; the accumulator out is untouched.  A record is
+ *                   smx_train's: the A op's column index, the B op's column index, and the addr
+ *                   and the file the A op carried when the step began.
+ *   counts[1] == 0  the step lands: status[1] = 0, status[2] = counts[0], and entry k of the
+ *                   accumulator out, for k < counts[0], is the old entry order[k] -- or a fresh
+ *                   one of the log, src = log_lo + order[k] - n_acc and SMX_NONE in the three
+ *                   fields -- with the step's addr[k] / file[k] / ctx[k] folded in per field:
+ *                   the step's value where it is not SMX_NONE, else the old one.
+ * smx_train_land does not read the staged columns.  An element index in order or conflicts
+ * that names no entry of the step is not read through (its entry or record is not written).
+ *
+ * Each call is one kernel launch on `stream` (smx_train_stage clears status[0] ahead of its
+ * kernel, stream-ordered): no host synchronisation, no allocation, no read-back, so the three
+ * calls of a step follow each other without waiting.  Both are valid with n_acc = 0 and with
+ * log_n = 0; with n_acc + log_n = 0 they launch nothing, write nothing and return SMX_OK.
+ */
+typedef struct smx_train_step {
+  /* the log store, as smx_train takes it */
+  int64_t n_total, n_sym;
+  const uint8_t* kind; const uint64_t* ts, *oid_hi, *oid_lo;
+  const uint32_t* sym; const int32_t* v0, *v1;     /* as smx_ops, n_total entries */
+  const int32_t* v1_alt;                  /* n_total entries, read for moves only; NULL with empty_str < 0 */
+  /* the accumulator in */
+  int64_t n_acc;
+  const int32_t* acc_src, *acc_addr, *acc_file, *acc_ctx;   /* n_acc entries */
+  /* the step's log: ops [log_lo, log_lo + log_n) of the columns */
+  int64_t log_lo, log_n;
+  /* the staged merge, written by smx_train_stage: capacity n_acc + log_n */
+  uint8_t* st_kind; uint64_t* st_ts, *st_oid_hi, *st_oid_lo;
+  uint32_t* st_sym; int32_t* st_v0, *st_v1;
+  /* the compose result that smx_train_land reads: smx_compose_out's fields */
+  const int32_t* order, *addr, *file, *ctx;
+  const int32_t* conflicts; int64_t conflict_cap;
+  const int64_t* counts;
+  /* the accumulator out, written by smx_train_land: capacity n_acc + log_n, not the
+   * accumulator in (the caller alternates between two sets) */
+  int32_t* out_src, *out_addr, *out_file, *out_ctx;
+  int32_t* records; int64_t record_cap;   /* 4 int32 per record */
+  int64_t* status;                        /* device [3]: stage's verdict, the step's outcome, the
+                                             accumulator's length after the step */
+  int32_t empty_str;                      /* as smx_train */
+} smx_train_step;
+/* Both calls return SMX_E_ARG before any HIP call for: a null struct; a negative size, log_lo,
+ * conflict_cap or record_cap; n_total or n_acc + log_n over 2^31 - 1; log_lo + log_n > n_total;
+ * n_sym > 2^32 - 1; empty_str < -1; a null v1_alt with empty_str >= 0 and n_total > 0; and,
+ * with n_acc + log_n > 0, a null pointer that the call would use.  smx_train_stage uses status,
+ * the columns (n_total > 0), acc_src / acc_addr / acc_file (n_acc > 0) and the staged columns.
+ * smx_train_land uses status, counts, order / addr / file / ctx, the accumulator out, the four
+ * arrays of the accumulator in (n_acc > 0), conflicts (conflict_cap > 0) and records
+ * (record_cap > 0); an array of the accumulator out that is one of the accumulator in is
+ * SMX_E_ARG too. */
+int smx_train_stage(const struct smx_train_step* s, void* stream);
+int smx_train_land(const struct smx_train_step* s, void* stream);
 
 /*
  * Conflict screen of merge trains: which steps of smx_compose_train's trains have

@@ -189,6 +189,50 @@ class SmxTrain(C.Structure):
     ]
 
 
+class SmxTrainStep(C.Structure):
+    _fields_ = [
+        ("n_total", C.c_int64),
+        ("n_sym", C.c_int64),
+        ("kind", C.c_void_p),
+        ("ts", C.c_void_p),
+        ("oid_hi", C.c_void_p),
+        ("oid_lo", C.c_void_p),
+        ("sym", C.c_void_p),
+        ("v0", C.c_void_p),
+        ("v1", C.c_void_p),
+        ("v1_alt", C.c_void_p),
+        ("n_acc", C.c_int64),
+        ("acc_src", C.c_void_p),
+        ("acc_addr", C.c_void_p),
+        ("acc_file", C.c_void_p),
+        ("acc_ctx", C.c_void_p),
+        ("log_lo", C.c_int64),
+        ("log_n", C.c_int64),
+        ("st_kind", C.c_void_p),
+        ("st_ts", C.c_void_p),
+        ("st_oid_hi", C.c_void_p),
+        ("st_oid_lo", C.c_void_p),
+        ("st_sym", C.c_void_p),
+        ("st_v0", C.c_void_p),
+        ("st_v1", C.c_void_p),
+        ("order", C.c_void_p),
+        ("addr", C.c_void_p),
+        ("file", C.c_void_p),
+        ("ctx", C.c_void_p),
+        ("conflicts", C.c_void_p),
+        ("conflict_cap", C.c_int64),
+        ("counts", C.c_void_p),
+        ("out_src", C.c_void_p),
+        ("out_addr", C.c_void_p),
+        ("out_file", C.c_void_p),
+        ("out_ctx", C.c_void_p),
+        ("records", C.c_void_p),
+        ("record_cap", C.c_int64),
+        ("status", C.c_void_p),
+        ("empty_str", C.c_int32),
+    ]
+
+
 class SmxScreenTrain(C.Structure):
     _fields_ = [
         ("n_logs", C.c_int64),
@@ -328,6 +372,8 @@ EXPORTS = (
     "smx_compose_pairs",
     "smx_compose_train_workspace_bytes",
     "smx_compose_train",
+    "smx_train_stage",
+    "smx_train_land",
     "smx_screen_workspace_bytes",
     "smx_screen",
     "smx_screen_ex_workspace_bytes",
@@ -403,6 +449,10 @@ def declare(lib: C.CDLL) -> C.CDLL:
         lib.smx_compose_train_workspace_bytes.restype = C.c_int
         lib.smx_compose_train.argtypes = [C.POINTER(SmxTrain), C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
         lib.smx_compose_train.restype = C.c_int
+    if hasattr(lib, "smx_train_stage"):  # (older builds, e.g. A/B baselines, lack it)
+        for f in ("smx_train_stage", "smx_train_land"):
+            getattr(lib, f).argtypes = [C.POINTER(SmxTrainStep), C.c_void_p]
+            getattr(lib, f).restype = C.c_int
     if hasattr(lib, "smx_screen"):  # (older builds, e.g. A/B baselines, lack it)
         lib.smx_screen_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]
         lib.smx_screen_workspace_bytes.restype = C.c_int

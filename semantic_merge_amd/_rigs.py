@@ -413,6 +413,120 @@ class DeviceTrains(_DeviceMany):
         return out
 
 
+class DeviceTrainLoop(_DeviceMany):
+    """One train of any size on device-resident columns, as the host loop of smx_train_stage,
+    smx_compose and smx_train_land (_session.run_train_loop; tests, tools/train_loop_probe.py).
+    v1_alt, empty_str  smx_train_step's two (default: none, SMX_NONE);
+    record_caps   per-step capacities in conflict records (default: the step's log's length,
+                  which always suffices);
+    fill          every output word (the staged columns, the two state buffers, the records,
+                  status) starts as this value, and CONF_GUARD such words follow every array;
+    acc           a hand-made accumulator to start from: (src, addr, file, ctx) arrays;
+    log_off, n_sym, n_total  passed instead of the LogsSoA's own;
+    share         another DeviceTrainLoop over the same LogsSoA, at least as large: its device
+                  buffers and workspace are used instead of new ones.
+    run() keeps, per step that ran on the device, its status triple in `steps`."""
+
+    _OUT = ("st_kind", "st_ts", "st_oid_hi", "st_oid_lo", "st_sym", "st_v0", "st_v1", "state0", "state1", "records",
+            "status")
+
+    def __init__(self, lsoa, train, v1_alt=None, empty_str: int = -1, record_caps=None, fill: Optional[int] = None,
+                 device: str = "cuda", acc=None, log_off=None, n_sym: Optional[int] = None,
+                 n_total: Optional[int] = None, share=None) -> None:
+        self._open(device)
+        torch, dev = self.torch, self.device
+        self.lsoa = lsoa
+        self.train = [int(l) for l in train]
+        L, S = lsoa.n_logs, len(self.train)
+        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
+        tot = int(lsoa.n_total)
+        self.n_total = tot if n_total is None else n_total
+        self.n_sym = int(lsoa.n_sym) if n_sym is None else n_sym
+        lens = np.diff(np.asarray(lsoa.log_off, np.int64))
+        self.step_len = np.asarray([int(lens[l]) if 0 <= l < L else 0 for l in self.train], np.int64)
+        self._acc = None if acc is None else [np.ascontiguousarray(a, dtype=np.int32) for a in acc]
+        cap = self.cap = int(self.step_len.sum()) + (len(self._acc[0]) if acc is not None else 0)
+        self.rec_off = np.zeros(S + 1, np.int64)
+        np.cumsum(self.step_len if record_caps is None else record_caps, out=self.rec_off[1:])
+        f = 0 if fill is None else fill
+        G = self.CONF_GUARD
+
+        def full(n, dt):
+            return torch.full((n + G,), f & 0xFF if dt == torch.uint8 else f, dtype=dt, device=dev)
+
+        if share is not None:
+            if share.lsoa is not lsoa or cap > share.cap or self.rec_off[-1] > share.rec_off[-1]:
+                raise ValueError("share: a DeviceTrainLoop over the same LogsSoA, at least as large")
+            cap = self.cap = share.cap
+            for name in self._OUT + ("_in", "_alt", "order", "addr", "file", "ctx", "conf", "counts", "_status_host",
+                                     "_wsbox"):
+                setattr(self, name, getattr(share, name))
+        else:
+            self._upload_cols([lsoa])
+            self._alt = None if v1_alt is None else self._up(np.asarray(v1_alt, np.int32))
+            for (name, _, view) in OP_COLS:
+                setattr(self, "st_" + name, full(cap, getattr(torch, view.name)))
+            self.state0, self.state1 = full(4 * (cap + G), torch.int32), full(4 * (cap + G), torch.int32)
+            self.records = full(4 * int(self.rec_off[-1]), torch.int32)
+            self.status = full(3, torch.int64)
+            # (smx_compose's own outputs: it alone writes them)
+            self.order, self.addr, self.file, self.ctx = (torch.zeros(max(cap, 1), dtype=torch.int32, device=dev)
+                                                          for _ in range(4))
+            self.conf = torch.zeros(max(cap, 2), dtype=torch.int32, device=dev)  # (2 * min(n_acc, log_n) words at most)
+            self.counts = torch.zeros(2, dtype=torch.int64, device=dev)
+            self._status_host = torch.zeros(3, dtype=torch.int64, pin_memory=True)
+            self._wsbox = {"bytes": 0, "ws": None}  # (the workspace, grown on demand)
+        self._base = _abi.SmxTrainStep(
+            n_total=self.n_total, n_sym=self.n_sym, **{name: _ptr(t) for (name, _, _), t in zip(OP_COLS, self._in)},
+            v1_alt=_ptr(self._alt), **{"st_" + name: getattr(self, "st_" + name).data_ptr() for name, _, _ in OP_COLS},
+            order=self.order.data_ptr(), addr=self.addr.data_ptr(), file=self.file.data_ptr(), ctx=self.ctx.data_ptr(),
+            conflicts=self.conf.data_ptr(), counts=self.counts.data_ptr(), records=self.records.data_ptr(),
+            status=self.status.data_ptr(), empty_str=empty_str)
+        self.steps, self.cur, self.n_acc, self.landed = [], 0, 0, 0
+
+    def _state(self, i: int):
+        """The four arrays of state buffer i, cap + CONF_GUARD words apart."""
+        t, q = (self.state0, self.state1)[i], self.cap + self.CONF_GUARD
+        return tuple(t.data_ptr() + 4 * q * f for f in range(4))
+
+    def _ws(self, nbytes: int) -> int:
+        box = self._wsbox
+        if box["ws"] is None or nbytes > box["bytes"]:
+            self.torch.cuda.synchronize(self.device)
+            box["bytes"], box["ws"] = nbytes, self.torch.empty(max(nbytes, 1), dtype=self.torch.uint8, device=self.device)
+            self.torch.cuda.synchronize(self.device)
+        return box["ws"].data_ptr()
+
+    def run(self, stream=None, hook=None) -> None:
+        """The train's steps one after another on `stream` (default: torch's current stream),
+        from an empty accumulator (or `acc`) in state buffer 0."""
+        from ._session import run_train_loop
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        n0 = 0
+        if self._acc is not None:
+            n0, q = len(self._acc[0]), self.cap + self.CONF_GUARD
+            for f, a in enumerate(self._acc):
+                self.state0[f * q: f * q + n0] = self._up(a)
+            self.torch.cuda.synchronize(self.device)
+        self.cur, self.n_acc, self.landed, self.steps = run_train_loop(
+            s.cuda_stream, self._base, (self._state(0), self._state(1)), self.log_off, self.train, self.rec_off,
+            self._ws, self._status_host.numpy(), hook, n_acc=n0)
+
+    def results(self, raw: Optional[dict] = None):
+        """DeviceTrains' per-train tuple (src, addr, file, ctx, landed, steps): the final
+        accumulator, the steps that landed, and per step (accumulator length after it, outcome,
+        its conflict records as an (n, 4) array trimmed to its capacity)."""
+        r = self.raw() if raw is None else raw
+        q = self.cap + self.CONF_GUARD
+        fin = r["state%d" % self.cur]
+        steps = []
+        for g, (acc, oc, _) in enumerate(self.steps):
+            c = int(self.rec_off[g])
+            nc = min(max(oc, 0), int(self.rec_off[g + 1]) - c)
+            steps.append((acc, oc, r["records"][4 * c: 4 * (c + nc)].reshape(nc, 4)))
+        return tuple(fin[f * q: f * q + self.n_acc] for f in range(4)) + (self.landed, steps)
+
+
 class DeviceScreen(_DeviceMany):
     """Device-resident inputs, outputs and workspace for repeated smx_screen calls on a
     LogsSoA and a list of (i, j) pairs (tests, tools/screen_probe.py).  The optional

@@ -84,6 +84,76 @@ def screen_results(hout, conf_at: int, counts_at: int, conf_off, pairs) -> list:
             for p in range(P)]
 
 
+def run_train_loop(st: int, base, state, log_off, train, rec_off, ws, status_host, hook=None, n_acc: int = 0):
+    """One train of any size as a host loop over device-resident columns (include/smx.h
+    smx_train_step): per step smx_train_stage, smx_compose on the staged columns with
+    conflict_cap = max(min(n_acc, log_n), 1), smx_train_land, then the 24 bytes of `status`
+    read back on stream `st` -- the step's only read-back -- and the two state buffers flipped
+    when the step landed.
+
+    base        an _abi.SmxTrainStep with the log store, the staged columns, the compose result
+                (conflicts with room for the largest step's pairs), status and empty_str set;
+                its records field is the start of all the steps' records
+    state       two 4-tuples of device addresses (src, addr, file, ctx); the train starts with
+                the accumulator in state[0], n_acc entries long (0: empty)
+    log_off     the logs' offsets (host); a log index outside them, or offsets that decrease
+                or leave the columns, give the step -1 on the host, as smx_compose_train does
+    rec_off     per step where its records start, in records, n_steps + 1 entries
+    ws          ws(nbytes) -> device address of a workspace of at least nbytes
+    status_host int64[3] in pinned host memory
+    hook        hook(step index, status triple) after each step that ran on the device
+
+    Returns (cur, n_acc, landed, steps): the state buffer that holds the accumulator, its
+    length, the steps that landed, and per step (length after it, outcome, status triple or
+    None for a step decided on the host)."""
+    L = lib()
+    off = np.asarray(log_off, np.int64)
+    n_total, n_logs = int(base.n_total), len(off) - 1
+    before = np.maximum.accumulate(np.concatenate([[0], off[:-1]]))[:-1] if n_logs > 0 else np.zeros(0, np.int64)
+    ok = (off[:-1] >= before) & (off[1:] >= off[:-1]) & (off[1:] <= n_total)
+    records, h_status = int(base.records or 0), status_host.ctypes.data
+    ops = _abi.SmxOps(0, 0, int(base.n_sym), base.st_kind, base.st_ts, base.st_oid_hi, base.st_oid_lo, base.st_sym,
+                      base.st_v0, base.st_v1, 0)
+    out = _abi.SmxComposeOut(base.order, base.addr, base.file, base.ctx, base.conflicts, 0, base.counts)
+    need = C.c_size_t(0)
+    cur, landed, steps = 0, 0, []
+    for g, l in enumerate(train):
+        if not (0 <= l < n_logs) or not ok[l]:
+            steps.append((n_acc, -1, None))
+            continue
+        lo, nb = int(off[l]), int(off[l + 1] - off[l])
+        if n_acc + nb == 0:  # (nothing to launch: empty against empty lands)
+            landed += 1
+            steps.append((0, 0, None))
+            continue
+        base.n_acc, base.log_lo, base.log_n = n_acc, lo, nb
+        base.acc_src, base.acc_addr, base.acc_file, base.acc_ctx = state[cur]
+        base.out_src, base.out_addr, base.out_file, base.out_ctx = state[cur ^ 1]
+        base.conflict_cap = out.conflict_cap = max(min(n_acc, nb), 1)
+        base.records = records + 16 * int(rec_off[g])
+        base.record_cap = int(rec_off[g + 1] - rec_off[g])
+        ops.n_a, ops.n_b = n_acc, nb
+        check(L.smx_train_stage(C.byref(base), st))
+        check(L.smx_compose_workspace_bytes(n_acc, nb, ops.n_sym, C.byref(need)))
+        rc = L.smx_compose(C.byref(ops), C.byref(out), ws(need.value), need.value, st)
+        err = L.smx_last_error().decode(errors="replace") if rc else ""
+        check(L.smx_train_land(C.byref(base), st))
+        _Staging._copy(h_status, int(base.status), 24, 2, st, "hipMemcpyAsync (status)")
+        _hip_check(_hiprt().hipStreamSynchronize(st), "hipStreamSynchronize")
+        s = tuple(int(x) for x in status_host)
+        if rc and s[0] == 0:  # (a step that stage found invalid is refused by smx_compose too: that is its -1)
+            raise SmxError(rc, f"step {g}: {err}")
+        if s[1] == 0:
+            cur ^= 1
+            n_acc = s[2]
+            landed += 1
+        steps.append((n_acc, s[1], s))
+        if hook is not None:
+            hook(g, s)
+    base.records = records
+    return cur, n_acc, landed, steps
+
+
 class _Staging:
     """One pair of pinned-host and device buffers for a call's input (h_in, d_in) and one for
     its output (h_out, d_out), sized in bytes; hin / hout are the host buffers as numpy bytes.
@@ -646,6 +716,81 @@ class ComposeSession:
             o = int(res_off[r])
             res.append(tuple(hout[f * q + 4 * o: f * q + 4 * (o + k)].view(np.int32).copy() for f in range(4))
                        + (landed, steps))
+        self.last = _last(pack_s=t1 - t0, device_s=t2 - t1, unpack_s=time.perf_counter() - t2, in_bytes=lay["in_bytes"])
+        return res
+
+    # -- one train of any size: the host loop of smx_train_stage, smx_compose, smx_train_land ----
+
+    def compose_train_loop(self, lsoa, train, v1_alt=None, empty_str: int = -1):
+        """compose_trains' result for one train, (src, addr, file, ctx, landed, steps), with no
+        limit on a step's size and so no outcome -2: the columns, every log once, are copied in
+        once, and every step is smx_train_stage, smx_compose on the staged columns and
+        smx_train_land on the session's stream, over buffers that stay on the device
+        (run_train_loop: 24 bytes read back per step).  The final accumulator and the records are
+        copied back once at the end.  A step over 2048 ops takes smx_compose's sorting plans: the
+        accumulator is kind-major, not timestamp-ordered.  Invalid input raises
+        SmxError naming the step.  The results are copies.  `last` holds the call's legs and
+        "in_bytes"."""
+        t0 = time.perf_counter()
+        train = [int(l) for l in np.asarray(train, np.int64).reshape(-1)]
+        L, tot, S = lsoa.n_logs, int(lsoa.n_total), len(train)
+        if any(not 0 <= l < L for l in train):
+            raise SmxError(-1, f"a log index outside [0, {L})")
+        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
+        lens = log_off[1:] - log_off[:-1]
+        if int(log_off[0]) < 0 or (lens < 0).any() or int(log_off[-1]) > tot:
+            raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
+        rec_off = np.concatenate([[0], np.cumsum(lens[train] if S else [], dtype=np.int64)]).astype(np.int64)
+        cap = int(rec_off[-1])  # (the accumulator holds at most every op of the train's steps)
+        alt = np.zeros(tot, np.int32) if v1_alt is None else np.ascontiguousarray(v1_alt, dtype=np.int32)
+        # in: the columns and v1_alt.  out: the two state buffers and the records (what is copied
+        # back), then what only the device sees: the staged columns, the compose result, status
+        q = _al(4 * cap)
+        lay = self._layout(tot, [(name, tot * dt.itemsize) for name, dt, _ in OP_COLS] + [("v1_alt", tot * 4)], 0, 0, 0)
+        o, scratch = 8 * q + _al(16 * cap), {}
+        for name, nbytes in [("st_" + name, cap * dt.itemsize) for name, dt, _ in OP_COLS] + \
+                            [(name, 4 * cap) for name in ("order", "addr", "file", "ctx")] + \
+                            [("conflicts", 4 * cap + 8), ("counts", 16), ("status", 24)]:
+            scratch[name] = o
+            o += _al(nbytes)
+        m = self.main
+        self._ensure(m, lay["in_bytes"], o, 0)
+        hin, h0, d0, o0 = m.hin, m.hin.ctypes.data, m.d_in.data_ptr(), m.d_out.data_ptr()
+        for name, dt, _ in OP_COLS:
+            _pack(hin, h0, getattr(lsoa, name), lay[name], tot * dt.itemsize)
+        _pack(hin, h0, alt, lay["v1_alt"], alt.nbytes)
+        t1 = time.perf_counter()
+        st = self.stream.cuda_stream
+        m.copy_in(st, lay["in_bytes"])
+        if getattr(self, "_status_host", None) is None:
+            self._status_host = self.torch.zeros(3, dtype=self.torch.int64, pin_memory=True)
+        base = _abi.SmxTrainStep(n_total=tot, n_sym=int(lsoa.n_sym), **{name: d0 + lay[name] for name, _, _ in OP_COLS},
+                                 v1_alt=d0 + lay["v1_alt"], records=o0 + 8 * q, empty_str=int(empty_str),
+                                 **{name: o0 + at for name, at in scratch.items()})
+
+        def ws(nbytes: int) -> int:
+            self._ensure(m, 0, 0, nbytes)
+            return self.ws.data_ptr()
+
+        state = tuple(tuple(o0 + (4 * b + f) * q for f in range(4)) for b in range(2))
+        cur, n_acc, landed, ran = run_train_loop(st, base, state, log_off, train, rec_off, ws, self._status_host.numpy())
+        h_out = m.h_out.data_ptr()
+        if n_acc:
+            m._copy(h_out + 4 * cur * q, o0 + 4 * cur * q, 3 * q + 4 * n_acc, 2, st, "hipMemcpyAsync (accumulator)")
+        if cap:
+            m._copy(h_out + 8 * q, o0 + 8 * q, 16 * cap, 2, st, "hipMemcpyAsync (records)")
+        _hip_check(_hiprt().hipStreamSynchronize(st), "hipStreamSynchronize")
+        t2 = time.perf_counter()
+        hout = m.hout
+        recs = hout[8 * q: 8 * q + 16 * cap].view(np.int32).reshape(-1, 4)
+        steps = []
+        for g, (acc, oc, _) in enumerate(ran):
+            if oc == -1:
+                raise SmxError(-1, f"step {g}: invalid input: sym >= n_sym or kind >= 18")
+            c = int(rec_off[g])
+            steps.append((acc, oc, recs[c: c + min(max(oc, 0), int(rec_off[g + 1]) - c)].copy()))
+        fin = 4 * cur * q
+        res = tuple(hout[fin + f * q: fin + f * q + 4 * n_acc].view(np.int32).copy() for f in range(4)) + (landed, steps)
         self.last = _last(pack_s=t1 - t0, device_s=t2 - t1, unpack_s=time.perf_counter() - t2, in_bytes=lay["in_bytes"])
         return res
 

@@ -148,8 +148,11 @@ def _train_on_host(logs: Sequence[Sequence[Any]], train: Sequence[int]) -> Tuple
     return acc, steps
 
 
-def compose_train(logs: Sequence[Sequence[Any]],
-                  trains: Optional[Sequence[Sequence[int]]] = None) -> List[Tuple[List[Any], List[List[Any]]]]:
+LOOP_MAX_SYM = 1 << 30  # symbols that smx_compose's window plans accept (more: the host loop)
+
+
+def compose_train(logs: Sequence[Sequence[Any]], trains: Optional[Sequence[Sequence[int]]] = None,
+                  large: bool = False) -> List[Tuple[List[Any], List[List[Any]]]]:
     """Merge trains over logs given once.  A train takes its logs in order: each is composed
     against what landed before it, ``compose_oplogs(acc, log)``; a log that conflicts is put
     off the train (as ``semmerge`` exits before applying anything) and the next one goes on
@@ -160,7 +163,11 @@ def compose_train(logs: Sequence[Sequence[Any]],
     host loop.  Every log is marshalled and copied to the GPU once and all the trains run in one
     call (one copy in, one smx_compose_train, one copy back, one sync); the ops are materialised
     once per train.  A train whose accumulator and next log exceed 2048 ops runs as the host
-    loop instead.  An index outside the logs raises ``IndexError``.  Inputs are never mutated."""
+    loop instead.  ``large=True``: such a train runs on the GPU too, step by step over columns
+    that stay on the device (smx_train_stage, smx_compose, smx_train_land per step:
+    ``ComposeSession.compose_train_loop``), and is materialised once like the others; only logs
+    with more than 2^30 symbols keep the host loop.  An index outside the logs raises
+    ``IndexError``.  Inputs are never mutated."""
     ops = [list(x) for x in logs]
     if trains is None:
         trains = [list(range(len(ops)))]
@@ -178,6 +185,9 @@ def compose_train(logs: Sequence[Sequence[Any]],
         flat = [o for x in ops for o in x]
         alt, empty = move_file_alt(flat, lsoa.kind, lsoa.strings)
         found = sess.compose_trains(lsoa, trains, v1_alt=alt, empty_str=empty)
+        if large and int(lsoa.n_sym) <= LOOP_MAX_SYM:
+            found = [sess.compose_train_loop(lsoa, tr, v1_alt=alt, empty_str=empty)
+                     if any(oc == -2 for _, oc, _ in f[5]) else f for tr, f in zip(trains, found)]
     for tr, (src, addr, file, ctx, _, steps) in zip(trains, found):
         if any(oc == -2 for _, oc, _ in steps):
             res.append(_train_on_host(ops, tr))

@@ -3,7 +3,9 @@
 // and smx_batch_large.h) and smx_screen /
 // smx_screen_ex (kernels in smx_screen.h), and smx_screen_candidates (kernels in smx_cand.h,
 // DESIGN.md §14), which has a shape of its own: a sort and a bit matrix, no size classes; and
-// smx_compose_train (kernels in smx_train.h), the class launch over trains, and
+// smx_compose_train (kernels in smx_train.h), the class launch over trains, with
+// smx_train_stage / smx_train_land beside it (kernels in smx_train_step.h, DESIGN.md §23: one
+// step of a train of any size, a launch each and no workspace), and
 // smx_screen_train (kernels in smx_screen_train.h), the screen's over trains.
 //
 // All three have one shape: a pre-pass sorts the items (merges, pairs) into three size
@@ -22,6 +24,7 @@
 #include "smx_screen.h"
 #include "smx_cand.h"
 #include "smx_train.h"
+#include "smx_train_step.h"
 #include "smx_screen_train.h"
 
 // The kernels with a residency-capped grid, and the threads of a workgroup of each.
@@ -391,6 +394,76 @@ extern "C" int smx_compose_train(const struct smx_train* b, void* workspace, siz
     HIP_TRY(hipGetLastError());
     return launch_classes(kTrainKernels, kBatchCaps, resident + R_TRAIN, b->n_trains, b->grid_cap, st, w.cnt, w.lists,
                           w.stride, *b, w);
+  } catch (const std::exception& e) {
+    return smx_set_error(SMX_E_HIP, e.what());
+  }
+}
+
+// What smx_train_stage and smx_train_land check alike: the struct's sizes.  *n: n_acc + log_n.
+static int train_step_sizes(const char* name, const smx_train_step* s, i64* n) {
+  if (!s) return smx_set_error(SMX_E_ARG, (std::string(name) + ": null train step struct").c_str());
+  if (s->n_total < 0 || s->n_sym < 0 || s->n_acc < 0 || s->log_lo < 0 || s->log_n < 0 || s->conflict_cap < 0 ||
+      s->record_cap < 0 || s->empty_str < SMX_NONE)
+    return smx_set_error(SMX_E_ARG, (std::string(name) + ": negative size, or empty_str below SMX_NONE").c_str());
+  if (s->n_total > 0x7fffffffll || s->n_acc > 0x7fffffffll || s->log_n > 0x7fffffffll ||
+      s->n_acc + s->log_n > 0x7fffffffll)
+    return smx_set_error(SMX_E_ARG, (std::string(name) + ": n_total or n_acc + log_n over 2^31 - 1").c_str());
+  if (s->log_lo + s->log_n > s->n_total)  // (both at most 2^31 - 1 here, or log_lo alone is past n_total)
+    return smx_set_error(SMX_E_ARG, (std::string(name) + ": the log [log_lo, log_lo + log_n) leaves the columns").c_str());
+  if (s->n_sym > 0xffffffffll) return smx_set_error(SMX_E_ARG, (std::string(name) + ": n_sym over 2^32 - 1").c_str());
+  if (s->n_total > 0 && s->empty_str >= 0 && !s->v1_alt)
+    return smx_set_error(SMX_E_ARG, (std::string(name) + ": null v1_alt with empty_str set").c_str());
+  *n = s->n_acc + s->log_n;
+  return SMX_OK;
+}
+
+// The checks; then status[0] cleared and k_train_stage, a thread per staged entry.
+extern "C" int smx_train_stage(const struct smx_train_step* s, void* stream) {
+  i64 n = 0;
+  if (int rc = train_step_sizes(__func__, s, &n)) return rc;
+  if (n == 0) return SMX_OK;
+  if (!s->status) return smx_set_error(SMX_E_ARG, "smx_train_stage: null status");
+  if (s->n_total > 0 && (!s->kind || !s->ts || !s->oid_hi || !s->oid_lo || !s->sym || !s->v0 || !s->v1))
+    return smx_set_error(SMX_E_ARG, "smx_train_stage: null column");
+  if (s->n_acc > 0 && (!s->acc_src || !s->acc_addr || !s->acc_file))
+    return smx_set_error(SMX_E_ARG, "smx_train_stage: null accumulator array");
+  if (!s->st_kind || !s->st_ts || !s->st_oid_hi || !s->st_oid_lo || !s->st_sym || !s->st_v0 || !s->st_v1)
+    return smx_set_error(SMX_E_ARG, "smx_train_stage: null staged column");
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  try {
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(s->status, 0, sizeof(int64_t), st));
+    hipLaunchKernelGGL(k_train_stage, dim3(train_step_grid(n)), dim3(TRAIN_STEP_T), 0, st, *s);
+    HIP_TRY(hipGetLastError());
+    return SMX_OK;
+  } catch (const std::exception& e) {
+    return smx_set_error(SMX_E_HIP, e.what());
+  }
+}
+
+// The checks; then k_train_land, a thread per entry of the accumulator out (or per record).
+extern "C" int smx_train_land(const struct smx_train_step* s, void* stream) {
+  i64 n = 0;
+  if (int rc = train_step_sizes(__func__, s, &n)) return rc;
+  if (n == 0) return SMX_OK;
+  if (!s->status || !s->counts) return smx_set_error(SMX_E_ARG, "smx_train_land: null status / counts");
+  if (!s->order || !s->addr || !s->file || !s->ctx) return smx_set_error(SMX_E_ARG, "smx_train_land: null result array");
+  if (!s->out_src || !s->out_addr || !s->out_file || !s->out_ctx)
+    return smx_set_error(SMX_E_ARG, "smx_train_land: null accumulator out");
+  if (s->n_acc > 0 && (!s->acc_src || !s->acc_addr || !s->acc_file || !s->acc_ctx))
+    return smx_set_error(SMX_E_ARG, "smx_train_land: null accumulator array");
+  if (s->conflict_cap > 0 && !s->conflicts) return smx_set_error(SMX_E_ARG, "smx_train_land: null conflicts");
+  if (s->record_cap > 0 && !s->records) return smx_set_error(SMX_E_ARG, "smx_train_land: null records");
+  const int32_t* const in[4] = {s->acc_src, s->acc_addr, s->acc_file, s->acc_ctx};
+  const int32_t* const out[4] = {s->out_src, s->out_addr, s->out_file, s->out_ctx};
+  for (const int32_t* o : out)
+    for (const int32_t* i : in)
+      if (o == i) return smx_set_error(SMX_E_ARG, "smx_train_land: the accumulator out aliases the accumulator in");
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  try {
+    hipLaunchKernelGGL(k_train_land, dim3(train_step_grid(n)), dim3(TRAIN_STEP_T), 0, (hipStream_t)stream, *s);
+    HIP_TRY(hipGetLastError());
+    return SMX_OK;
   } catch (const std::exception& e) {
     return smx_set_error(SMX_E_HIP, e.what());
   }
