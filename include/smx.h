@@ -26,6 +26,9 @@
  *                    batched over many independent lists
  *   smx_rga_replay_onto <- the same, for many event streams replayed onto base lists that
  *                    are stored once (RGA._fold's shape, many branches per base list)
+ *   smx_rga_replay_chain <- the same, for jobs that are runs of segments stored once (a
+ *                    three-way reconcile base ++ target ++ pull request, what a merge train
+ *                    landed, every prefix of a commit stack)
  *
  * Plain C types only.  All device pointers are HIP device (or managed) memory
  * owned by the caller; the library never allocates: temporary space comes from a
@@ -1009,6 +1012,72 @@ typedef struct smx_rga_onto {
 int smx_rga_replay_onto_workspace_bytes(int64_t n_jobs, int64_t n_out, size_t* bytes);
 int smx_rga_replay_onto(const smx_rga_onto* onto, const smx_rga_out* out, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/*
+ * RGA replay of many jobs that are runs of segments stored once (a three-way list reconcile
+ * base ++ target ++ pull request over K targets and M pull requests; the list a merge train
+ * leaves, base ++ the landed logs' events; the states after commits 1, 1..2, ... 1..n of a
+ * stack).  smx_rga_replay_onto's job is two column ranges; here it is any number.  The events
+ * of job j are the events of its segments, one segment after another in job_seg order, and the
+ * job's results are exactly those of smx_rga_replay on that concatenated stream as one list,
+ * in both output modes -- but a segment's events are stored, copied and read from one place
+ * however many jobs name it.
+ *   seg_off   [n_segs + 1]: segment s is columns [seg_off[s], seg_off[s + 1])
+ *   job_off   [n_jobs + 1]: job j's segments are job_seg[job_off[j] .. job_off[j + 1])
+ *   job_seg   [n_links]:    segment indices < n_segs
+ *   op .. opid_lo           the event columns of smx_rga_ops, n_total entries each; values,
+ *                           anchors and authors form one id domain for the whole call (a move
+ *                           or delete in one segment reaches an element of the same value id
+ *                           that an earlier segment of the job created)
+ * Within a job the segment indices strictly ascend, and seg_off does not decrease.  The
+ * creation index that breaks ties between equal keys is the column index, and column order is
+ * the concatenated stream's order only if a job's segments ascend; it also means that no job
+ * names a segment twice.  (Store the base, then the targets, then the pull requests; or the
+ * commits in stack order.)  A job may skip segments; jobs may come in any order; a segment may
+ * be in any number of jobs or in none, and one that no job names is never read; a segment or
+ * a job may be empty.
+ * Output: smx_rga_out with one "list" per job: out_offsets has n_jobs + 1 entries,
+ * out_value / out_src / out_tomb have capacity n_out (at least the sum over the jobs of their
+ * segments' events), out_src[k] is the COLUMN index of the event that created element k,
+ * counts[0] the total.
+ * Stream-ordered on `stream`, in a number of launches that does not depend on the data; ends,
+ * as smx_rga_replay_onto does, with the read-back of one error word and a stream wait:
+ * SMX_E_ARG ("invalid input") for a seg_off or job_off entry that is negative, decreasing or
+ * past n_total / n_links, a job_seg outside [0, n_segs), segment indices that do not strictly
+ * ascend within a job, an op > 2 in a segment that some job names, or job lengths that sum to
+ * more than n_out (all found on the device before a column is read through an unchecked
+ * offset); the next call on the same workspace is served.  A null struct or output, sizes that
+ * are negative, n_total or n_out above 2^30 - 1, n_segs, n_jobs or n_links at or above
+ * 2^31 - 1, a null pointer with a non-zero size and a workspace that is too small or not
+ * 16-byte aligned come back (SMX_E_ARG / SMX_E_WORKSPACE) before any HIP call.
+ * n_jobs = 0 writes out_offsets[0] = 0 and counts[0] = 0 and needs no workspace.
+ * Workspace: smx_rga_replay_onto's for (n_jobs, n_out) without its 16 bytes per job, plus the
+ * column map, 4 bytes per entry of n_out, and the link scan's two arrays, 4 (n_links + 1) bytes
+ * each; every part rounded up to 256 bytes.  Each call clears the state it needs, so one
+ * workspace serves any sequence of smx_rga_replay_ex, smx_rga_replay_onto and
+ * smx_rga_replay_chain calls that it is large enough for.
+ */
+typedef struct smx_rga_chain {
+  int64_t n_total; /* events in the columns */
+  int64_t n_segs;
+  int64_t n_jobs;
+  int64_t n_links;
+  int64_t n_out;
+  const int64_t* seg_off;
+  const int64_t* job_off;
+  const int32_t* job_seg;
+  const uint8_t* op;
+  const uint32_t* value;
+  const uint32_t* anchor;
+  const int64_t* t;
+  const uint32_t* author;
+  const uint64_t* opid_hi;
+  const uint64_t* opid_lo;
+} smx_rga_chain;
+
+int smx_rga_replay_chain_workspace_bytes(int64_t n_jobs, int64_t n_links, int64_t n_out, size_t* bytes);
+int smx_rga_replay_chain(const smx_rga_chain* c, const smx_rga_out* out, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 const char* smx_last_error(void);
 const char* smx_version(void);

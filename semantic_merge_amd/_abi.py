@@ -347,6 +347,26 @@ class SmxRgaOnto(C.Structure):
     ]
 
 
+class SmxRgaChain(C.Structure):
+    _fields_ = [
+        ("n_total", C.c_int64),
+        ("n_segs", C.c_int64),
+        ("n_jobs", C.c_int64),
+        ("n_links", C.c_int64),
+        ("n_out", C.c_int64),
+        ("seg_off", C.c_void_p),
+        ("job_off", C.c_void_p),
+        ("job_seg", C.c_void_p),
+        ("op", C.c_void_p),
+        ("value", C.c_void_p),
+        ("anchor", C.c_void_p),
+        ("t", C.c_void_p),
+        ("author", C.c_void_p),
+        ("opid_hi", C.c_void_p),
+        ("opid_lo", C.c_void_p),
+    ]
+
+
 # Every symbol include/smx.h declares (tests check the built library exports them).
 RGA_GROUPED = 1   # smx_rga_replay_ex flag (include/smx.h SMX_RGA_GROUPED)
 SCREEN_LARGE = 1  # smx_screen_ex flag (include/smx.h SMX_SCREEN_LARGE): no limit on renames
@@ -394,6 +414,8 @@ EXPORTS = (
     "smx_rga_replay_ex",
     "smx_rga_replay_onto_workspace_bytes",
     "smx_rga_replay_onto",
+    "smx_rga_replay_chain_workspace_bytes",
+    "smx_rga_replay_chain",
     "smx_last_error",
     "smx_version",
 )
@@ -505,6 +527,12 @@ def declare(lib: C.CDLL) -> C.CDLL:
         lib.smx_rga_replay_onto.argtypes = [C.POINTER(SmxRgaOnto), C.POINTER(SmxRgaOut), C.c_void_p,
                                             C.c_size_t, C.c_void_p]
         lib.smx_rga_replay_onto.restype = C.c_int
+    if hasattr(lib, "smx_rga_replay_chain"):  # (older builds, e.g. A/B baselines, lack it)
+        lib.smx_rga_replay_chain_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]
+        lib.smx_rga_replay_chain_workspace_bytes.restype = C.c_int
+        lib.smx_rga_replay_chain.argtypes = [C.POINTER(SmxRgaChain), C.POINTER(SmxRgaOut), C.c_void_p,
+                                             C.c_size_t, C.c_void_p]
+        lib.smx_rga_replay_chain.restype = C.c_int
     lib.smx_last_error.argtypes = []
     lib.smx_last_error.restype = C.c_char_p
     lib.smx_version.argtypes = []

@@ -186,6 +186,40 @@ def rga_replay_onto_device(batch, device: str = "cuda", tombstones: bool = False
     return res + (tomb[:k].cpu().numpy().astype(np.bool_),) if tombstones else res
 
 
+def rga_replay_chain_device(batch, device: str = "cuda", tombstones: bool = False):
+    """(values, src, offsets) of smx_rga_replay_chain for a crdt.RgaChainBatch, one list per
+    job; src holds column indices of the batch.  With tombstones=True the whole list states
+    and a fourth array, the tombstone flags.  Buffers and stream as rga_replay_device."""
+    torch = _torch()
+    dev = torch.device(device)
+    n, nj, nk, n_out = batch.n, batch.n_jobs, batch.n_links, batch.n_out
+    if nj == 0:
+        e = (np.zeros(0, np.uint32), np.zeros(0, np.int32), np.zeros(1, np.int64))
+        return e + (np.zeros(0, np.bool_),) if tombstones else e
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)
+
+    ins = [up(batch.seg_off, np.int64), up(batch.job_off, np.int64), up(batch.job_seg, np.int32),
+           up(batch.op, np.uint8), up(batch.value, np.int32), up(batch.anchor, np.int32), up(batch.t, np.int64),
+           up(batch.author, np.int32), up(batch.opid_hi, np.int64), up(batch.opid_lo, np.int64)]
+    vals, src = (torch.empty(max(n_out, 1), dtype=torch.int32, device=dev) for _ in range(2))
+    offs = torch.empty(nj + 1, dtype=torch.int64, device=dev)
+    counts = torch.zeros(1, dtype=torch.int64, device=dev)
+    tomb = torch.empty(max(n_out, 1), dtype=torch.uint8, device=dev) if tombstones else None
+    ws = C.c_size_t(0)
+    check(lib().smx_rga_replay_chain_workspace_bytes(nj, nk, n_out, C.byref(ws)))
+    wst = torch.empty(max(ws.value, 1), dtype=torch.uint8, device=dev)
+    chain = _abi.SmxRgaChain(n, batch.n_segs, nj, nk, n_out, *[_ptr(t) for t in ins])
+    out = _abi.SmxRgaOut(_ptr(vals), _ptr(src), _ptr(offs), _ptr(counts), _ptr(tomb))
+    check(lib().smx_rga_replay_chain(C.byref(chain), C.byref(out), _ptr(wst), ws.value,
+                                     torch.cuda.current_stream(dev).cuda_stream))
+    torch.cuda.synchronize(dev)
+    k = int(counts.item())
+    res = (vals[:k].cpu().numpy().view(np.uint32), src[:k].cpu().numpy(), offs.cpu().numpy())
+    return res + (tomb[:k].cpu().numpy().astype(np.bool_),) if tombstones else res
+
+
 # These moved to _session.py and _rigs.py and stay importable from here under their old names
 # (bench.py, the tests and the tools import them from _lib); resolved on first use, because
 # both modules import this one.

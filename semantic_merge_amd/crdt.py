@@ -7,7 +7,8 @@ argument meaning are unchanged; ``RGA`` records its event stream and
 keeps the tombstoned elements.
 :func:`replay` is the batched entry point: many independent lists in one launch;
 :func:`replay_onto` replays many event streams onto base lists that are stored once
-(``smx_rga_replay_onto``).
+(``smx_rga_replay_onto``); :func:`replay_chain` replays jobs that are runs of segments stored
+once (``smx_rga_replay_chain``).
 
 Exact parallel restatement used by the device: the fate
 of every element depends only on the events of its (list, value); survivors
@@ -195,6 +196,109 @@ def replay_lists_onto(bases: Sequence[Sequence[Event]], jobs: Sequence[Job]) -> 
     batch = marshal_onto(bases, jobs)
     _, src, offsets, tomb = rga_replay_onto_device(batch, tombstones=True)
     events = [ev for stream in bases for ev in stream] + [ev for _, own in jobs for ev in own]
+    srcl, tl, offl = src.tolist(), tomb.tolist(), offsets.tolist()
+    return [[Elem(events[s][1], events[s][2], bool(tb)) for s, tb in
+             zip(srcl[offl[i]:offl[i + 1]], tl[offl[i]:offl[i + 1]])] for i in range(len(jobs))]
+
+
+@dataclass
+class RgaChainBatch:
+    """Host image of ``smx_rga_chain``: every segment's events once, and the jobs as runs of
+    segment indices."""
+
+    n_segs: int
+    n_jobs: int
+    seg_off: np.ndarray        # i64 [n_segs + 1]
+    job_off: np.ndarray        # i64 [n_jobs + 1], into job_seg
+    job_seg: np.ndarray        # i32 [n_links], strictly ascending within a job
+    op: np.ndarray
+    value: np.ndarray
+    anchor: np.ndarray
+    t: np.ndarray
+    author: np.ndarray
+    opid_hi: np.ndarray
+    opid_lo: np.ndarray
+    values: List[Any]          # column index -> value object
+
+    @property
+    def n(self) -> int:
+        return len(self.op)
+
+    @property
+    def n_links(self) -> int:
+        return len(self.job_seg)
+
+    @property
+    def job_len(self) -> np.ndarray:
+        """Events per job: its segments'."""
+        csum = np.concatenate([[0], np.cumsum(np.diff(self.seg_off)[self.job_seg])]).astype(np.int64)
+        return csum[self.job_off[1:]] - csum[self.job_off[:-1]]
+
+    @property
+    def n_out(self) -> int:
+        return int(self.job_len.sum())
+
+
+def _chain_tables(n_segs: int, jobs: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
+    """(job_off, job_seg) of `jobs`; ValueError for a job whose segment indices are out of range
+    or do not strictly ascend (the column index breaks ties between equal keys, so a job's
+    segments must lie in the columns in the order the job replays them)."""
+    job_off = np.zeros(len(jobs) + 1, np.int64)
+    links: List[int] = []
+    for j, job in enumerate(jobs):
+        prev = -1
+        for s in job:
+            s = int(s)
+            if not 0 <= s < n_segs:
+                raise ValueError(f"job {j}: segment {s} of {n_segs}")
+            if s <= prev:
+                raise ValueError(f"job {j}: segment {s} after segment {prev}: indices must strictly ascend")
+            prev = s
+            links.append(s)
+        job_off[j + 1] = len(links)
+    return job_off, np.asarray(links, np.int32).reshape(len(links))
+
+
+def marshal_chain(segments: Sequence[Sequence[Event]], jobs: Sequence[Sequence[int]]) -> RgaChainBatch:
+    """The columns of ``smx_rga_replay_chain``: each segment marshalled once, all in one id
+    domain (a move or delete in one segment reaches the elements an earlier one created)."""
+    ns = len(segments)
+    job_off, job_seg = _chain_tables(ns, jobs)  # (before anything is marshalled)
+    lid, *cols = _event_columns(segments)
+    seg_off = np.zeros(ns + 1, np.int64)
+    np.cumsum(np.bincount(lid, minlength=ns), out=seg_off[1:])
+    return RgaChainBatch(ns, len(jobs), seg_off, job_off, job_seg, *cols)
+
+
+def chain_columns(batch: RgaChainBatch) -> Tuple[np.ndarray, np.ndarray]:
+    """The jobs' events spelled out: (column index of every event, job by job, segment after
+    segment; the jobs' starts in that array, n_jobs + 1)."""
+    starts = np.concatenate([[0], np.cumsum(batch.job_len)]).astype(np.int64)
+    a, b = int(batch.job_off[0]), int(batch.job_off[-1])
+    parts = [np.arange(batch.seg_off[s], batch.seg_off[s + 1], dtype=np.int64) for s in batch.job_seg[a:b].tolist()]
+    return (np.concatenate(parts) if parts else np.zeros(0, np.int64)), starts
+
+
+def replay_chain(segments: Sequence[Sequence[Event]], jobs: Sequence[Sequence[int]]) -> List[List[Any]]:
+    """Materialize, for every job (a strictly ascending sequence of segment indices), the list
+    that its segments' events build one segment after another --
+    ``replay([sum((segments[s] for s in job), []) for job in jobs])`` with every segment
+    marshalled, copied and stored once."""
+    from ._lib import rga_replay_chain_device  # the HIP library; raises if missing
+    batch = marshal_chain(segments, jobs)
+    _, src, offsets = rga_replay_chain_device(batch)
+    srcl = src.tolist()
+    offl = offsets.tolist()
+    return [[batch.values[s] for s in srcl[offl[i]:offl[i + 1]]] for i in range(len(jobs))]
+
+
+def replay_lists_chain(segments: Sequence[Sequence[Event]], jobs: Sequence[Sequence[int]]) -> List[List[Elem]]:
+    """Every job's final list state, as :func:`replay_lists` returns it for its segments' events
+    one segment after another."""
+    from ._lib import rga_replay_chain_device  # the HIP library; raises if missing
+    batch = marshal_chain(segments, jobs)
+    _, src, offsets, tomb = rga_replay_chain_device(batch, tombstones=True)
+    events = [ev for stream in segments for ev in stream]
     srcl, tl, offl = src.tolist(), tomb.tolist(), offsets.tolist()
     return [[Elem(events[s][1], events[s][2], bool(tb)) for s, tb in
              zip(srcl[offl[i]:offl[i + 1]], tl[offl[i]:offl[i + 1]])] for i in range(len(jobs))]

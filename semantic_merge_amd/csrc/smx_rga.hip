@@ -17,6 +17,7 @@
 // output offset summed by its own wave from per-chunk survivor sums.
 // smx_rga_replay_onto (at the end, smx_rga_onto.h): the same list kernels over jobs, each a
 // base's events followed by its own, read in place from bases that are stored once.
+// smx_rga_replay_chain (after it, smx_rga_chain.h): jobs that are runs of segments stored once.
 #include <algorithm>
 #include <chrono>
 #include <string>
@@ -24,6 +25,7 @@
 #include "smx_scan.h"
 #include "smx_rga_part.h"
 #include "smx_rga_onto.h"
+#include "smx_rga_chain.h"
 #include "smx_wave_sort.h"
 #include "smx_rga_list.h"
 #include "smx_rga_out.h"
@@ -35,16 +37,19 @@ static bool o_ok(const smx_rga_ops* o) {
   return o->list && o->op && o->value && o->anchor && o->t && o->author && o->opid_hi && o->opid_lo;
 }
 
-struct RgaLayout { size_t off[16], total; };
-enum { R_REC, R_REC2, R_KEYS, R_KEYS2, R_RHIST, R_TV, R_TS, R_BST, R_GP, R_DEF2, R_PART, R_LSTART, R_SCNT, R_SOFF, R_JOBS, R_N };
+struct RgaLayout { size_t off[20], total; };
+enum { R_REC, R_REC2, R_KEYS, R_KEYS2, R_RHIST, R_TV, R_TS, R_BST, R_GP, R_DEF2, R_PART, R_LSTART, R_SCNT, R_SOFF, R_JOBS, R_CMAP, R_LLEN, R_LPOS, R_N };
 // R_PART in u32 words: scan_excl's SCAN_NB partials (8 bytes each), then 16 status words (the
 // first 8 zeroed per call): the error word, scan_excl's total, the counts of deferred lists;
-// smx_rga_replay_onto zeroes all 16: the jobs' total length, 64 bits (k_rga_onto_jobs).
+// smx_rga_replay_onto and _chain zero all 16: the jobs' total length, 64 bits (k_rga_onto_jobs,
+// k_rga_chain_check).
 enum { RP_ERR = SCAN_NB * 2, RP_TOTALS = RP_ERR + 2, RP_NDEF = RP_ERR + 4, RP_NDEF_BIG = RP_NDEF + 1,
        RP_ONTO_SUM = RP_ERR + 8, RP_WORDS = RP_ERR + 16 };
 
-// onto (smx_rga_replay_onto): n = n_out, nl = n_jobs; no partition buffers, the jobs' descriptors.
-static RgaLayout rga_layout(i64 n, i64 nl, bool onto = false) {
+// RGA_SRC_ONTO (smx_rga_replay_onto): n = n_out, nl = n_jobs; no partition buffers, the jobs'
+// descriptors.  RGA_SRC_CHAIN (smx_rga_replay_chain): the same without the descriptors, plus the
+// column map (n_out entries) and the links' lengths and first slots (n_links + 1 each).
+static RgaLayout rga_layout(i64 n, i64 nl, int src = RGA_SRC_LISTS, i64 n_links = 0) {
   const i64 nn = n > 0 ? n : 1;
   size_t sz[R_N];
   sz[R_REC] = sz[R_REC2] = (size_t)nn * RGA_REC * 8;
@@ -56,10 +61,12 @@ static RgaLayout rga_layout(i64 n, i64 nl, bool onto = false) {
   sz[R_LSTART] = sz[R_SOFF] = sz[R_DEF2] = (size_t)(nl + 1) * 4;
   // scnt: RGA_CS_MAX chunk sums, then the counts padded to whole 256-list chunks
   sz[R_SCNT] = (size_t)(RGA_CS_MAX + SMX_CEIL_DIV(nl + 1, (i64)RGA_CS_LISTS) * RGA_CS_LISTS) * 4;
-  sz[R_JOBS] = 0;
-  if (onto) {
-    sz[R_REC2] = sz[R_KEYS] = sz[R_KEYS2] = sz[R_RHIST] = 0;
-    sz[R_JOBS] = (size_t)(nl + 1) * 16;
+  sz[R_JOBS] = sz[R_CMAP] = sz[R_LLEN] = sz[R_LPOS] = 0;
+  if (src != RGA_SRC_LISTS) sz[R_REC2] = sz[R_KEYS] = sz[R_KEYS2] = sz[R_RHIST] = 0;
+  if (src == RGA_SRC_ONTO) sz[R_JOBS] = (size_t)(nl + 1) * 16;
+  if (src == RGA_SRC_CHAIN) {
+    sz[R_CMAP] = (size_t)nn * 4;
+    sz[R_LLEN] = sz[R_LPOS] = (size_t)(n_links + 1) * 4;
   }
   RgaLayout L;
   L.total = 0;
@@ -83,7 +90,8 @@ struct RgaWs {
   u32 *totals, *ndef, *ndef_big;  // scan_excl's total; deferred lists (ndef: spare), those for k_rga_big
   u32 *lstart, *csum, *scnt, *soff;  // list starts; 256-list survivor sums, just before the counts; output offsets
   uint4* jobs;                   // smx_rga_replay_onto: the jobs' source descriptors (OntoSrc)
-  unsigned long long* onto_sum;  // and their total length
+  unsigned long long* onto_sum;  // and their total length (smx_rga_replay_chain's jobs' too)
+  u32 *cmap, *llen, *lpos;       // smx_rga_replay_chain: the column map; the links' lengths, their first slots
 };
 
 static RgaWs rga_carve(void* ws, const RgaLayout& L, i64 n) {
@@ -101,6 +109,7 @@ static RgaWs rga_carve(void* ws, const RgaLayout& L, i64 n) {
   w.totals = w.part + RP_TOTALS, w.ndef = w.part + RP_NDEF, w.ndef_big = w.part + RP_NDEF_BIG;
   w.lstart = at(R_LSTART), w.csum = at(R_SCNT), w.scnt = w.csum + RGA_CS_MAX, w.soff = at(R_SOFF);
   w.jobs = (uint4*)at(R_JOBS), w.onto_sum = (unsigned long long*)(w.part + RP_ONTO_SUM);
+  w.cmap = at(R_CMAP), w.llen = at(R_LLEN), w.lpos = at(R_LPOS);
   return w;
 }
 
@@ -234,9 +243,9 @@ static int rga_impl(const smx_rga_ops* ops, const smx_rga_out* out, void* ws, si
   // lists of more than RW_CAP events (a few, if any).  (On a second stream beside
   // k_rga_wave they measured no faster: their workgroups trail k_rga_wave's, and the
   // join costs ~14 us, round 4.)
-  hipLaunchKernelGGL(k_rga_wave2<false>, dim3(64), dim3(WAVE * RW_WAVES), 0, st, o, w.rec, w.lstart, n, nl, w.def2,
+  hipLaunchKernelGGL(k_rga_wave2<RGA_SRC_LISTS>, dim3(64), dim3(WAVE * RW_WAVES), 0, st, o, w.rec, w.lstart, n, nl, w.def2,
                      w.ndef_big, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err, (int)grouped);
-  hipLaunchKernelGGL(k_rga_big<false>, dim3(RGA_BIG_GRID), dim3(1024), 0, st, o, w.rec, w.lstart, n, nl, w.def2, w.ndef_big,
+  hipLaunchKernelGGL(k_rga_big<RGA_SRC_LISTS>, dim3(RGA_BIG_GRID), dim3(1024), 0, st, o, w.rec, w.lstart, n, nl, w.def2, w.ndef_big,
                      w.bst, w.gp, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err);
 
   if (int rc = rga_out_stage(w, nl, out, st)) return rc;
@@ -264,9 +273,9 @@ extern "C" int smx_rga_replay(const smx_rga_ops* ops, const smx_rga_out* out, vo
 // ---------------------------------------------------------------------------
 // smx_rga_replay_onto: many jobs, each a base's events followed by its own, over bases
 // stored once (smx_rga_onto.h).  The pre-pass gives each job its length and slice; the
-// list kernels' ONTO instantiations read a job's events from the two column ranges; the
+// list kernels' RGA_SRC_ONTO instantiations read a job's events from the two column ranges; the
 // output stage is the replay's own, one "list" per job.
-static RgaLayout rga_onto_layout(i64 n_jobs, i64 n_out) { return rga_layout(n_out, n_jobs, true); }
+static RgaLayout rga_onto_layout(i64 n_jobs, i64 n_out) { return rga_layout(n_out, n_jobs, RGA_SRC_ONTO); }
 
 extern "C" int smx_rga_replay_onto_workspace_bytes(int64_t n_jobs, int64_t n_out, size_t* bytes) {
   if (!bytes || n_jobs < 0 || n_out < 0 || n_jobs >= (i64)0x7fffffff || n_out > (i64)RGA_IDX_MASK)
@@ -317,11 +326,11 @@ extern "C" int smx_rga_replay_onto(const smx_rga_onto* onto, const smx_rga_out* 
 
   const int tomb = out->out_tomb != nullptr;
   const i64 n = q.n_total;
-  hipLaunchKernelGGL((k_rga_wave<true, true>), dim3(rga_wave_grid(nj)), dim3(WAVE * RW_WAVES), 0, st, o, w.rec, w.lstart,
+  hipLaunchKernelGGL((k_rga_wave<true, RGA_SRC_ONTO>), dim3(rga_wave_grid(nj)), dim3(WAVE * RW_WAVES), 0, st, o, w.rec, w.lstart,
                      n, nj, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err);
-  hipLaunchKernelGGL(k_rga_wave2<true>, dim3(64), dim3(WAVE * RW_WAVES), 0, st, o, w.rec, w.lstart, n, nj, w.def2,
+  hipLaunchKernelGGL(k_rga_wave2<RGA_SRC_ONTO>, dim3(64), dim3(WAVE * RW_WAVES), 0, st, o, w.rec, w.lstart, n, nj, w.def2,
                      w.ndef_big, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err, 1);
-  hipLaunchKernelGGL(k_rga_big<true>, dim3(RGA_BIG_GRID), dim3(1024), 0, st, o, w.rec, w.lstart, n, nj, w.def2,
+  hipLaunchKernelGGL(k_rga_big<RGA_SRC_ONTO>, dim3(RGA_BIG_GRID), dim3(1024), 0, st, o, w.rec, w.lstart, n, nj, w.def2,
                      w.ndef_big, w.bst, w.gp, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err);
   if (int rc = rga_out_stage(w, nj, out, st)) return rc;
   i32 herr = 0;
@@ -329,5 +338,85 @@ extern "C" int smx_rga_replay_onto(const smx_rga_onto* onto, const smx_rga_out* 
   HIP_TRY(rga_stream_wait(st));
   if (herr & RGA_E_INPUT)
     return smx_set_error(SMX_E_ARG, "invalid input: an op > 2, a bad offset or job_base, or more events than n_out");
+  return SMX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// smx_rga_replay_chain: many jobs, each a run of segments stored once (smx_rga_chain.h).  The
+// pre-pass checks the tables and gives each job its slice and its part of the column map; the
+// list kernels' RGA_SRC_CHAIN instantiations read a job's events through the map; the output
+// stage is the replay's own, one "list" per job.
+static RgaLayout rga_chain_layout(i64 n_jobs, i64 n_links, i64 n_out) {
+  return rga_layout(n_out, n_jobs, RGA_SRC_CHAIN, n_links);
+}
+
+extern "C" int smx_rga_replay_chain_workspace_bytes(int64_t n_jobs, int64_t n_links, int64_t n_out, size_t* bytes) {
+  if (!bytes || n_jobs < 0 || n_links < 0 || n_out < 0 || n_jobs >= (i64)0x7fffffff || n_links >= (i64)0x7fffffff ||
+      n_out > (i64)RGA_IDX_MASK)
+    return smx_set_error(SMX_E_ARG, "bad sizes");
+  *bytes = rga_chain_layout(n_jobs, n_links, n_out).total;
+  return SMX_OK;
+}
+
+extern "C" int smx_rga_replay_chain(const smx_rga_chain* chain, const smx_rga_out* out, void* ws, size_t wsb,
+                                    void* stream) {
+  if (!chain) return smx_set_error(SMX_E_ARG, "null smx_rga_chain");
+  const smx_rga_chain& q = *chain;
+  const i64 nj = q.n_jobs;
+  if (q.n_total < 0 || q.n_segs < 0 || nj < 0 || q.n_links < 0 || q.n_out < 0)
+    return smx_set_error(SMX_E_ARG, "negative size");
+  if (q.n_total > (i64)RGA_IDX_MASK) return smx_set_error(SMX_E_ARG, "n_total too large");
+  if (q.n_out > (i64)RGA_IDX_MASK) return smx_set_error(SMX_E_ARG, "n_out too large");
+  if (q.n_segs >= (i64)0x7fffffff || nj >= (i64)0x7fffffff || q.n_links >= (i64)0x7fffffff)
+    return smx_set_error(SMX_E_ARG, "too many segments, jobs or links");
+  if (!out || !out->out_offsets || !out->counts) return smx_set_error(SMX_E_ARG, "null output");
+  if (q.n_out > 0 && (!out->out_value || !out->out_src)) return smx_set_error(SMX_E_ARG, "null output");
+  if (!q.seg_off || !q.job_off || (q.n_links > 0 && !q.job_seg))
+    return smx_set_error(SMX_E_ARG, "null offsets or job_seg");
+  if (q.n_total > 0 && !(q.op && q.value && q.anchor && q.t && q.author && q.opid_hi && q.opid_lo))
+    return smx_set_error(SMX_E_ARG, "null input pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const RgaLayout L = rga_chain_layout(nj, q.n_links, q.n_out);
+  if (nj > 0) {
+    if (!ws || wsb < L.total)
+      return smx_set_error(SMX_E_WORKSPACE, ("workspace too small: need " + std::to_string(L.total)).c_str());
+    if (reinterpret_cast<uintptr_t>(ws) & 15) return smx_set_error(SMX_E_WORKSPACE, "workspace not 16-byte aligned");
+  }
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  if (nj == 0) {
+    HIP_TRY(hipMemsetAsync(out->out_offsets, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(out->counts, 0, 8, st));
+    return SMX_OK;
+  }
+  const RgaWs w = rga_carve(ws, L, q.n_out > 0 ? q.n_out : 1);
+  // the columns as the list kernels take them; in place of the list ids, the column map
+  const smx_rga_ops o = {q.n_total, nj, w.cmap, q.op, q.value, q.anchor, q.t, q.author, q.opid_hi, q.opid_lo};
+  const RgaChainJobs jq = {q.n_total, q.n_segs, nj, q.n_links, q.n_out, q.seg_off, q.job_off, q.job_seg};
+  HIP_TRY(hipMemsetAsync(w.err, 0, 64, st));
+  if (int rc = rga_device_init()) return rc;
+  // a wave per job, then per link; a thread per entry of the offset tables
+  const i64 waves = std::max(nj, q.n_links), top = std::max(waves, q.n_segs) + 1;
+  const i64 want = std::max(SMX_CEIL_DIV(waves, (i64)(BLOCK / WAVE)), SMX_CEIL_DIV(top, (i64)BLOCK));
+  const int grid = (int)std::min<i64>(want, 2048);
+  hipLaunchKernelGGL(k_rga_chain_check, dim3(grid), dim3(BLOCK), 0, st, jq, w.llen, w.csum, w.onto_sum, w.err);
+  HIP_TRY((scan_excl<OpSum, u32, u32>(w.llen, w.lpos, q.n_links + 1, nullptr, w.part, w.totals, st)));
+  hipLaunchKernelGGL(k_rga_onto_fit, dim3(1), dim3(1), 0, st, w.onto_sum, q.n_out, w.err);
+  hipLaunchKernelGGL(k_rga_chain_map, dim3(grid), dim3(BLOCK), 0, st, jq, w.lpos, w.lstart, w.cmap, w.err);
+
+  const int tomb = out->out_tomb != nullptr;
+  const i64 n = q.n_total;
+  hipLaunchKernelGGL((k_rga_wave<true, RGA_SRC_CHAIN>), dim3(rga_wave_grid(nj)), dim3(WAVE * RW_WAVES), 0, st, o, w.rec,
+                     w.lstart, n, nj, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err);
+  hipLaunchKernelGGL(k_rga_wave2<RGA_SRC_CHAIN>, dim3(64), dim3(WAVE * RW_WAVES), 0, st, o, w.rec, w.lstart, n, nj,
+                     w.def2, w.ndef_big, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err, 1);
+  hipLaunchKernelGGL(k_rga_big<RGA_SRC_CHAIN>, dim3(RGA_BIG_GRID), dim3(1024), 0, st, o, w.rec, w.lstart, n, nj, w.def2,
+                     w.ndef_big, w.bst, w.gp, w.tmp_v, w.tmp_s, w.scnt, tomb, w.err);
+  if (int rc = rga_out_stage(w, nj, out, st)) return rc;
+  i32 herr = 0;
+  HIP_TRY(hipMemcpyAsync(&herr, w.err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(rga_stream_wait(st));
+  if (herr & RGA_E_INPUT)
+    return smx_set_error(SMX_E_ARG, "invalid input: an op > 2, a bad offset or job_seg, segments that do not ascend "
+                                    "within a job, or more events than n_out");
   return SMX_OK;
 }

@@ -5,11 +5,14 @@
 __device__ __forceinline__ u32 rga_lend(const u32* lstart, u32 l, i64 nl, i64 n) {
   return l + 1 < nl ? lstart[l + 1] : (u32)n;
 }
-// ONTO (smx_rga_replay_onto): a "list" is a job, lstart the jobs' slice starts, nl + 1 of
-// them (smx_rga_onto.h: the total is known on the device alone)
-template <bool ONTO>
+// Where the list kernels' events come from.  RGA_SRC_LISTS: the lists of smx_rga_replay.
+// RGA_SRC_ONTO (smx_rga_replay_onto) and RGA_SRC_CHAIN (smx_rga_replay_chain): a "list" is a
+// job, lstart the jobs' slice starts, nl + 1 of them (smx_rga_onto.h, smx_rga_chain.h: the
+// total is known on the device alone)
+enum { RGA_SRC_LISTS = 0, RGA_SRC_ONTO = 1, RGA_SRC_CHAIN = 2 };
+template <int SRC>
 __device__ __forceinline__ u32 rga_lend_of(const u32* lstart, u32 l, i64 nl, i64 n) {
-  if constexpr (ONTO) return lstart[l + 1];
+  if constexpr (SRC != RGA_SRC_LISTS) return lstart[l + 1];
   else return rga_lend(lstart, l, nl, n);
 }
 
@@ -109,6 +112,9 @@ struct RwLds {
 //  OntoSrc the input columns, for a job of smx_rga_replay_onto: its first lb events are
 //          its base's (columns b0 ...), the others its own (columns dq + lb ...); the words
 //          as ColSrc builds them, the index being the column.  An op > 2 raises the error word.
+//  ChainSrc the input columns, for a job of smx_rga_replay_chain: event e is column cm[e], cm
+//          the job's part of the column map (k_rga_chain_map), one coalesced 4-byte load; the
+//          words and the op check as OntoSrc's.
 struct RecSrc {
   const u64* p;  // the list's first record
   __device__ __forceinline__ u64 w0(u32 e) const { return p[(u64)e * RGA_REC]; }
@@ -152,6 +158,29 @@ struct OntoSrc {
 __device__ __forceinline__ OntoSrc rga_onto_src(const smx_rga_ops& o, u32 job, const i32* gate) {
   const uint4 d = reinterpret_cast<const uint4*>(o.list)[job];
   return OntoSrc{o.anchor, o.t, o.value, o.op, const_cast<i32*>(gate), d.x, d.y, d.z};
+}
+
+struct ChainSrc {
+  const u32* anchor;
+  const i64* t;
+  const u32* value;
+  const u8* op;
+  i32* err;
+  const u32* cm;  // the column of the job's event 0 (cmap + the job's slice start)
+  __device__ __forceinline__ u32 col(u32 e) const { return cm[e]; }
+  __device__ __forceinline__ u64 w0(u32 e) const {
+    const u32 j = col(e);
+    return ((u64)anchor[j] << 32) | (((u64)t[j] ^ 0x8000000000000000ull) >> 32);
+  }
+  __device__ __forceinline__ u64 w1(u32 e) const {
+    const u32 j = col(e), op3 = op[j];
+    if (op3 > 2) atomicOr(err, (i32)RGA_E_INPUT);
+    return ((u64)value[j] << 32) | ((op3 > 2 ? 0u : op3) << 30) | j;
+  }
+};
+// A job's source from the column map (kept where a batch keeps its list ids) and its slice start
+__device__ __forceinline__ ChainSrc rga_chain_src(const smx_rga_ops& o, u32 s0, const i32* gate) {
+  return ChainSrc{o.anchor, o.t, o.value, o.op, const_cast<i32*>(gate), o.list + s0};
 }
 
 // Event a before event b of one list in (key, index) order (crdt.py:48-57): word 0
@@ -475,7 +504,7 @@ __device__ __forceinline__ u32 rga_wave_list(const smx_rga_ops& o, const SRC src
   return m;
 }
 
-template <bool DIRECT, bool ONTO = false>
+template <bool DIRECT, int SRC = RGA_SRC_LISTS>
 __global__ void __launch_bounds__(WAVE * RW_WAVES) RW_OCC k_rga_wave(smx_rga_ops o, const u64* __restrict__ R,
                                                              const u32* __restrict__ lstart,
                                                              i64 n, i64 nl, u32* __restrict__ tmp_v,
@@ -496,7 +525,7 @@ __global__ void __launch_bounds__(WAVE * RW_WAVES) RW_OCC k_rga_wave(smx_rga_ops
   const u32 L0 = min((u64)wid * per, (u64)nl), L1 = min((u64)L0 + per, (u64)nl);
   u32 acc = 0;
   for (u32 l = L0; l < L1; ++l) {
-    const u32 s0 = lstart[l], cnt = rga_lend_of<ONTO>(lstart, l, nl, n) - s0;
+    const u32 s0 = lstart[l], cnt = rga_lend_of<SRC>(lstart, l, nl, n) - s0;
     if (cnt <= RW_CAP) {  // (longer lists: k_rga_wave2 / k_rga_big count themselves)
       // the lane id laundered per list: otherwise the compiler hoists every lane-derived
       // constant of the list code out of the loop and keeps it live
@@ -508,7 +537,8 @@ __global__ void __launch_bounds__(WAVE * RW_WAVES) RW_OCC k_rga_wave(smx_rga_ops
         if (cnt <= 128) return rga_wave_list<2>(o, src, l, s0, cnt, lds[w], ln, tomb != 0, tmp_v, tmp_s, scnt);
         return rga_wave_list<4>(o, src, l, s0, cnt, lds[w], ln, tomb != 0, tmp_v, tmp_s, scnt);
       };
-      if constexpr (ONTO) m = run(rga_onto_src(o, l, gate));
+      if constexpr (SRC == RGA_SRC_ONTO) m = run(rga_onto_src(o, l, gate));
+      else if constexpr (SRC == RGA_SRC_CHAIN) m = run(rga_chain_src(o, s0, gate));
       else if constexpr (DIRECT) m = run(ColSrc{o.anchor, o.t, o.value, o.op, s0});
       else m = run(RecSrc{R + (u64)s0 * RGA_REC});
       if (lane == 0) scnt[l] = m;
@@ -522,10 +552,22 @@ __global__ void __launch_bounds__(WAVE * RW_WAVES) RW_OCC k_rga_wave(smx_rga_ops
   }
 }
 
+// A wave writes the records of a list's cnt events, read through cs, to rw.
+template <class CS>
+__device__ __forceinline__ void rw_records(const CS cs, u64* rw, u32 cnt, u32 lane) {
+  for (u32 e = lane; e < cnt; e += WAVE) {
+    R16 r;
+    r.a = cs.w0(e);
+    r.b = cs.w1(e);
+    *reinterpret_cast<R16*>(rw + (u64)e * RGA_REC) = r;
+  }
+  __threadfence_block();  // (this wave reads them back; k_rga_big after this kernel)
+}
+
 // Lists of RW_CAP + 1 .. 2 * RW_CAP events: the same wave per list with twice the
 // slots; longer ones go on to k_rga_big.  Each wave sweeps 64 lists at a time for the
 // long ones itself (k_rga_wave skips them; no hand-off list).
-template <bool ONTO = false>
+template <int SRC = RGA_SRC_LISTS>
 __global__ void __launch_bounds__(WAVE * RW_WAVES) k_rga_wave2(smx_rga_ops o, const u64* __restrict__ R,
                                                               const u32* __restrict__ lstart,
                                                               i64 n, i64 nl, u32* __restrict__ defer,
@@ -538,33 +580,17 @@ __global__ void __launch_bounds__(WAVE * RW_WAVES) k_rga_wave2(smx_rga_ops o, co
   const u64 nw = (u64)gridDim.x * RW_WAVES;
   for (u64 l0 = ((u64)blockIdx.x * RW_WAVES + w) * WAVE; l0 < (u64)nl; l0 += nw * WAVE) {
     const u64 me = l0 + lane;
-    const u32 c = me < (u64)nl ? rga_lend_of<ONTO>(lstart, (u32)me, nl, n) - lstart[me] : 0u;
+    const u32 c = me < (u64)nl ? rga_lend_of<SRC>(lstart, (u32)me, nl, n) - lstart[me] : 0u;
     u64 todo = __ballot(c > RW_CAP);
     while (todo) {
       const u32 l = (u32)(l0 + (u64)(__ffsll((unsigned long long)todo) - 1));
       todo &= todo - 1;
-      const u32 s0 = lstart[l], cnt = rga_lend_of<ONTO>(lstart, l, nl, n) - s0;
-      if constexpr (ONTO) {  // a long job's records from its two column ranges, into its slice
-        const OntoSrc cs = rga_onto_src(o, l, gate);
-        u64* rw = const_cast<u64*>(R) + (u64)s0 * RGA_REC;
-        for (u32 e = lane; e < cnt; e += WAVE) {
-          R16 r;
-          r.a = cs.w0(e);
-          r.b = cs.w1(e);
-          *reinterpret_cast<R16*>(rw + (u64)e * RGA_REC) = r;
-        }
-        __threadfence_block();
-      } else if (direct) {  // grouped events, no partition: this long list's records from the columns
-        const ColSrc cs{o.anchor, o.t, o.value, o.op, s0};
-        u64* rw = const_cast<u64*>(R) + (u64)s0 * RGA_REC;
-        for (u32 e = lane; e < cnt; e += WAVE) {
-          R16 r;
-          r.a = cs.w0(e);
-          r.b = cs.w1(e);
-          *reinterpret_cast<R16*>(rw + (u64)e * RGA_REC) = r;
-        }
-        __threadfence_block();  // (this wave reads them back; k_rga_big after this kernel)
-      }
+      const u32 s0 = lstart[l], cnt = rga_lend_of<SRC>(lstart, l, nl, n) - s0;
+      // no partition: a long list's or job's records from the columns, into its slice
+      u64* rw = const_cast<u64*>(R) + (u64)s0 * RGA_REC;
+      if constexpr (SRC == RGA_SRC_CHAIN) rw_records(rga_chain_src(o, s0, gate), rw, cnt, lane);
+      else if constexpr (SRC == RGA_SRC_ONTO) rw_records(rga_onto_src(o, l, gate), rw, cnt, lane);
+      else if (direct) rw_records(ColSrc{o.anchor, o.t, o.value, o.op, s0}, rw, cnt, lane);  // (grouped events)
       if (cnt > 2 * RW_CAP) {
         if (lane == 0) defer[atomicAdd(ndefer, 1u)] = l;
         continue;
@@ -604,13 +630,13 @@ __device__ void block_sort_positions(u32* p, u32 cnt, Less less) {
 // (such lists are rare — a whole file's history in one list).  Per list, in its
 // record range: gp = positions sorted by (value, index), bst = state by that order;
 // then the survivors' positions sorted by (key, index).
-template <bool ONTO>
+template <int SRC>
 __device__ void rga_big_list(const smx_rga_ops& o, const u64* __restrict__ R, u32 l, const u32* __restrict__ lstart, i64 n, i64 nl,
                              u8* __restrict__ bst, u32* __restrict__ gp, u32* __restrict__ tmp_v,
                              u32* __restrict__ tmp_s, u32* __restrict__ scnt, bool tomb) {
   __shared__ u32 ns;
   const u32 t = threadIdx.x, NT = blockDim.x;
-  const u32 s0 = lstart[l], cnt = rga_lend_of<ONTO>(lstart, l, nl, n) - s0;
+  const u32 s0 = lstart[l], cnt = rga_lend_of<SRC>(lstart, l, nl, n) - s0;
   const u64* L = R + (u64)s0 * RGA_REC;
   u8* S = bst + s0;
   u32* G = gp + s0;
@@ -668,7 +694,7 @@ __device__ void rga_big_list(const smx_rga_ops& o, const u64* __restrict__ R, u3
 #define RGA_BIG_GRID 32  // workgroups of k_rga_big (lists of > 2 RW_CAP events, one per workgroup at a time;
                          // 256 cost ~5 us of launch on every call, most of which have none)
 #endif
-template <bool ONTO = false>
+template <int SRC = RGA_SRC_LISTS>
 __global__ void __launch_bounds__(1024) k_rga_big(smx_rga_ops o, const u64* __restrict__ R,
                                                   const u32* __restrict__ lstart, i64 n,
                                                   i64 nl, const u32* __restrict__ todo, const u32* __restrict__ ntodo,
@@ -678,6 +704,6 @@ __global__ void __launch_bounds__(1024) k_rga_big(smx_rga_ops o, const u64* __re
   if (*gate & RGA_E_UNGROUPED) return;
   for (u32 item = blockIdx.x; item < *ntodo; item += gridDim.x) {
     __syncthreads();
-    rga_big_list<ONTO>(o, R, todo[item], lstart, n, nl, bst, gp, tmp_v, tmp_s, scnt, tomb != 0);
+    rga_big_list<SRC>(o, R, todo[item], lstart, n, nl, bst, gp, tmp_v, tmp_s, scnt, tomb != 0);
   }
 }
