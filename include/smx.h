@@ -15,6 +15,8 @@
  *   smx_compose_train <- that loop in a loop: a merge train over such logs, each log
  *                    composed against what landed before it, conflicting logs put off
  *                    (what semmerge/__main__.py:65-69 does to one merge, per step)
+ *   smx_compose_tree <- the same for trains that share prefixes (a speculative merge queue,
+ *                    every prefix of a commit stack): a tree of logs, every node composed once
  *   smx_train_stage, smx_train_land <- one step of that loop for trains of any size: the
  *                    materialise, marshal and copy between two compose_oplogs calls, as two
  *                    gathers on either side of smx_compose
@@ -620,6 +622,100 @@ int smx_compose_train_workspace_bytes(int64_t n_logs, int64_t n_trains, int64_t 
  * call; n_trains = 0 returns SMX_OK and launches nothing. */
 int smx_compose_train(const struct smx_train* t, void* workspace, size_t workspace_bytes, uint32_t flags,
                       void* stream);
+
+/*
+ * Merge trains that share prefixes, composed once.  A speculative merge queue
+ * wants the state after pull request 1, after 1+2, ... and the fallbacks that drop a member; a
+ * rebase wants the composed log after every commit of a stack.  Those trains form a tree, and a
+ * root-to-node path of the tree is a train of smx_compose_train.  Here every node is composed
+ * once, its accumulator is a result, and it is where all its children start.  The logs are laid
+ * out as smx_train takes them.
+ *
+ * The n_nodes nodes are stored level by level: level d is the nodes [level_off[d],
+ * level_off[d+1]).  node_parent[n] is SMX_NONE for a node of level 0 and a node of level d-1 for
+ * a node of level d; node_log[n] is its log.  A log may be in any number of nodes, and more than
+ * once on a path.
+ *
+ * Node n composes (the accumulator of its parent as A, log node_log[n] as B) exactly as step g
+ * of smx_compose_train does: the same staging rule (v1_alt, empty_str), the same landing rule,
+ * the same records.  A node of level 0 starts from the empty accumulator.  With zero conflicts
+ * the node lands, and its accumulator, the composed log, is written as src / addr / file / ctx
+ * entries into its own region [res_off[n], res_off[n+1]).  Any other outcome (conflicts, -1,
+ * -2 below) leaves the node's accumulator as its parent's, and nothing is copied.
+ *
+ *   node_acc     [n]: the node whose region holds n's accumulator: n itself if it landed, else
+ *                node_acc[parent]; SMX_NONE if no node of its root path landed (the accumulator
+ *                is empty)
+ *   node_counts  [2n]: the accumulator's length after the node, whatever happened;
+ *                [2n+1]: >= 0 the node's conflicts (0: it landed);
+ *                        -1 a log index outside [0, n_logs), a log invalid under smx_screen's
+ *                           log_off rules, or an op with kind >= 18 or sym >= n_sym in it;
+ *                        -2 accumulator plus log exceed 2048 ops
+ *   conflicts    per node n the first conf_off[n+1] - conf_off[n] records at conflicts[4 *
+ *                conf_off[n]], the full number in node_counts[2n+1], nothing at or past the
+ *                capacity (a negative or decreasing conf_off gives the node none).  A record is
+ *                smx_train's: the A op's column index, the B op's column index, and the addr and
+ *                the file the A op carried in the parent's accumulator.
+ *
+ * So for every valid node n, node_counts[2n], node_counts[2n+1], its records and the accumulator
+ * reached through node_acc[n] equal what smx_compose_train reports for the last step and the
+ * final accumulator of the train that is n's root path.
+ *
+ * A node fails structurally -- node_counts[2n] = node_counts[2n+1] = -1, node_acc[n] = SMX_NONE,
+ * nothing else written -- when
+ *   - it lies in no valid level.  Level d is valid when level_off[d] is not negative and not
+ *     below an earlier entry, level_off[d+1] is not below level_off[d] and not past n_nodes,
+ *     level 0 starts at node 0 and the last level ends at n_nodes;
+ *   - its parent is not in the level before (no node is in an invalid level), or it is of
+ *     level 0 and has a parent;
+ *   - its res_off entries are negative, below an earlier entry, decreasing or past n_out;
+ *   - its region is smaller than min(2048, the sum of the valid logs' lengths on its root path);
+ *   - its parent failed structurally.
+ * All of this is checked on the device before any column of the node is read through an
+ * unchecked index.  Failed nodes never touch their neighbours.
+ *
+ * Stream-ordered: a pre-pass, then per level one launch for each of the three size classes of
+ * smx_compose_batch (256 / 1024 / 2048 ops, by min(path sum, 2048)): 1 + 3 * n_levels launches
+ * whatever the data.  A level depends on the level before through stream order alone: no
+ * workgroup waits for another one.  No host synchronisation, no allocation, no read-back; the
+ * call clears the workspace state it needs, so one workspace serves any sequence of calls.
+ * grid_cap caps every launch.  flags must be 0.
+ */
+#define SMX_TREE_MAX_LEVELS 4096
+typedef struct smx_tree {
+  int64_t n_logs, n_total, n_nodes, n_levels, n_sym, n_out;   /* n_levels: a host scalar */
+  const int64_t* log_off;                 /* device [n_logs+1], as smx_screen */
+  const uint8_t* kind; const uint64_t* ts, *oid_hi, *oid_lo;
+  const uint32_t* sym; const int32_t* v0, *v1;     /* as smx_ops, n_total entries, one id domain for all logs */
+  const int32_t* v1_alt;                  /* as smx_train */
+  const int64_t* level_off;               /* device [n_levels+1], into the nodes */
+  const int32_t* node_parent;             /* device [n_nodes]: a node of the level before, or SMX_NONE */
+  const int32_t* node_log;                /* device [n_nodes]: log indices */
+  const int64_t* res_off;                 /* device [n_nodes+1]: node n's accumulator at [res_off[n], res_off[n+1]) */
+  int32_t* src, *addr, *file, *ctx;       /* n_out entries */
+  int32_t* conflicts; const int64_t* conf_off;     /* 4 int32 per record; conf_off [n_nodes+1], in records */
+  int64_t* node_counts;                   /* [2*n_nodes]: accumulator length after the node, its outcome */
+  int32_t* node_acc;                      /* [n_nodes]: the node whose region holds the accumulator */
+  int32_t grid_cap;                       /* as smx_batch */
+  int32_t empty_str;                      /* as smx_train */
+} smx_tree;
+/* Workspace (8-byte aligned), linear in its arguments, each term rounded up to 256 bytes: 4
+ * bytes per log, 20 per node (two verdicts and the three class lists), 20 per level (its class
+ * counts and a verdict) and 57 per entry of n_out (37 of staged columns, 16 of a step's scratch
+ * result, 4 of its conflict pairs); no state buffers: the accumulators live in the result
+ * regions.  n_logs, n_nodes, n_out in 0 .. 2^31 - 1, n_levels in 0 .. SMX_TREE_MAX_LEVELS;
+ * flags 0. */
+int smx_compose_tree_workspace_bytes(int64_t n_logs, int64_t n_nodes, int64_t n_levels, int64_t n_out,
+                                     uint32_t flags, size_t* bytes);
+/* SMX_E_ARG (a non-zero flag; then a null struct, negative sizes, n_levels over
+ * SMX_TREE_MAX_LEVELS, n_logs, n_nodes, n_total or n_out over 2^31 - 1, grid_cap < 0,
+ * empty_str < -1, n_sym > 2^32 - 1; a null v1_alt with empty_str >= 0 and n_total > 0; a null
+ * level_off / node_parent / node_log / res_off / conf_off / conflicts / node_counts / node_acc,
+ * a null log_off with n_logs > 0, a null column with n_total > 0, a null result array with
+ * n_out > 0) and SMX_E_WORKSPACE (too small, or not 8-byte aligned) are reported before any HIP
+ * call; n_nodes = 0 returns SMX_OK and launches nothing. */
+int smx_compose_tree(const struct smx_tree* t, void* workspace, size_t workspace_bytes, uint32_t flags,
+                     void* stream);
 
 /*
  * One step of a merge train of any size, as two calls on either side of smx_compose (DESIGN.md

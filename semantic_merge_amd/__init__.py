@@ -3,7 +3,7 @@ from .ops import Op, Target  # noqa: F401
 from .conflict import Conflict  # noqa: F401
 
 __all__ = ["Op", "Target", "Conflict", "compose_oplogs", "compose_many", "compose_against",
-           "compose_pairs", "compose_train", "screen_conflicts", "screen_all", "screen_train"]
+           "compose_pairs", "compose_train", "compose_tree", "screen_conflicts", "screen_all", "screen_train"]
 
 
 def __getattr__(name):
@@ -23,6 +23,9 @@ def __getattr__(name):
     if name == "compose_train":
         from .compose import compose_train
         return compose_train
+    if name == "compose_tree":
+        from .compose import compose_tree
+        return compose_tree
     if name == "screen_conflicts":
         from .compose import screen_conflicts
         return screen_conflicts

@@ -189,6 +189,43 @@ class SmxTrain(C.Structure):
     ]
 
 
+TREE_MAX_LEVELS = 4096  # SMX_TREE_MAX_LEVELS
+
+
+class SmxTree(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_int64),
+        ("n_total", C.c_int64),
+        ("n_nodes", C.c_int64),
+        ("n_levels", C.c_int64),
+        ("n_sym", C.c_int64),
+        ("n_out", C.c_int64),
+        ("log_off", C.c_void_p),
+        ("kind", C.c_void_p),
+        ("ts", C.c_void_p),
+        ("oid_hi", C.c_void_p),
+        ("oid_lo", C.c_void_p),
+        ("sym", C.c_void_p),
+        ("v0", C.c_void_p),
+        ("v1", C.c_void_p),
+        ("v1_alt", C.c_void_p),
+        ("level_off", C.c_void_p),
+        ("node_parent", C.c_void_p),
+        ("node_log", C.c_void_p),
+        ("res_off", C.c_void_p),
+        ("src", C.c_void_p),
+        ("addr", C.c_void_p),
+        ("file", C.c_void_p),
+        ("ctx", C.c_void_p),
+        ("conflicts", C.c_void_p),
+        ("conf_off", C.c_void_p),
+        ("node_counts", C.c_void_p),
+        ("node_acc", C.c_void_p),
+        ("grid_cap", C.c_int32),
+        ("empty_str", C.c_int32),
+    ]
+
+
 class SmxTrainStep(C.Structure):
     _fields_ = [
         ("n_total", C.c_int64),
@@ -392,6 +429,8 @@ EXPORTS = (
     "smx_compose_pairs",
     "smx_compose_train_workspace_bytes",
     "smx_compose_train",
+    "smx_compose_tree_workspace_bytes",
+    "smx_compose_tree",
     "smx_train_stage",
     "smx_train_land",
     "smx_screen_workspace_bytes",
@@ -471,6 +510,12 @@ def declare(lib: C.CDLL) -> C.CDLL:
         lib.smx_compose_train_workspace_bytes.restype = C.c_int
         lib.smx_compose_train.argtypes = [C.POINTER(SmxTrain), C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
         lib.smx_compose_train.restype = C.c_int
+    if hasattr(lib, "smx_compose_tree"):  # (older builds, e.g. A/B baselines, lack it)
+        lib.smx_compose_tree_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32,
+                                                         C.POINTER(C.c_size_t)]
+        lib.smx_compose_tree_workspace_bytes.restype = C.c_int
+        lib.smx_compose_tree.argtypes = [C.POINTER(SmxTree), C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+        lib.smx_compose_tree.restype = C.c_int
     if hasattr(lib, "smx_train_stage"):  # (older builds, e.g. A/B baselines, lack it)
         for f in ("smx_train_stage", "smx_train_land"):
             getattr(lib, f).argtypes = [C.POINTER(SmxTrainStep), C.c_void_p]

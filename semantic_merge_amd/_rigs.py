@@ -413,6 +413,103 @@ class DeviceTrains(_DeviceMany):
         return out
 
 
+class DeviceTree(_DeviceMany):
+    """Device-resident inputs, outputs and workspace for repeated smx_compose_tree calls on a
+    LogsSoA and a tree in level order (tests, tools/tree_probe.py): `parents` and `node_log` per
+    node, `level_off` the levels' bounds (_session.tree_levels gives all three for a tree in any
+    order).  The optional arguments reach the corners of the C ABI (include/smx.h smx_tree):
+    conflict_caps per-node capacities in conflict records (default: the node's log's length,
+                  which always suffices);
+    grid_cap      smx_tree.grid_cap;
+    log_off       the offsets passed instead of the LogsSoA's own;
+    res_off       the result offsets passed (default: min(2048, the sum of the logs' lengths on
+                  its root path) per node, one after another; a log index outside the logs
+                  counts as empty);
+    n_sym, n_total, n_levels, n_out  passed instead of the real ones;
+    v1_alt, empty_str  smx_tree's two (default: none, SMX_NONE);
+    fill          every output word (results, conflict records, node counts, node_acc) starts as
+                  this value, and CONF_GUARD such words follow the last regions;
+    share         another DeviceTree or DeviceTrains with a workspace at least as large: its
+                  workspace is used instead of a new one."""
+
+    _OUT = ("src", "addr", "file", "ctx", "conf", "node_counts", "node_acc")
+
+    def __init__(self, lsoa, parents, node_log, level_off, device: str = "cuda", conflict_caps=None,
+                 grid_cap: int = 0, log_off=None, res_off=None, n_sym: Optional[int] = None,
+                 n_total: Optional[int] = None, n_levels: Optional[int] = None, n_out: Optional[int] = None,
+                 fill: Optional[int] = None, v1_alt=None, empty_str: int = -1, share=None) -> None:
+        self._open(device)
+        torch, dev = self.torch, self.device
+        self.lsoa = lsoa
+        self._alt = None if v1_alt is None else self._up(np.asarray(v1_alt, np.int32))
+        L = self.n_logs = lsoa.n_logs
+        self.parents = np.asarray(parents, np.int32).reshape(-1)
+        N = self.n_nodes = len(self.parents)
+        self.node_log = np.asarray(node_log, np.int32).reshape(N)
+        self.level_off = np.asarray(level_off, np.int64).reshape(-1)
+        D = self.n_levels = len(self.level_off) - 1
+        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
+        tot = self.n_total = int(lsoa.n_total)
+        lens = np.diff(np.asarray(lsoa.log_off, np.int64))
+        ok = (self.node_log >= 0) & (self.node_log < L)
+        self.node_len = np.where(ok, lens[np.where(ok, self.node_log, 0)], 0) if L else np.zeros(N, np.int64)
+        if res_off is None:
+            psum = np.zeros(N, np.int64)
+            for n in range(N):  # (level order: a parent lies before its children)
+                p = int(self.parents[n])
+                psum[n] = (psum[p] if 0 <= p < n else 0) + self.node_len[n]
+            res_off = np.concatenate([[0], np.cumsum(np.minimum(psum, _abi.BATCH_MAX_OPS), dtype=np.int64)])
+        self.res_off = np.asarray(res_off, np.int64).reshape(N + 1)
+        self.n_out = max(int(self.res_off.max()), 0) if N else 0
+        self.n_sym = int(lsoa.n_sym) if n_sym is None else n_sym
+        self._upload_cols([lsoa])
+        self.conf_off = np.zeros(N + 1, np.int64)
+        np.cumsum(self.node_len if conflict_caps is None else conflict_caps, out=self.conf_off[1:])
+        f = 0 if fill is None else fill
+        for name in self._OUT[:4]:
+            setattr(self, name, torch.full((self.n_out + self.CONF_GUARD,), f, dtype=torch.int32, device=dev))
+        self.conf = torch.full((4 * max(int(self.conf_off.max()), 0) + self.CONF_GUARD,), f, dtype=torch.int32,
+                               device=dev)
+        self.node_counts = torch.full((2 * N + self.CONF_GUARD,), f, dtype=torch.int64, device=dev)
+        self.node_acc = torch.full((N + self.CONF_GUARD,), f, dtype=torch.int32, device=dev)
+        if share is None:
+            self._workspace(lib().smx_compose_tree_workspace_bytes, L, N, D, self.n_out, 0)
+        else:
+            ws = C.c_size_t(0)
+            check(lib().smx_compose_tree_workspace_bytes(L, N, D, self.n_out, 0, C.byref(ws)))
+            if share.ws_bytes < ws.value:
+                raise ValueError("share: a rig whose workspace is at least as large")
+            self.ws_bytes, self.ws = share.ws_bytes, share.ws
+        self._idx = [self._up(self.log_off), self._up(self.level_off), self._up(self.parents),
+                     self._up(self.node_log), self._up(self.res_off), self._up(self.conf_off)]
+        self._call = lambda arg, ws, nbytes, st: lib().smx_compose_tree(arg, ws, nbytes, 0, st)
+        self._arg = _abi.SmxTree(L, tot if n_total is None else n_total, N, D if n_levels is None else n_levels,
+                                 self.n_sym, self.n_out if n_out is None else n_out, self._idx[0].data_ptr(),
+                                 *[t.data_ptr() for t in self._in], _ptr(self._alt), self._idx[1].data_ptr(),
+                                 self._idx[2].data_ptr(), self._idx[3].data_ptr(), self._idx[4].data_ptr(),
+                                 self.src.data_ptr(), self.addr.data_ptr(), self.file.data_ptr(),
+                                 self.ctx.data_ptr(), self.conf.data_ptr(), self._idx[5].data_ptr(),
+                                 self.node_counts.data_ptr(), self.node_acc.data_ptr(), grid_cap, empty_str)
+
+    def results(self, raw: Optional[dict] = None):
+        """Per node -1 for one that failed structurally, else (src, addr, file, ctx, acc, length,
+        outcome, records): the accumulator after the node, read through node_acc (`acc`: that
+        node, or -1 for an empty accumulator) and trimmed to the node's count, the node's
+        outcome, and its conflict records as an (n, 4) array trimmed to its capacity."""
+        r = self.raw() if raw is None else raw
+        out = []
+        for n in range(self.n_nodes):
+            k, oc, acc = int(r["node_counts"][2 * n]), int(r["node_counts"][2 * n + 1]), int(r["node_acc"][n])
+            if k < 0:
+                out.append(-1)
+                continue
+            c = int(self.conf_off[n])
+            nc = min(max(oc, 0), max(int(self.conf_off[n + 1]) - c, 0)) if c >= 0 else 0
+            o = int(self.res_off[acc]) if acc >= 0 else 0
+            out.append(tuple(r[x][o: o + k] for x in self._OUT[:4]) + (acc, k, oc, r["conf"][4 * c: 4 * (c + nc)].reshape(nc, 4)))
+        return out
+
+
 class DeviceTrainLoop(_DeviceMany):
     """One train of any size on device-resident columns, as the host loop of smx_train_stage,
     smx_compose and smx_train_land (_session.run_train_loop; tests, tools/train_loop_probe.py).

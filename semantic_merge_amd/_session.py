@@ -84,6 +84,29 @@ def screen_results(hout, conf_at: int, counts_at: int, conf_off, pairs) -> list:
             for p in range(P)]
 
 
+def tree_levels(parents):
+    """A tree given as per-node parents in the caller's order (None or -1: a root; a parent
+    precedes its children) in the level order smx_compose_tree takes: (order, level_off, back).
+    order[i] is the caller's index of the node stored at i -- level by level, nodes of a level
+    in the caller's order --, level_off the levels' bounds (int64 [n_levels + 1]) and back its
+    inverse: back[order[i]] = i.  A parent at or after its child raises ValueError, an index
+    outside the nodes IndexError."""
+    par = [-1 if p is None else int(p) for p in parents]
+    n = len(par)
+    depth = np.zeros(n, np.int64)
+    for i, p in enumerate(par):
+        if p < -1 or p >= n:
+            raise IndexError(f"node {i}: parent {p} outside the {n} nodes")
+        if p >= i:
+            raise ValueError(f"node {i}: parent {p} does not precede it")
+        depth[i] = depth[p] + 1 if p >= 0 else 0
+    order = np.argsort(depth, kind="stable").astype(np.int64)
+    level_off = np.concatenate([[0], np.cumsum(np.bincount(depth, minlength=0), dtype=np.int64)]).astype(np.int64)
+    back = np.empty(n, np.int64)
+    back[order] = np.arange(n, dtype=np.int64)
+    return order, level_off, back
+
+
 def run_train_loop(st: int, base, state, log_off, train, rec_off, ws, status_host, hook=None, n_acc: int = 0):
     """One train of any size as a host loop over device-resident columns (include/smx.h
     smx_train_step): per step smx_train_stage, smx_compose on the staged columns with
@@ -719,6 +742,86 @@ class ComposeSession:
         self.last = _last(pack_s=t1 - t0, device_s=t2 - t1, unpack_s=time.perf_counter() - t2, in_bytes=lay["in_bytes"])
         return res
 
+    # -- trains that share prefixes: a tree of logs, every node composed once (smx_compose_tree) --
+
+    def compose_tree(self, lsoa, parents, node_log, v1_alt=None, empty_str: int = -1):
+        """Per node of a tree over a LogsSoA what smx_compose_tree leaves, in the caller's order:
+        (state, acc, length, outcome, records).  parents[n]: the node's parent (None or -1: a
+        root; a parent precedes its children, tree_levels), node_log[n]: its log.  state: the
+        node's own accumulator (src, addr, file, ctx) if it landed, else None; acc: the node
+        whose state is this node's accumulator (itself if it landed, -1: the accumulator is
+        empty), `length` entries long; outcome: its conflicts, or -2 (accumulator plus log over
+        BATCH_MAX_OPS ops), reported as it is; records: its conflict records as an (n, 4) array.
+        The columns, every log once, are staged as they are: one host-to-device copy, one
+        smx_compose_tree, one copy back, one stream sync, whatever the tree.  Invalid input raises
+        SmxError naming the node.  v1_alt, empty_str: smx_tree's two (marshal.move_file_alt).
+        The results are copies.  `last` holds the call's legs and "in_bytes"."""
+        t0 = time.perf_counter()
+        order, level_off, back = tree_levels(parents)
+        N, D, L, tot = len(order), len(level_off) - 1, lsoa.n_logs, int(lsoa.n_total)
+        self.last = _last(("in_bytes",))
+        if N == 0:
+            return []
+        if D > _abi.TREE_MAX_LEVELS:
+            raise SmxError(-1, f"a tree of {D} levels: over SMX_TREE_MAX_LEVELS ({_abi.TREE_MAX_LEVELS})")
+        logs = np.asarray(node_log, np.int32).reshape(N)
+        if int(logs.min()) < 0 or int(logs.max()) >= L:
+            raise SmxError(-1, f"node {int(np.flatnonzero((logs < 0) | (logs >= L))[0])}: a log index outside [0, {L})")
+        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
+        lens = log_off[1:] - log_off[:-1]
+        if int(log_off[0]) < 0 or (lens < 0).any() or int(log_off[-1]) > tot:
+            raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
+        par = np.asarray([-1 if p is None else int(p) for p in parents], np.int64)
+        # (level order: the stored parent is the caller's parent's place)
+        lv_par = np.where(par[order] >= 0, back[np.maximum(par[order], 0)], -1).astype(np.int32)
+        lv_log = np.ascontiguousarray(logs[order])
+        lv_len = lens[lv_log]
+        psum = np.zeros(N, np.int64)
+        for d in range(D):  # (a level's path sums from the level before)
+            a, b = int(level_off[d]), int(level_off[d + 1])
+            psum[a:b] = lv_len[a:b] + (psum[lv_par[a:b]] if d else 0)
+        res_off = np.concatenate([[0], np.cumsum(np.minimum(psum, _abi.BATCH_MAX_OPS), dtype=np.int64)])
+        conf_off = np.concatenate([[0], np.cumsum(lv_len, dtype=np.int64)])  # (at most a conflict per op of the log)
+        n_out, n_conf = int(res_off[-1]), int(conf_off[-1])
+        alt = np.zeros(tot, np.int32) if v1_alt is None else np.ascontiguousarray(v1_alt, dtype=np.int32)
+        lay = self._compose_layout(tot, [("v1_alt", tot * 4), ("log_off", (L + 1) * 8), ("level_off", (D + 1) * 8),
+                                         ("node_parent", N * 4), ("node_log", N * 4), ("res_off", (N + 1) * 8),
+                                         ("conf_off", (N + 1) * 8)], n_out, 16 * n_conf, 0)
+        lay["node_acc"] = lay["counts"] + _al(16 * N)
+        lay["out_bytes"] = lay["node_acc"] + 4 * N
+        q = lay["q"]
+        t1, t2 = self._staged_call(
+            self.main, lib().smx_compose_tree_workspace_bytes, (L, N, D, n_out, 0), lay,
+            [(getattr(lsoa, name), lay[name], tot * dt.itemsize) for name, dt, _ in OP_COLS],
+            (("v1_alt", alt), ("log_off", log_off), ("level_off", level_off), ("node_parent", lv_par),
+             ("node_log", lv_log), ("res_off", res_off), ("conf_off", conf_off)),
+            lambda d0, o0: _abi.SmxTree(L, tot, N, D, int(lsoa.n_sym), n_out, d0 + lay["log_off"],
+                                        *[d0 + lay[name] for name, _, _ in OP_COLS], d0 + lay["v1_alt"],
+                                        d0 + lay["level_off"], d0 + lay["node_parent"], d0 + lay["node_log"],
+                                        d0 + lay["res_off"], o0, o0 + q, o0 + 2 * q, o0 + 3 * q, o0 + lay["conf"],
+                                        d0 + lay["conf_off"], o0 + lay["counts"], o0 + lay["node_acc"], 0,
+                                        int(empty_str)),
+            lambda arg, ws, nbytes, st: lib().smx_compose_tree(arg, ws, nbytes, 0, st))
+        hout = self.main.hout
+        counts = hout[lay["counts"]: lay["counts"] + 16 * N].view(np.int64).tolist()
+        acc = hout[lay["node_acc"]: lay["node_acc"] + 4 * N].view(np.int32).tolist()
+        conf = hout[lay["conf"]: lay["conf"] + 16 * n_conf].view(np.int32).reshape(-1, 4)
+        res = [None] * N
+        for i in range(N):
+            n, k, oc = int(order[i]), counts[2 * i], counts[2 * i + 1]
+            if k < 0:
+                raise SmxError(-1, f"node {n}: invalid input")
+            if oc == -1:
+                raise SmxError(-1, f"node {n}: invalid input: sym >= n_sym or kind >= 18")
+            state = None
+            if acc[i] == i:
+                o = int(res_off[i])
+                state = tuple(hout[f * q + 4 * o: f * q + 4 * (o + k)].view(np.int32).copy() for f in range(4))
+            c = int(conf_off[i])
+            res[n] = (state, int(order[acc[i]]) if acc[i] >= 0 else -1, k, oc, conf[c: c + max(oc, 0)].copy())
+        self.last = _last(pack_s=t1 - t0, device_s=t2 - t1, unpack_s=time.perf_counter() - t2, in_bytes=lay["in_bytes"])
+        return res
+
     # -- one train of any size: the host loop of smx_train_stage, smx_compose, smx_train_land ----
 
     def compose_train_loop(self, lsoa, train, v1_alt=None, empty_str: int = -1):
@@ -1109,6 +1212,11 @@ def compose_pairs_soa(lsoa, pairs, device: str = "cuda", large: bool = False, la
 def compose_trains_soa(lsoa, trains, device: str = "cuda", v1_alt=None, empty_str: int = -1):
     """ComposeSession.compose_trains on the thread's free session: the trains over a LogsSoA in one call."""
     return _free_session(device).compose_trains(lsoa, trains, v1_alt=v1_alt, empty_str=empty_str)
+
+
+def compose_tree_soa(lsoa, parents, node_log, device: str = "cuda", v1_alt=None, empty_str: int = -1):
+    """ComposeSession.compose_tree on the thread's free session: a tree of logs over a LogsSoA in one call."""
+    return _free_session(device).compose_tree(lsoa, parents, node_log, v1_alt=v1_alt, empty_str=empty_str)
 
 
 def screen_soa(lsoa, pairs, device: str = "cuda", large: bool = False):

@@ -202,6 +202,74 @@ def compose_train(logs: Sequence[Sequence[Any]], trains: Optional[Sequence[Seque
     return res
 
 
+def compose_tree(logs: Sequence[Sequence[Any]], nodes: Sequence[Tuple[Optional[int], int]],
+                 want: Any = "leaves") -> List[Tuple[Optional[List[Any]], List[Any]]]:
+    """Merge trains that share prefixes, over logs given once: a speculative merge queue (the
+    state after pull request 1, after 1+2, ... and the fallbacks that drop a member), every
+    prefix of a commit stack.  ``nodes``: per node ``(parent, log)`` -- the index of an earlier
+    node or ``None`` for a root, and a log index; the node's root path is a train of
+    ``compose_train``: the node composes its log against what landed on the way to it, and a
+    node that conflicts leaves that state to its children.  Per node the result is
+    ``(ops, conflicts)``: ``conflicts`` is the node's step's conflicts (an empty list: it
+    landed), and ``ops`` what has landed after the node, for the nodes ``want`` selects --
+    ``"leaves"``, ``"all"`` or an iterable of node indices -- and ``None`` for the others; equal,
+    per node, to the host loop over ``compose_oplogs`` on its root path.  Every log is marshalled
+    and copied to the GPU once and every node is composed once, whatever the number of paths
+    through it (one copy in, one smx_compose_tree, one copy back, one sync); the ops are
+    materialised once per selected node.  A node whose accumulator and log exceed 2048 ops, and
+    every node below it, is computed by the host loop instead.  A parent that does not precede
+    its node raises ``ValueError``, an index outside the nodes or the logs ``IndexError``.
+    Inputs are never mutated."""
+    from ._session import tree_levels
+    ops = [list(x) for x in logs]
+    nodes = [(None if p is None else int(p), int(l)) for p, l in nodes]
+    parents = [p for p, _ in nodes]
+    tree_levels(parents)  # (the parents' checks)
+    for n, (_, l) in enumerate(nodes):
+        if not 0 <= l < len(ops):
+            raise IndexError(f"node {n}: log {l} outside the {len(ops)} logs")
+    N = len(nodes)
+    if N == 0:
+        return []
+    if isinstance(want, str):
+        if want not in ("leaves", "all"):
+            raise ValueError("want must be 'leaves', 'all' or node indices")
+        inner = {p for p in parents if p is not None}
+        chosen = set(range(N)) if want == "all" else set(range(N)) - inner
+    else:
+        chosen = {int(n) for n in want}
+        for n in chosen:
+            if not 0 <= n < N:
+                raise IndexError(f"want: node {n} outside the {N} nodes")
+    make = conflict_factory()
+    with dropin_session() as sess:
+        lsoa = marshal_logs(ops)
+        flat = [o for x in ops for o in x]
+        alt, empty = move_file_alt(flat, lsoa.kind, lsoa.strings)
+        found = sess.compose_tree(lsoa, parents, [l for _, l in nodes], v1_alt=alt, empty_str=empty)
+    res: List[Any] = []
+    on_host = [False] * N  # the node or one above it reports -2
+    for n, (state, acc, _, oc, recs) in enumerate(found):
+        p = parents[n]
+        on_host[n] = oc == -2 or (p is not None and on_host[p])
+        if on_host[n]:
+            path, up = [], n
+            while up is not None:
+                path.append(nodes[up][1])
+                up = parents[up]
+            out, steps = _train_on_host(ops, path[::-1])
+            res.append((out if n in chosen else None, steps[-1]))
+            continue
+        out = None
+        if n in chosen:
+            src, addr, file, ctx = found[acc][0] if acc >= 0 else (np.zeros(0, np.int32),) * 4
+            out = materialize_ops_native(flat, lsoa.kind, lsoa.strings, src, addr, file, ctx)
+        a = materialize_ops_native(flat, lsoa.kind, lsoa.strings, recs[:, 0], recs[:, 2], recs[:, 3],
+                                   np.full(len(recs), -1, np.int32)) if len(recs) else []
+        res.append((out, [make(x, flat[b]) for x, b in zip(a, recs[:, 1].tolist())]))
+    return res
+
+
 def screen_train(logs: Sequence[Sequence[Any]], trains: Optional[Sequence[Sequence[int]]] = None
                  ) -> List[List[List[Tuple[Tuple[int, int], Tuple[int, int]]]]]:
     """Which logs fall off a merge train, and over which ops, without composing anything: per

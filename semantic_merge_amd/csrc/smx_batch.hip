@@ -6,7 +6,9 @@
 // smx_compose_train (kernels in smx_train.h), the class launch over trains, with
 // smx_train_stage / smx_train_land beside it (kernels in smx_train_step.h, DESIGN.md §23: one
 // step of a train of any size, a launch each and no workspace), and
-// smx_screen_train (kernels in smx_screen_train.h), the screen's over trains.
+// smx_screen_train (kernels in smx_screen_train.h), the screen's over trains, and
+// smx_compose_tree (kernels in smx_tree.h), the class launch once per level of a
+// tree of logs.
 //
 // All three have one shape: a pre-pass sorts the items (merges, pairs) into three size
 // classes, then one kernel per class runs its list on a grid capped by what the device
@@ -26,6 +28,7 @@
 #include "smx_train.h"
 #include "smx_train_step.h"
 #include "smx_screen_train.h"
+#include "smx_tree.h"
 
 // The kernels with a residency-capped grid, and the threads of a workgroup of each.
 enum {
@@ -41,7 +44,8 @@ enum {
   R_LARGE_PAIRS = 17,
   R_TRAIN = 18,
   R_SCREEN_TRAIN = 21,
-  R_N = 24
+  R_TREE = 24,
+  R_N = 27
 };
 template <typename B>
 using BatchKernel = void (*)(B, const u32*, const u32*);
@@ -58,6 +62,9 @@ static constexpr TrainKernel kTrainKernels[BATCH_CLASSES] = {
 typedef void (*ScreenTrainKernel)(ScreenTrainArgs, ScreenWs, const u32*, const u32*);
 static constexpr ScreenTrainKernel kScreenTrainKernels[SCREEN_CLASSES] = {
     k_screen_train<screen_class_cap(0)>, k_screen_train<screen_class_cap(1)>, k_screen_train<screen_class_cap(2)>};
+typedef void (*TreeKernel)(smx_tree, TreeWs, i32, const u32*, const u32*);
+static constexpr TreeKernel kTreeKernels[BATCH_CLASSES] = {
+    k_compose_tree<batch_class_cap(0)>, k_compose_tree<batch_class_cap(1)>, k_compose_tree<batch_class_cap(2)>};
 static constexpr int kBatchCaps[BATCH_CLASSES] = {batch_class_cap(0), batch_class_cap(1), batch_class_cap(2)};
 static constexpr int kScreenCaps[SCREEN_CLASSES] = {screen_class_cap(0), screen_class_cap(1), screen_class_cap(2)};
 
@@ -81,7 +88,9 @@ static int resident_of(const int** out) {
       fn[R_SHARED + c] = (const void*)kBatchKernels<smx_batch_shared>[c];
       fn[R_PAIRS + c] = (const void*)kBatchKernels<smx_pairs>[c];
       fn[R_TRAIN + c] = (const void*)kTrainKernels[c];
-      threads[R_BATCH + c] = threads[R_SHARED + c] = threads[R_PAIRS + c] = threads[R_TRAIN + c] = kBatchCaps[c] / 2;
+      fn[R_TREE + c] = (const void*)kTreeKernels[c];
+      threads[R_BATCH + c] = threads[R_SHARED + c] = threads[R_PAIRS + c] = threads[R_TRAIN + c] =
+          threads[R_TREE + c] = kBatchCaps[c] / 2;
     }
     fn[R_EXTRACT] = (const void*)k_screen_extract;
     threads[R_EXTRACT] = SCREEN_T1;
@@ -394,6 +403,65 @@ extern "C" int smx_compose_train(const struct smx_train* b, void* workspace, siz
     HIP_TRY(hipGetLastError());
     return launch_classes(kTrainKernels, kBatchCaps, resident + R_TRAIN, b->n_trains, b->grid_cap, st, w.cnt, w.lists,
                           w.stride, *b, w);
+  } catch (const std::exception& e) {
+    return smx_set_error(SMX_E_HIP, e.what());
+  }
+}
+
+extern "C" int smx_compose_tree_workspace_bytes(int64_t n_logs, int64_t n_nodes, int64_t n_levels, int64_t n_out,
+                                                uint32_t flags, size_t* bytes) {
+  if (flags) return smx_set_error(SMX_E_ARG, "unknown smx_compose_tree flag");
+  if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
+  if (n_logs < 0 || n_logs > 0x7fffffffll || n_nodes < 0 || n_nodes > 0x7fffffffll || n_out < 0 ||
+      n_out > 0x7fffffffll)
+    return smx_set_error(SMX_E_ARG, "n_logs, n_nodes or n_out outside 0 .. 2^31 - 1");
+  if (n_levels < 0 || n_levels > TREE_MAX_LEVELS)
+    return smx_set_error(SMX_E_ARG, "n_levels outside 0 .. SMX_TREE_MAX_LEVELS");
+  *bytes = tree_ws_bytes(n_logs, n_nodes, n_levels, n_out);
+  return SMX_OK;
+}
+
+// The checks; then the pre-pass (k_tree_prepass) and, level by level, the three classes'
+// k_compose_tree.
+extern "C" int smx_compose_tree(const struct smx_tree* b, void* workspace, size_t workspace_bytes, uint32_t flags,
+                                void* stream) {
+  if (flags) return smx_set_error(SMX_E_ARG, "unknown smx_compose_tree flag");
+  if (!b) return smx_set_error(SMX_E_ARG, "null tree struct");
+  if (b->n_logs < 0 || b->n_total < 0 || b->n_nodes < 0 || b->n_levels < 0 || b->n_sym < 0 || b->n_out < 0 ||
+      b->grid_cap < 0 || b->empty_str < SMX_NONE)
+    return smx_set_error(SMX_E_ARG, "negative size, or empty_str below SMX_NONE");
+  if (b->n_levels > TREE_MAX_LEVELS) return smx_set_error(SMX_E_ARG, "n_levels over SMX_TREE_MAX_LEVELS");
+  if (b->n_sym > 0xffffffffll) return smx_set_error(SMX_E_ARG, "n_sym over 2^32 - 1");
+  if (b->n_logs > 0x7fffffffll || b->n_nodes > 0x7fffffffll) return smx_set_error(SMX_E_ARG, "n_logs or n_nodes over 2^31 - 1");
+  if (b->n_total > 0x7fffffffll || b->n_out > 0x7fffffffll)
+    return smx_set_error(SMX_E_ARG, "n_total or n_out over 2^31 - 1");
+  if (b->n_nodes == 0) return SMX_OK;
+  if (!b->level_off || !b->node_parent || !b->node_log || !b->res_off || !b->conf_off || !b->conflicts ||
+      !b->node_counts || !b->node_acc)
+    return smx_set_error(SMX_E_ARG,
+                         "null level_off / node_parent / node_log / res_off / conf_off / conflicts / node_counts / node_acc");
+  if (b->n_logs > 0 && !b->log_off) return smx_set_error(SMX_E_ARG, "null log_off");
+  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1))
+    return smx_set_error(SMX_E_ARG, "null column");
+  if (b->n_total > 0 && b->empty_str >= 0 && !b->v1_alt) return smx_set_error(SMX_E_ARG, "null v1_alt with empty_str set");
+  if (b->n_out > 0 && (!b->src || !b->addr || !b->file || !b->ctx)) return smx_set_error(SMX_E_ARG, "null result array");
+  if (!workspace || ((uintptr_t)workspace & 7) ||
+      workspace_bytes < tree_ws_bytes(b->n_logs, b->n_nodes, b->n_levels, b->n_out))
+    return smx_set_error(SMX_E_WORKSPACE,
+                         "workspace too small or not 8-byte aligned (smx_compose_tree_workspace_bytes)");
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  try {
+    const int* resident;
+    if (int rc = resident_of(&resident)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const TreeWs w = tree_ws(workspace, b->n_logs, b->n_nodes, b->n_levels, b->n_out);
+    hipLaunchKernelGGL(k_tree_prepass, dim3(1), dim3(1024), 0, st, *b, w);
+    HIP_TRY(hipGetLastError());
+    for (i32 d = 0; d < (i32)b->n_levels; ++d)
+      if (int rc = launch_classes(kTreeKernels, kBatchCaps, resident + R_TREE, b->n_nodes, b->grid_cap, st,
+                                  w.lcnt + 4 * d, w.lists, w.stride, *b, w, d))
+        return rc;
+    return SMX_OK;
   } catch (const std::exception& e) {
     return smx_set_error(SMX_E_HIP, e.what());
   }
