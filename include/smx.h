@@ -24,6 +24,8 @@
  *                    looks at first), for many pairs of logs, from the logs' renames
  *   smx_screen_train <- the conflict lists of smx_compose_train's steps alone, from the
  *                    logs' renames, for trains of any size
+ *   smx_screen_tree <- the same for trains that share prefixes: smx_compose_tree's tree, every
+ *                    node screened once, no size refused
  *   smx_rga_replay <- semmerge/crdt.py:23-57  RGA.insert/move/delete/materialize,
  *                    batched over many independent lists
  *   smx_rga_replay_onto <- the same, for many event streams replayed onto base lists that
@@ -865,6 +867,94 @@ int smx_screen_train_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_
  * any HIP call; n_trains = 0 returns SMX_OK and launches nothing. */
 int smx_screen_train(const struct smx_screen_train* t, void* workspace, size_t workspace_bytes, uint32_t flags,
                      void* stream);
+
+/*
+ * Conflict screen of merge trains that share prefixes: which nodes of smx_compose_tree's tree
+ * have DivergentRename conflicts, and which ones, from the logs' renames alone.
+ * The logs and the columns are laid out as smx_screen_train takes them, the nodes as smx_tree
+ * takes them: level by level, node_parent[n] SMX_NONE for a node of level 0 and a node of level
+ * d-1 for a node of level d, node_log[n] its log.  As far as conflicts go an accumulator is a
+ * sorted list of rename records (smx_screen_train above).  Node n walks its parent's list (A)
+ * against its log's sorted renames (B); without conflicts it merges the two stably, A first on
+ * equal (ts, oid_hi, oid_lo), into its own region, where all its children start.  Every log's
+ * renames are extracted and sorted once and every node is walked once, however many root paths
+ * run through it.  Nothing is composed, and no size is refused: there is no -2.
+ *
+ * For every valid node n, node_counts[2n], node_counts[2n+1] and the written records equal what
+ * smx_screen_train reports (step_counts and records) for the last step of the train that is n's
+ * root path.  So they also equal, wherever smx_compose_tree / smx_compose_train report a count,
+ * that count and the first two words of each of their records.
+ *
+ *   node_counts  [2n]: the renames in the accumulator after the node, whatever happened;
+ *                [2n+1]: >= 0 the node's conflicts (0: it landed; a log without renames lands
+ *                        and leaves the accumulator's renames as they were);
+ *                        -1 a log index outside [0, n_logs), a log invalid under smx_screen's
+ *                           log_off rules, or an op with kind >= 18 in it: the accumulator
+ *                           stays the parent's, and the children go on from it
+ *   conflicts    per node n the first conf_off[n+1] - conf_off[n] records at conflicts[2 *
+ *                conf_off[n]], two int32 each (the A op's column index, the B op's column index),
+ *                the full number in node_counts[2n+1], nothing at or past the node's region (a
+ *                negative or decreasing conf_off gives the node none).  conflicts and conf_off
+ *                both NULL: capacity 0 everywhere (counts only).
+ *   acc_off      node n may hold acc_off[n+1] - acc_off[n] renames.  Let P(n) be the sum, over
+ *                the nodes of n's root path with valid logs (n included), of their logs' rename
+ *                counts.  A node whose own log is valid and has renames needs at least P(n); any
+ *                other node needs nothing (it writes no accumulator: the list stays where its
+ *                parent's is).  Region space is quadratic in the depth of a stack, and
+ *                rename-free logs, the common ones, cost none.
+ *
+ * A node fails structurally -- node_counts[2n] = node_counts[2n+1] = -1, nothing else written --
+ * when
+ *   - it lies in no valid level (smx_tree's rules: level_off[d] not negative and not below an
+ *     earlier entry, level_off[d+1] not below level_off[d] and not past n_nodes, level 0 starts
+ *     at node 0 and the last level ends at n_nodes);
+ *   - its parent is not in the level before (no node is in an invalid level), or it is of
+ *     level 0 and has a parent;
+ *   - its acc_off entries are negative, below an earlier entry, decreasing or past n_acc;
+ *   - its region is below the room rule (checked on the device from the extracted counts);
+ *   - its parent failed structurally.
+ * All of this is checked on the device before any index is read through.  Failed nodes never
+ * touch their neighbours.
+ *
+ * Stream-ordered: the offsets' check, the two extraction launches of SMX_SCREEN_LARGE over every
+ * log, a pre-pass over the nodes, then per level one launch for each of the three size classes
+ * of smx_screen (128 / 512 / 2048 renames, by min(P(n), 2048); a node whose own log is invalid
+ * or has no renames is of the smallest class): 4 + 3 * n_levels launches whatever the data.  A
+ * node of more than 2048 renames runs in rounds.  A level depends on the level before through
+ * stream order alone: no workgroup waits for another one.  No host synchronisation, no
+ * allocation, no read-back; the call clears the workspace state it needs, so one workspace
+ * serves any sequence of smx_screen_tree, smx_screen_train and smx_screen_ex calls it is large
+ * enough for.  grid_cap caps every launch.  flags must be 0.
+ */
+struct smx_screen_tree {
+  int64_t n_logs, n_total, n_nodes, n_levels, n_acc;   /* n_levels: a host scalar, as smx_tree */
+  const int64_t* log_off;                 /* device [n_logs+1], as smx_screen */
+  const uint8_t* kind; const uint64_t* ts, *oid_hi, *oid_lo;
+  const uint32_t* sym; const int32_t* v0;          /* as smx_screen: n_total entries, no v1, no n_sym */
+  const int64_t* level_off;               /* device [n_levels+1], into the nodes, as smx_tree */
+  const int32_t* node_parent;             /* device [n_nodes]: a node of the level before, or SMX_NONE */
+  const int32_t* node_log;                /* device [n_nodes]: log indices */
+  const int64_t* acc_off;                 /* device [n_nodes+1]: node n's room in renames, entries up to n_acc */
+  int32_t* conflicts; const int64_t* conf_off;     /* 2 int32 per record; conf_off [n_nodes+1], in records;
+                                                      both NULL: counts only */
+  int64_t* node_counts;                   /* [2*n_nodes]: the accumulator's renames after the node, its outcome */
+  int32_t grid_cap;                       /* as smx_batch; also caps the per-log launches */
+};
+/* Workspace (8-byte aligned), linear in its arguments, each term rounded up to 256 bytes: a
+ * 256-byte header, 4 bytes per log, 28 per node (the three class lists, two verdicts and the node
+ * that holds its accumulator), 20 per level (its class counts and a verdict), 44 per op (36 of
+ * rename records, 8 of the large logs' index arrays) and 36 per entry of n_acc.  n_logs,
+ * n_total, n_nodes, n_acc in 0 .. 2^31 - 1, n_levels in 0 .. SMX_TREE_MAX_LEVELS; flags 0. */
+int smx_screen_tree_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_nodes, int64_t n_levels,
+                                    int64_t n_acc, uint32_t flags, size_t* bytes);
+/* SMX_E_ARG (a non-zero flag; then a null struct, negative sizes, n_levels over
+ * SMX_TREE_MAX_LEVELS, n_logs, n_total, n_nodes or n_acc over 2^31 - 1, grid_cap < 0, exactly one
+ * of conflicts / conf_off null; a null level_off / node_parent / node_log / acc_off /
+ * node_counts, a null log_off with n_logs > 0, a null column with n_total > 0) and
+ * SMX_E_WORKSPACE (too small, or not 8-byte aligned) are reported before any HIP call;
+ * n_nodes = 0 returns SMX_OK and launches nothing. */
+int smx_screen_tree(const struct smx_screen_tree* t, void* workspace, size_t workspace_bytes, uint32_t flags,
+                    void* stream);
 
 /*
  * Sharded single merge: one process per GPU, shard r of G.

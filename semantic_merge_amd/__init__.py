@@ -3,7 +3,8 @@ from .ops import Op, Target  # noqa: F401
 from .conflict import Conflict  # noqa: F401
 
 __all__ = ["Op", "Target", "Conflict", "compose_oplogs", "compose_many", "compose_against",
-           "compose_pairs", "compose_train", "compose_tree", "screen_conflicts", "screen_all", "screen_train"]
+           "compose_pairs", "compose_train", "compose_tree", "screen_conflicts", "screen_all", "screen_train",
+           "screen_tree"]
 
 
 def __getattr__(name):
@@ -35,4 +36,7 @@ def __getattr__(name):
     if name == "screen_train":
         from .compose import screen_train
         return screen_train
+    if name == "screen_tree":
+        from .compose import screen_tree
+        return screen_tree
     raise AttributeError(name)

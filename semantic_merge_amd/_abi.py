@@ -295,7 +295,32 @@ class SmxScreenTrain(C.Structure):
     ]
 
 
-CAND_MAX_LOGS = 16384        # logs per smx_screen_candidates call (include/smx.h SMX_CAND_MAX_LOGS)
+class SmxScreenTree(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_int64),
+        ("n_total", C.c_int64),
+        ("n_nodes", C.c_int64),
+        ("n_levels", C.c_int64),
+        ("n_acc", C.c_int64),
+        ("log_off", C.c_void_p),
+        ("kind", C.c_void_p),
+        ("ts", C.c_void_p),
+        ("oid_hi", C.c_void_p),
+        ("oid_lo", C.c_void_p),
+        ("sym", C.c_void_p),
+        ("v0", C.c_void_p),
+        ("level_off", C.c_void_p),
+        ("node_parent", C.c_void_p),
+        ("node_log", C.c_void_p),
+        ("acc_off", C.c_void_p),
+        ("conflicts", C.c_void_p),
+        ("conf_off", C.c_void_p),
+        ("node_counts", C.c_void_p),
+        ("grid_cap", C.c_int32),
+    ]
+
+
+CAND_MAX_LOGS = 16384       # logs per smx_screen_candidates call (include/smx.h SMX_CAND_MAX_LOGS)
 SCREEN_MAX_RENAMES = 2048     # renames per pair of smx_screen, both logs together (more: counts -2)
 SCREEN_CLASSES = (128, 512, 2048)  # its size classes, in renames (csrc/smx_screen.h)
 BATCH_MAX_OPS = 2048          # ops per merge of smx_compose_batch (larger: counts -2)
@@ -441,6 +466,8 @@ EXPORTS = (
     "smx_screen_candidates",
     "smx_screen_train_workspace_bytes",
     "smx_screen_train",
+    "smx_screen_tree_workspace_bytes",
+    "smx_screen_tree",
     "smx_shard_step",
     "smx_shard_range_info",
     "smx_set_profiling",
@@ -541,6 +568,11 @@ def declare(lib: C.CDLL) -> C.CDLL:
         lib.smx_screen_train_workspace_bytes.restype = C.c_int
         lib.smx_screen_train.argtypes = [C.POINTER(SmxScreenTrain), C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
         lib.smx_screen_train.restype = C.c_int
+    if hasattr(lib, "smx_screen_tree"):  # (older builds, e.g. A/B baselines, lack it)
+        lib.smx_screen_tree_workspace_bytes.argtypes = [C.c_int64] * 5 + [C.c_uint32, C.POINTER(C.c_size_t)]
+        lib.smx_screen_tree_workspace_bytes.restype = C.c_int
+        lib.smx_screen_tree.argtypes = [C.POINTER(SmxScreenTree), C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+        lib.smx_screen_tree.restype = C.c_int
     lib.smx_shard_step.argtypes = [C.POINTER(SmxOps), C.POINTER(SmxShard), C.POINTER(SmxComposeOut),
                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
     lib.smx_shard_step.restype = C.c_int

@@ -225,10 +225,10 @@ def rga_replay_chain_device(batch, device: str = "cuda", tombstones: bool = Fals
 # both modules import this one.
 _MOVED = {**dict.fromkeys(("ComposeSession", "session", "dropin_session", "compose_soa", "compose_soa_many",
                           "compose_soa_shared", "compose_pairs_soa", "compose_trains_soa", "compose_tree_soa", "tree_levels", "screen_soa", "screen_all_soa",
-                          "screen_trains_soa"),
+                          "screen_trains_soa", "screen_tree_soa"),
                           "_session"),
           **dict.fromkeys(("DeviceCompose", "DeviceBatch", "DeviceBatchShared", "DevicePairs", "DeviceTrains", "DeviceTree", "DeviceScreen",
-                           "DeviceScreenTrains", "DeviceCandidates"), "_rigs")}
+                           "DeviceScreenTrains", "DeviceScreenTree", "DeviceCandidates"), "_rigs")}
 
 
 def __getattr__(name: str):

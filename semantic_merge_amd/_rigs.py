@@ -757,6 +757,99 @@ class DeviceScreenTrains(_DeviceMany):
         return out
 
 
+class DeviceScreenTree(_DeviceMany):
+    """Device-resident inputs, outputs and workspace for repeated smx_screen_tree calls on a
+    LogsSoA and a tree in level order (tests, tools/screen_tree_probe.py): `parents` and `node_log`
+    per node, `level_off` the levels' bounds (_session.tree_levels gives all three for a tree in
+    any order).  The optional arguments reach the corners of the C ABI (include/smx.h
+    smx_screen_tree):
+    conf_caps     per-node capacities in conflict records (default: the renames of the node's
+                  log, which always suffices); "null": conflicts and conf_off are NULL;
+    conf_off      the record offsets passed instead of the capacities' running sum;
+    grid_cap      smx_screen_tree.grid_cap;
+    log_off       the offsets passed instead of the LogsSoA's own;
+    acc_off       the accumulator offsets passed (default: the room rule, _session.tree_room, one
+                  region after another; a log index outside the logs counts as empty);
+    n_total, n_levels, n_acc  passed instead of the real ones;
+    fill          every output word (conflict records, node counts) starts as this value, and
+                  CONF_GUARD such words follow the last regions;
+    share         another screen rig with a workspace at least as large: its workspace is used
+                  instead of a new one."""
+
+    _OUT = ("conf", "node_counts")
+
+    def __init__(self, lsoa, parents, node_log, level_off, device: str = "cuda", conf_caps=None, grid_cap: int = 0,
+                 log_off=None, acc_off=None, conf_off=None, n_total: Optional[int] = None,
+                 n_levels: Optional[int] = None, n_acc: Optional[int] = None, fill: Optional[int] = None,
+                 share=None) -> None:
+        from ._session import tree_room
+        self._open(device)
+        torch, dev = self.torch, self.device
+        self.lsoa = lsoa
+        L = self.n_logs = lsoa.n_logs
+        self.parents = np.asarray(parents, np.int32).reshape(-1)
+        N = self.n_nodes = len(self.parents)
+        self.node_log = np.asarray(node_log, np.int32).reshape(N)
+        self.level_off = np.asarray(level_off, np.int64).reshape(-1)
+        D = self.n_levels = len(self.level_off) - 1
+        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
+        tot = self.n_total = int(lsoa.n_total)
+        ren = _rename_counts(lsoa.kind, lsoa.log_off)
+        ok = (self.node_log >= 0) & (self.node_log < L)
+        self.node_ren = np.where(ok, ren[np.where(ok, self.node_log, 0)], 0).astype(np.int64) if L \
+            else np.zeros(N, np.int64)
+        if acc_off is None:
+            acc_off = np.concatenate([[0], np.cumsum(tree_room(self.parents, self.node_ren), dtype=np.int64)])
+        self.acc_off = np.asarray(acc_off, np.int64).reshape(N + 1)
+        self.n_acc = max(int(self.acc_off.max()), 0) if N else 0
+        self.null_conf = isinstance(conf_caps, str) and conf_caps == "null"
+        self._upload_cols([lsoa], SCREEN_COLS)
+        self.conf_off = np.zeros(N + 1, np.int64)
+        if conf_off is not None:
+            self.conf_off = np.asarray(conf_off, np.int64).reshape(N + 1)
+        elif not self.null_conf:
+            np.cumsum(self.node_ren if conf_caps is None else conf_caps, out=self.conf_off[1:])
+        f = 0 if fill is None else fill
+        self.conf = torch.full((2 * max(int(self.conf_off.max()), 0) + self.CONF_GUARD,), f, dtype=torch.int32,
+                               device=dev)
+        self.node_counts = torch.full((2 * N + self.CONF_GUARD,), f, dtype=torch.int64, device=dev)
+        n_acc = self.n_acc if n_acc is None else n_acc
+        sizes = (L, tot, N, D, max(n_acc, self.n_acc, 0), 0)
+        if share is None:
+            self._workspace(lib().smx_screen_tree_workspace_bytes, *sizes)
+        else:
+            ws = C.c_size_t(0)
+            check(lib().smx_screen_tree_workspace_bytes(*sizes, C.byref(ws)))
+            if share.ws_bytes < ws.value:
+                raise ValueError("share: a rig whose workspace is at least as large")
+            self.ws_bytes, self.ws = share.ws_bytes, share.ws
+        self._idx = [self._up(self.log_off), self._up(self.level_off), self._up(self.parents),
+                     self._up(self.node_log), self._up(self.acc_off), self._up(self.conf_off)]
+        self._call = lambda arg, ws, nbytes, st: lib().smx_screen_tree(arg, ws, nbytes, 0, st)
+        self._arg = _abi.SmxScreenTree(L, tot if n_total is None else n_total, N, D if n_levels is None else n_levels,
+                                       n_acc, self._idx[0].data_ptr(), *[_ptr(t) for t in self._in],
+                                       self._idx[1].data_ptr(), _ptr(self._idx[2]), _ptr(self._idx[3]),
+                                       self._idx[4].data_ptr(), 0 if self.null_conf else self.conf.data_ptr(),
+                                       0 if self.null_conf else self._idx[5].data_ptr(),
+                                       self.node_counts.data_ptr(), grid_cap)
+
+    def results(self, raw: Optional[dict] = None):
+        """Per node -1 for one that failed structurally, else (renames, outcome, records): the
+        renames in the accumulator after the node, its outcome, and its conflict records as an
+        (n, 2) array trimmed to its capacity."""
+        r = self.raw() if raw is None else raw
+        out = []
+        for n in range(self.n_nodes):
+            k, oc = int(r["node_counts"][2 * n]), int(r["node_counts"][2 * n + 1])
+            if k < 0:
+                out.append(-1)
+                continue
+            c = int(self.conf_off[n])
+            nc = min(max(oc, 0), max(int(self.conf_off[n + 1]) - c, 0)) if c >= 0 else 0
+            out.append((k, oc, r["conf"][2 * c: 2 * (c + nc)].reshape(nc, 2)))
+        return out
+
+
 class DeviceCandidates(_DeviceMany):
     """Device-resident inputs, outputs and workspace for repeated smx_screen_candidates calls
     on a LogsSoA (tests, tools/cand_probe.py).  The optional arguments reach the corners of

@@ -107,6 +107,17 @@ def tree_levels(parents):
     return order, level_off, back
 
 
+def tree_room(parents, ren) -> np.ndarray:
+    """smx_screen_tree's room rule for a tree in level order (a parent lies before its children;
+    any other parent counts as none): per node, with ren[n] the renames of its log, P(n) -- the
+    sum of ren over its root path -- if ren[n] > 0, else 0 (int64 [n_nodes])."""
+    par, ren = np.asarray(parents, np.int64).tolist(), np.asarray(ren, np.int64).tolist()
+    psum = [0] * len(par)
+    for n, p in enumerate(par):
+        psum[n] = (psum[p] if 0 <= p < n else 0) + ren[n]
+    return np.asarray([s if r > 0 else 0 for s, r in zip(psum, ren)], np.int64)
+
+
 def run_train_loop(st: int, base, state, log_off, train, rec_off, ws, status_host, hook=None, n_acc: int = 0):
     """One train of any size as a host loop over device-resident columns (include/smx.h
     smx_train_step): per step smx_train_stage, smx_compose on the staged columns with
@@ -1036,6 +1047,74 @@ class ComposeSession:
                           in_bytes=lay["in_bytes"], out_bytes=lay["out_bytes"])
         return res
 
+    # -- the screen of trains that share prefixes (smx_screen_tree): every node screened once -----
+
+    def screen_tree(self, lsoa, parents, node_log):
+        """Per node of a tree over a LogsSoA what smx_screen_tree leaves, in the caller's order:
+        (renames, outcome, pairs) -- the renames in the accumulator after the node, its conflicts
+        (0: it landed) and its conflict records as an (n, 2) int32 array of (A column index, B
+        column index).  parents[n]: the node's parent (None or -1: a root; a parent precedes its
+        children, tree_levels), node_log[n]: its log.  Per node they are smx_screen_train's last
+        step on the node's root path, whatever the sizes: no node is sent back.  One
+        host-to-device copy of the six columns (33 bytes per op, each log once), one
+        smx_screen_tree, one copy back, one stream sync, whatever the tree.  Invalid input raises
+        SmxError naming the node.  The results are copies.  `last` holds the call's legs,
+        "in_bytes" and "out_bytes"."""
+        t0 = time.perf_counter()
+        order, level_off, back = tree_levels(parents)
+        N, D, L, tot = len(order), len(level_off) - 1, lsoa.n_logs, int(lsoa.n_total)
+        self.last = _last(("in_bytes", "out_bytes"))
+        if N == 0:
+            return []
+        if D > _abi.TREE_MAX_LEVELS:
+            raise SmxError(-1, f"a tree of {D} levels: over SMX_TREE_MAX_LEVELS ({_abi.TREE_MAX_LEVELS})")
+        logs = np.asarray(node_log, np.int32).reshape(N)
+        if int(logs.min()) < 0 or int(logs.max()) >= L:
+            raise SmxError(-1, f"node {int(np.flatnonzero((logs < 0) | (logs >= L))[0])}: a log index outside [0, {L})")
+        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
+        if int(log_off[0]) < 0 or (log_off[1:] < log_off[:-1]).any() or int(log_off[-1]) > tot:
+            raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
+        par = np.asarray([-1 if p is None else int(p) for p in parents], np.int64)
+        # (level order: the stored parent is the caller's parent's place)
+        lv_par = np.where(par[order] >= 0, back[np.maximum(par[order], 0)], -1).astype(np.int32)
+        lv_log = np.ascontiguousarray(logs[order])
+        lv_ren = _rename_counts(lsoa.kind, log_off)[lv_log].astype(np.int64)
+        acc_off = np.concatenate([[0], np.cumsum(tree_room(lv_par, lv_ren), dtype=np.int64)])
+        conf_off = np.concatenate([[0], np.cumsum(lv_ren, dtype=np.int64)])  # (at most one conflict per rename of B)
+        n_acc, n_conf = int(acc_off[-1]), int(conf_off[-1])
+        if n_acc > 0x7fffffff:
+            raise SmxError(-1, f"the nodes' accumulators need {n_acc} rename records: over 2^31 - 1")
+        lay = self._layout(tot, [(name, tot * dt.itemsize) for name, dt, _ in SCREEN_COLS]
+                           + [("log_off", (L + 1) * 8), ("level_off", (D + 1) * 8), ("node_parent", N * 4),
+                              ("node_log", N * 4), ("acc_off", (N + 1) * 8), ("conf_off", (N + 1) * 8)],
+                           0, 8 * n_conf, 16 * N)
+        t1, t2 = self._staged_call(
+            self.main, lib().smx_screen_tree_workspace_bytes, (L, tot, N, D, n_acc, 0), lay,
+            [(getattr(lsoa, name), lay[name], tot * dt.itemsize) for name, dt, _ in SCREEN_COLS],
+            (("log_off", log_off), ("level_off", level_off), ("node_parent", lv_par), ("node_log", lv_log),
+             ("acc_off", acc_off), ("conf_off", conf_off)),
+            lambda d0, o0: _abi.SmxScreenTree(L, tot, N, D, n_acc, d0 + lay["log_off"],
+                                              *[d0 + lay[name] for name, _, _ in SCREEN_COLS],
+                                              d0 + lay["level_off"], d0 + lay["node_parent"], d0 + lay["node_log"],
+                                              d0 + lay["acc_off"], o0 + lay["conf"], d0 + lay["conf_off"],
+                                              o0 + lay["counts"], 0),
+            lambda arg, ws, nbytes, st: lib().smx_screen_tree(arg, ws, nbytes, 0, st))
+        hout = self.main.hout
+        counts = hout[lay["counts"]: lay["counts"] + 16 * N].view(np.int64).tolist()
+        conf = hout[lay["conf"]: lay["conf"] + 8 * n_conf].view(np.int32).reshape(-1, 2)
+        res = [None] * N
+        for i in range(N):
+            n, k, oc = int(order[i]), counts[2 * i], counts[2 * i + 1]
+            if k < 0:
+                raise SmxError(-1, f"node {n}: invalid input")
+            if oc < 0:
+                raise SmxError(-1, f"node {n}: invalid input: kind >= 18")
+            c = int(conf_off[i])
+            res[n] = (k, oc, conf[c: c + oc].copy())
+        self.last = _last(pack_s=t1 - t0, device_s=t2 - t1, unpack_s=time.perf_counter() - t2,
+                          in_bytes=lay["in_bytes"], out_bytes=lay["out_bytes"])
+        return res
+
     # -- candidate pairs (smx_screen_candidates) and the screen of all of them ----------------
 
     @staticmethod
@@ -1232,3 +1311,8 @@ def screen_all_soa(lsoa, device: str = "cuda", large: bool = False):
 def screen_trains_soa(lsoa, trains, device: str = "cuda"):
     """ComposeSession.screen_trains on the thread's free session: the trains' steps screened in one call."""
     return _free_session(device).screen_trains(lsoa, trains)
+
+
+def screen_tree_soa(lsoa, parents, node_log, device: str = "cuda"):
+    """ComposeSession.screen_tree on the thread's free session: a tree's nodes screened in one call."""
+    return _free_session(device).screen_tree(lsoa, parents, node_log)

@@ -307,6 +307,44 @@ def screen_train(logs: Sequence[Sequence[Any]], trains: Optional[Sequence[Sequen
             for _, _, steps in found]
 
 
+def screen_tree(logs: Sequence[Sequence[Any]], nodes: Sequence[Tuple[Optional[int], int]]
+                ) -> List[List[Tuple[Tuple[int, int], Tuple[int, int]]]]:
+    """Which nodes of a tree of merge trains lose their log, and over which ops, without
+    composing anything: per node of ``compose_tree(logs, nodes)`` the conflicts of that node as
+    ``((log_a, index_a), (log_b, index_b))`` -- the positions in ``logs`` of the two ops of every
+    conflict, in the reference's order; an empty list means the node landed.  ``nodes``: per node
+    ``(parent, log)`` -- the index of an earlier node or ``None`` for a root, and a log index; per
+    node the answer is ``screen_train``'s for the last step of the node's root path.  It comes
+    from the logs' renames alone (one copy in, one smx_screen_tree, one copy back, one sync): every
+    log's renames are sorted once and every node is walked once, whatever the number of paths
+    through it, and trees of any size are served in the one call: no size is refused, nothing is
+    materialised and no host loop stands behind it.  ``opA`` of the reference's ``Conflict`` is
+    the accumulated clone, which comes from ``compose_tree``; this call names the ops only.  A
+    parent that does not precede its node raises ``ValueError``, an index outside the nodes or
+    the logs ``IndexError``.  Inputs are never mutated."""
+    from ._session import tree_levels
+    ops = [list(x) for x in logs]
+    nodes = [(None if p is None else int(p), int(l)) for p, l in nodes]
+    parents = [p for p, _ in nodes]
+    tree_levels(parents)  # (the parents' checks)
+    for n, (_, l) in enumerate(nodes):
+        if not 0 <= l < len(ops):
+            raise IndexError(f"node {n}: log {l} outside the {len(ops)} logs")
+    if not nodes:
+        return []
+    with dropin_session() as sess:
+        # marshalled straight into the session's pinned staging columns
+        lsoa = marshal_logs(ops, sess.staging_logs(sum(len(x) for x in ops), len(ops), 0))
+        found = sess.screen_tree(lsoa, parents, [l for _, l in nodes])
+    off = np.asarray(lsoa.log_off, np.int64)
+
+    def where(cols):
+        log = np.searchsorted(off, cols, "right") - 1
+        return list(zip(log.tolist(), (cols - off[log]).tolist()))
+
+    return [list(zip(where(recs[:, 0].astype(np.int64)), where(recs[:, 1].astype(np.int64)))) for _, _, recs in found]
+
+
 def screen_conflicts(logs: Sequence[Sequence[Any]],
                      pairs: Optional[Sequence[Tuple[int, int]]] = None, large: bool = False) -> List[List[Any]]:
     """``[compose_oplogs(logs[i], logs[j])[1] for i, j in pairs]`` -- the DivergentRename

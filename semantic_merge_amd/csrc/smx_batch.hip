@@ -8,7 +8,8 @@
 // step of a train of any size, a launch each and no workspace), and
 // smx_screen_train (kernels in smx_screen_train.h), the screen's over trains, and
 // smx_compose_tree (kernels in smx_tree.h), the class launch once per level of a
-// tree of logs.
+// tree of logs, and smx_screen_tree (kernels in smx_screen_tree.h), the screen's
+// over such a tree.
 //
 // All three have one shape: a pre-pass sorts the items (merges, pairs) into three size
 // classes, then one kernel per class runs its list on a grid capped by what the device
@@ -29,6 +30,7 @@
 #include "smx_train_step.h"
 #include "smx_screen_train.h"
 #include "smx_tree.h"
+#include "smx_screen_tree.h"
 
 // The kernels with a residency-capped grid, and the threads of a workgroup of each.
 enum {
@@ -45,7 +47,8 @@ enum {
   R_TRAIN = 18,
   R_SCREEN_TRAIN = 21,
   R_TREE = 24,
-  R_N = 27
+  R_SCREEN_TREE = 27,
+  R_N = 30
 };
 template <typename B>
 using BatchKernel = void (*)(B, const u32*, const u32*);
@@ -65,6 +68,9 @@ static constexpr ScreenTrainKernel kScreenTrainKernels[SCREEN_CLASSES] = {
 typedef void (*TreeKernel)(smx_tree, TreeWs, i32, const u32*, const u32*);
 static constexpr TreeKernel kTreeKernels[BATCH_CLASSES] = {
     k_compose_tree<batch_class_cap(0)>, k_compose_tree<batch_class_cap(1)>, k_compose_tree<batch_class_cap(2)>};
+typedef void (*ScreenTreeKernel)(ScreenTreeArgs, ScreenWs, ScreenTreeWs, i32, const u32*, const u32*);
+static constexpr ScreenTreeKernel kScreenTreeKernels[SCREEN_CLASSES] = {
+    k_screen_tree<screen_class_cap(0)>, k_screen_tree<screen_class_cap(1)>, k_screen_tree<screen_class_cap(2)>};
 static constexpr int kBatchCaps[BATCH_CLASSES] = {batch_class_cap(0), batch_class_cap(1), batch_class_cap(2)};
 static constexpr int kScreenCaps[SCREEN_CLASSES] = {screen_class_cap(0), screen_class_cap(1), screen_class_cap(2)};
 
@@ -97,7 +103,8 @@ static int resident_of(const int** out) {
     for (int c = 0; c < SCREEN_CLASSES; ++c) {
       fn[R_SCREEN + c] = (const void*)kScreenKernels[c];
       fn[R_SCREEN_TRAIN + c] = (const void*)kScreenTrainKernels[c];
-      threads[R_SCREEN + c] = threads[R_SCREEN_TRAIN + c] = kScreenCaps[c] / 2;
+      fn[R_SCREEN_TREE + c] = (const void*)kScreenTreeKernels[c];
+      threads[R_SCREEN + c] = threads[R_SCREEN_TRAIN + c] = threads[R_SCREEN_TREE + c] = kScreenCaps[c] / 2;
     }
     fn[R_EXTRACT_LARGE] = (const void*)k_screen_extract_large;
     threads[R_EXTRACT_LARGE] = SCREEN_TL;
@@ -599,6 +606,71 @@ extern "C" int smx_screen_train(const struct smx_screen_train* b, void* workspac
     HIP_TRY(hipGetLastError());
     return launch_classes(kScreenTrainKernels, kScreenCaps, resident + R_SCREEN_TRAIN, b->n_trains, b->grid_cap, st,
                           w.cnt, w.lists, w.list_stride, *b, w);
+  } catch (const std::exception& e) {
+    return smx_set_error(SMX_E_HIP, e.what());
+  }
+}
+
+extern "C" int smx_screen_tree_workspace_bytes(int64_t n_logs, int64_t n_total, int64_t n_nodes, int64_t n_levels,
+                                               int64_t n_acc, uint32_t flags, size_t* bytes) {
+  if (flags) return smx_set_error(SMX_E_ARG, "unknown smx_screen_tree flag");
+  if (!bytes) return smx_set_error(SMX_E_ARG, "null bytes");
+  for (int64_t v : {n_logs, n_total, n_nodes, n_acc})
+    if (v < 0 || v > 0x7fffffffll)
+      return smx_set_error(SMX_E_ARG, "n_logs, n_total, n_nodes or n_acc outside 0 .. 2^31 - 1");
+  if (n_levels < 0 || n_levels > TREE_MAX_LEVELS)
+    return smx_set_error(SMX_E_ARG, "n_levels outside 0 .. SMX_TREE_MAX_LEVELS");
+  *bytes = screen_tree_ws_bytes(n_logs, n_total, n_nodes, n_levels, n_acc);
+  return SMX_OK;
+}
+
+// The checks; then the offsets' pre-pass (k_screen_tree_offsets), the screen's two extraction
+// kernels over every log, the nodes' pre-pass (k_screen_tree_prepass) and, level by level, the
+// three classes' k_screen_tree.
+extern "C" int smx_screen_tree(const struct smx_screen_tree* b, void* workspace, size_t workspace_bytes,
+                               uint32_t flags, void* stream) {
+  if (flags) return smx_set_error(SMX_E_ARG, "unknown smx_screen_tree flag");
+  if (!b) return smx_set_error(SMX_E_ARG, "null screen tree struct");
+  if (b->n_logs < 0 || b->n_total < 0 || b->n_nodes < 0 || b->n_levels < 0 || b->n_acc < 0 || b->grid_cap < 0)
+    return smx_set_error(SMX_E_ARG, "negative size");
+  if (b->n_levels > TREE_MAX_LEVELS) return smx_set_error(SMX_E_ARG, "n_levels over SMX_TREE_MAX_LEVELS");
+  if (b->n_logs > 0x7fffffffll || b->n_total > 0x7fffffffll || b->n_nodes > 0x7fffffffll || b->n_acc > 0x7fffffffll)
+    return smx_set_error(SMX_E_ARG, "n_logs, n_total, n_nodes or n_acc over 2^31 - 1");
+  if ((b->conflicts == nullptr) != (b->conf_off == nullptr))
+    return smx_set_error(SMX_E_ARG, "conflicts and conf_off are both null or both set");
+  if (b->n_nodes == 0) return SMX_OK;
+  if (!b->level_off || !b->node_parent || !b->node_log || !b->acc_off || !b->node_counts)
+    return smx_set_error(SMX_E_ARG, "null level_off / node_parent / node_log / acc_off / node_counts");
+  if (b->n_logs > 0 && !b->log_off) return smx_set_error(SMX_E_ARG, "null log_off");
+  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0))
+    return smx_set_error(SMX_E_ARG, "null column");
+  if (!workspace || ((uintptr_t)workspace & 7) ||
+      workspace_bytes < screen_tree_ws_bytes(b->n_logs, b->n_total, b->n_nodes, b->n_levels, b->n_acc))
+    return smx_set_error(SMX_E_WORKSPACE,
+                         "workspace too small or not 8-byte aligned (smx_screen_tree_workspace_bytes)");
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  try {
+    const int* resident;
+    if (int rc = resident_of(&resident)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const ScreenWs w = screen_ws(workspace, b->n_logs, b->n_total + b->n_acc, b->n_nodes);
+    const ScreenTreeWs y = screen_tree_ws(workspace, b->n_logs, b->n_total, b->n_nodes, b->n_levels, b->n_acc);
+    const ScreenArgs s = screen_tree_logs(*b);
+    hipLaunchKernelGGL(k_screen_tree_offsets, dim3(1), dim3(1024), 0, st, *b, w, y);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_extract, capped_grid_min1(resident[R_EXTRACT], b->n_logs, b->grid_cap), dim3(SCREEN_T1),
+                       0, st, s, w);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_extract_large, capped_grid_min1(resident[R_EXTRACT_LARGE], b->n_logs, b->grid_cap),
+                       dim3(SCREEN_TL), 0, st, s, w, y.x);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_screen_tree_prepass, dim3(1), dim3(1024), 0, st, *b, w, y);
+    HIP_TRY(hipGetLastError());
+    for (i32 d = 0; d < (i32)b->n_levels; ++d)
+      if (int rc = launch_classes(kScreenTreeKernels, kScreenCaps, resident + R_SCREEN_TREE, b->n_nodes, b->grid_cap,
+                                  st, y.lcnt + 4 * d, w.lists, w.list_stride, *b, w, y, d))
+        return rc;
+    return SMX_OK;
   } catch (const std::exception& e) {
     return smx_set_error(SMX_E_HIP, e.what());
   }
