@@ -132,6 +132,43 @@ class _DeviceMany:
         a = np.ascontiguousarray(a)
         return self.torch.from_numpy(a.view(dt) if dt is not None else a).to(self.device)
 
+    def _train_index(self, lsoa, trains, log_off, train_off, per_log):
+        """What DeviceTrains and DeviceScreenTrains keep of their trains alike: lsoa, n_logs, trains,
+        n_trains, train_log, n_steps, train_off, log_off, n_total.  Returns (per step per_log's
+        entry of its log, 0 for a log index outside the logs; the default region offsets: those
+        summed per train, one train after another)."""
+        self.lsoa = lsoa
+        L = self.n_logs = lsoa.n_logs
+        self.trains = [[int(l) for l in tr] for tr in trains]
+        R = self.n_trains = len(self.trains)
+        self.train_log = np.asarray([l for tr in self.trains for l in tr], np.int32)
+        S = self.n_steps = len(self.train_log)
+        own_off = np.concatenate([[0], np.cumsum([len(tr) for tr in self.trains], dtype=np.int64)]).astype(np.int64)
+        self.train_off = np.asarray(own_off if train_off is None else train_off, np.int64).reshape(R + 1)
+        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
+        self.n_total = int(lsoa.n_total)
+        ok = (self.train_log >= 0) & (self.train_log < L)
+        per_step = np.where(ok, per_log[np.where(ok, self.train_log, 0)], 0).astype(np.int64) if L \
+            else np.zeros(S, np.int64)
+        csum = np.concatenate([[0], np.cumsum(per_step, dtype=np.int64)])
+        return per_step, np.concatenate([[0], np.cumsum(csum[own_off[1:]] - csum[own_off[:-1]], dtype=np.int64)])
+
+    def _tree_index(self, lsoa, parents, node_log, level_off, log_off, per_log):
+        """What DeviceTree and DeviceScreenTree keep of their tree alike: lsoa, n_logs, parents,
+        n_nodes, node_log, level_off, n_levels, log_off, n_total.  Returns per node per_log's
+        entry of its log, 0 for a log index outside the logs."""
+        self.lsoa = lsoa
+        L = self.n_logs = lsoa.n_logs
+        self.parents = np.asarray(parents, np.int32).reshape(-1)
+        N = self.n_nodes = len(self.parents)
+        self.node_log = np.asarray(node_log, np.int32).reshape(N)
+        self.level_off = np.asarray(level_off, np.int64).reshape(-1)
+        self.n_levels = len(self.level_off) - 1
+        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
+        self.n_total = int(lsoa.n_total)
+        ok = (self.node_log >= 0) & (self.node_log < L)
+        return np.where(ok, per_log[np.where(ok, self.node_log, 0)], 0).astype(np.int64) if L else np.zeros(N, np.int64)
+
     def _upload_cols(self, sources, cols=OP_COLS) -> None:
         """_in: the columns `cols` (rows of OP_COLS) of the sources, one after another, uploaded."""
         self._in = [self._up(np.concatenate([np.ascontiguousarray(getattr(s, name)).astype(dt, copy=False)
@@ -350,24 +387,11 @@ class DeviceTrains(_DeviceMany):
                  v1_alt=None, empty_str: int = -1) -> None:
         self._open(device)
         torch, dev = self.torch, self.device
-        self.lsoa = lsoa
         self._alt = None if v1_alt is None else self._up(np.asarray(v1_alt, np.int32))
-        L = self.n_logs = lsoa.n_logs
-        self.trains = [[int(l) for l in tr] for tr in trains]
-        R = self.n_trains = len(self.trains)
-        self.train_log = np.asarray([l for tr in self.trains for l in tr], np.int32)
-        S = self.n_steps = len(self.train_log)
-        own_off = np.concatenate([[0], np.cumsum([len(tr) for tr in self.trains], dtype=np.int64)]).astype(np.int64)
-        self.train_off = np.asarray(own_off if train_off is None else train_off, np.int64).reshape(R + 1)
-        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
-        tot = self.n_total = int(lsoa.n_total)
-        lens = np.diff(np.asarray(lsoa.log_off, np.int64))
-        ok = (self.train_log >= 0) & (self.train_log < L)
-        self.step_len = np.where(ok, lens[np.where(ok, self.train_log, 0)], 0) if L else np.zeros(S, np.int64)
-        if res_off is None:
-            csum = np.concatenate([[0], np.cumsum(self.step_len, dtype=np.int64)])
-            res_off = np.concatenate([[0], np.cumsum(csum[own_off[1:]] - csum[own_off[:-1]], dtype=np.int64)])
-        self.res_off = np.asarray(res_off, np.int64).reshape(R + 1)
+        self.step_len, own_res = self._train_index(lsoa, trains, log_off, train_off,
+                                                   np.diff(np.asarray(lsoa.log_off, np.int64)))
+        L, R, S, tot = self.n_logs, self.n_trains, self.n_steps, self.n_total
+        self.res_off = np.asarray(own_res if res_off is None else res_off, np.int64).reshape(R + 1)
         self.n_out = max(int(self.res_off.max()), 0) if R else 0
         self.n_sym = int(lsoa.n_sym) if n_sym is None else n_sym
         self._upload_cols([lsoa])
@@ -440,19 +464,10 @@ class DeviceTree(_DeviceMany):
                  fill: Optional[int] = None, v1_alt=None, empty_str: int = -1, share=None) -> None:
         self._open(device)
         torch, dev = self.torch, self.device
-        self.lsoa = lsoa
         self._alt = None if v1_alt is None else self._up(np.asarray(v1_alt, np.int32))
-        L = self.n_logs = lsoa.n_logs
-        self.parents = np.asarray(parents, np.int32).reshape(-1)
-        N = self.n_nodes = len(self.parents)
-        self.node_log = np.asarray(node_log, np.int32).reshape(N)
-        self.level_off = np.asarray(level_off, np.int64).reshape(-1)
-        D = self.n_levels = len(self.level_off) - 1
-        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
-        tot = self.n_total = int(lsoa.n_total)
-        lens = np.diff(np.asarray(lsoa.log_off, np.int64))
-        ok = (self.node_log >= 0) & (self.node_log < L)
-        self.node_len = np.where(ok, lens[np.where(ok, self.node_log, 0)], 0) if L else np.zeros(N, np.int64)
+        self.node_len = self._tree_index(lsoa, parents, node_log, level_off, log_off,
+                                         np.diff(np.asarray(lsoa.log_off, np.int64)))
+        L, N, D, tot = self.n_logs, self.n_nodes, self.n_levels, self.n_total
         if res_off is None:
             psum = np.zeros(N, np.int64)
             for n in range(N):  # (level order: a parent lies before its children)
@@ -696,24 +711,10 @@ class DeviceScreenTrains(_DeviceMany):
                  n_acc: Optional[int] = None, fill: Optional[int] = None) -> None:
         self._open(device)
         torch, dev = self.torch, self.device
-        self.lsoa = lsoa
-        L = self.n_logs = lsoa.n_logs
-        self.trains = [[int(l) for l in tr] for tr in trains]
-        R = self.n_trains = len(self.trains)
-        self.train_log = np.asarray([l for tr in self.trains for l in tr], np.int32)
-        S = self.n_steps = len(self.train_log)
-        own_off = np.concatenate([[0], np.cumsum([len(tr) for tr in self.trains], dtype=np.int64)]).astype(np.int64)
-        self.train_off = np.asarray(own_off if train_off is None else train_off, np.int64).reshape(R + 1)
-        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
-        tot = self.n_total = int(lsoa.n_total)
-        ren = _rename_counts(lsoa.kind, lsoa.log_off)
-        ok = (self.train_log >= 0) & (self.train_log < L)
-        self.step_ren = np.where(ok, ren[np.where(ok, self.train_log, 0)], 0).astype(np.int64) if L \
-            else np.zeros(S, np.int64)
-        if acc_off is None:
-            csum = np.concatenate([[0], np.cumsum(self.step_ren, dtype=np.int64)])
-            acc_off = np.concatenate([[0], np.cumsum(csum[own_off[1:]] - csum[own_off[:-1]], dtype=np.int64)])
-        self.acc_off = np.asarray(acc_off, np.int64).reshape(R + 1)
+        self.step_ren, own_acc = self._train_index(lsoa, trains, log_off, train_off,
+                                                   _rename_counts(lsoa.kind, lsoa.log_off))
+        L, R, S, tot = self.n_logs, self.n_trains, self.n_steps, self.n_total
+        self.acc_off = np.asarray(own_acc if acc_off is None else acc_off, np.int64).reshape(R + 1)
         self.n_acc = max(int(self.acc_off.max()), 0) if R else 0
         self.null_conf = isinstance(conf_caps, str) and conf_caps == "null"
         self._upload_cols([lsoa], SCREEN_COLS)
@@ -785,19 +786,9 @@ class DeviceScreenTree(_DeviceMany):
         from ._session import tree_room
         self._open(device)
         torch, dev = self.torch, self.device
-        self.lsoa = lsoa
-        L = self.n_logs = lsoa.n_logs
-        self.parents = np.asarray(parents, np.int32).reshape(-1)
-        N = self.n_nodes = len(self.parents)
-        self.node_log = np.asarray(node_log, np.int32).reshape(N)
-        self.level_off = np.asarray(level_off, np.int64).reshape(-1)
-        D = self.n_levels = len(self.level_off) - 1
-        self.log_off = np.asarray(lsoa.log_off if log_off is None else log_off, np.int64).reshape(L + 1)
-        tot = self.n_total = int(lsoa.n_total)
-        ren = _rename_counts(lsoa.kind, lsoa.log_off)
-        ok = (self.node_log >= 0) & (self.node_log < L)
-        self.node_ren = np.where(ok, ren[np.where(ok, self.node_log, 0)], 0).astype(np.int64) if L \
-            else np.zeros(N, np.int64)
+        self.node_ren = self._tree_index(lsoa, parents, node_log, level_off, log_off,
+                                         _rename_counts(lsoa.kind, lsoa.log_off))
+        L, N, D, tot = self.n_logs, self.n_nodes, self.n_levels, self.n_total
         if acc_off is None:
             acc_off = np.concatenate([[0], np.cumsum(tree_room(self.parents, self.node_ren), dtype=np.int64)])
         self.acc_off = np.asarray(acc_off, np.int64).reshape(N + 1)

@@ -118,6 +118,48 @@ def tree_room(parents, ren) -> np.ndarray:
     return np.asarray([s if r > 0 else 0 for s, r in zip(psum, ren)], np.int64)
 
 
+def checked_log_off(lsoa) -> np.ndarray:
+    """A LogsSoA's log offsets as contiguous int64, checked: they start at or after 0, do not
+    decrease and end inside the columns; else SmxError."""
+    log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
+    if int(log_off[0]) < 0 or (log_off[1:] < log_off[:-1]).any() or int(log_off[-1]) > int(lsoa.n_total):
+        raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
+    return log_off
+
+
+def train_index(lsoa, trains):
+    """What compose_trains and screen_trains build of `trains` (lists of log indices over a
+    LogsSoA) alike: (train_log, train_off, log_off) -- the trains flattened (int32), their bounds
+    in that (int64 [n_trains + 1]) and the checked log offsets.  A log index outside the logs
+    raises SmxError naming the train."""
+    trains = [np.asarray(tr, np.int32).reshape(-1) for tr in trains]
+    L = lsoa.n_logs
+    for r, tr in enumerate(trains):
+        if len(tr) and (int(tr.min()) < 0 or int(tr.max()) >= L):
+            raise SmxError(-1, f"train {r}: a log index outside [0, {L})")
+    train_log = np.ascontiguousarray(np.concatenate(trains)) if trains else np.zeros(0, np.int32)
+    train_off = np.concatenate([[0], np.cumsum([len(tr) for tr in trains], dtype=np.int64)]).astype(np.int64)
+    return train_log, train_off, checked_log_off(lsoa)
+
+
+def tree_index(lsoa, parents, node_log, order, level_off, back):
+    """What compose_tree and screen_tree build of a tree in tree_levels' order alike:
+    (lv_par, lv_log, log_off) -- per stored node its parent's place (int32, -1: a root) and its
+    log (int32), and the checked log offsets.  More levels than SMX_TREE_MAX_LEVELS or a log
+    index outside the logs raises SmxError."""
+    N, D, L = len(order), len(level_off) - 1, lsoa.n_logs
+    if D > _abi.TREE_MAX_LEVELS:
+        raise SmxError(-1, f"a tree of {D} levels: over SMX_TREE_MAX_LEVELS ({_abi.TREE_MAX_LEVELS})")
+    logs = np.asarray(node_log, np.int32).reshape(N)
+    if int(logs.min()) < 0 or int(logs.max()) >= L:
+        raise SmxError(-1, f"node {int(np.flatnonzero((logs < 0) | (logs >= L))[0])}: a log index outside [0, {L})")
+    log_off = checked_log_off(lsoa)
+    par = np.asarray([-1 if p is None else int(p) for p in parents], np.int64)
+    # (level order: the stored parent is the caller's parent's place)
+    lv_par = np.where(par[order] >= 0, back[np.maximum(par[order], 0)], -1).astype(np.int32)
+    return lv_par, np.ascontiguousarray(logs[order]), log_off
+
+
 def run_train_loop(st: int, base, state, log_off, train, rec_off, ws, status_host, hook=None, n_acc: int = 0):
     """One train of any size as a host loop over device-resident columns (include/smx.h
     smx_train_step): per step smx_train_stage, smx_compose on the staged columns with
@@ -631,10 +673,8 @@ class ComposeSession:
         bad = np.flatnonzero(((pairs < 0) | (pairs >= L)).any(axis=1))
         if len(bad):
             raise SmxError(-1, f"pair {int(bad[0])}: a log index outside [0, {L})")
-        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
+        log_off = checked_log_off(lsoa)
         lens = log_off[1:] - log_off[:-1]
-        if int(log_off[0]) < 0 or (lens < 0).any() or int(log_off[-1]) > tot:
-            raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
         if tot:  # (the batch has one bound for all its symbols; entries that no log covers are no pair's)
             over = np.flatnonzero(np.asarray(lsoa.sym) >= lsoa.n_sym)
             held = np.zeros(L, bool)
@@ -694,22 +734,14 @@ class ComposeSession:
         train.  v1_alt, empty_str: smx_train's two (marshal.move_file_alt).  The results are
         copies.  `last` holds the call's legs and "in_bytes"."""
         t0 = time.perf_counter()
-        trains = [np.asarray(tr, np.int32).reshape(-1) for tr in trains]
         R, L, tot = len(trains), lsoa.n_logs, int(lsoa.n_total)
         self.last = _last(("in_bytes",))
         if R == 0:
             return []
-        train_log = np.ascontiguousarray(np.concatenate(trains)) if R else np.zeros(0, np.int32)
+        train_log, train_off, log_off = train_index(lsoa, trains)
         S = len(train_log)
-        for r, tr in enumerate(trains):
-            if len(tr) and (int(tr.min()) < 0 or int(tr.max()) >= L):
-                raise SmxError(-1, f"train {r}: a log index outside [0, {L})")
-        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
         lens = log_off[1:] - log_off[:-1]
-        if int(log_off[0]) < 0 or (lens < 0).any() or int(log_off[-1]) > tot:
-            raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
         step_len = lens[train_log] if S else np.zeros(0, np.int64)
-        train_off = np.concatenate([[0], np.cumsum([len(tr) for tr in trains], dtype=np.int64)]).astype(np.int64)
         csum = np.concatenate([[0], np.cumsum(step_len, dtype=np.int64)])
         res_off = np.concatenate([[0], np.cumsum(csum[train_off[1:]] - csum[train_off[:-1]], dtype=np.int64)])
         conf_off = csum.astype(np.int64)  # (a step has at most as many conflicts as its log has ops)
@@ -773,20 +805,8 @@ class ComposeSession:
         self.last = _last(("in_bytes",))
         if N == 0:
             return []
-        if D > _abi.TREE_MAX_LEVELS:
-            raise SmxError(-1, f"a tree of {D} levels: over SMX_TREE_MAX_LEVELS ({_abi.TREE_MAX_LEVELS})")
-        logs = np.asarray(node_log, np.int32).reshape(N)
-        if int(logs.min()) < 0 or int(logs.max()) >= L:
-            raise SmxError(-1, f"node {int(np.flatnonzero((logs < 0) | (logs >= L))[0])}: a log index outside [0, {L})")
-        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
-        lens = log_off[1:] - log_off[:-1]
-        if int(log_off[0]) < 0 or (lens < 0).any() or int(log_off[-1]) > tot:
-            raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
-        par = np.asarray([-1 if p is None else int(p) for p in parents], np.int64)
-        # (level order: the stored parent is the caller's parent's place)
-        lv_par = np.where(par[order] >= 0, back[np.maximum(par[order], 0)], -1).astype(np.int32)
-        lv_log = np.ascontiguousarray(logs[order])
-        lv_len = lens[lv_log]
+        lv_par, lv_log, log_off = tree_index(lsoa, parents, node_log, order, level_off, back)
+        lv_len = (log_off[1:] - log_off[:-1])[lv_log]
         psum = np.zeros(N, np.int64)
         for d in range(D):  # (a level's path sums from the level before)
             a, b = int(level_off[d]), int(level_off[d + 1])
@@ -850,10 +870,8 @@ class ComposeSession:
         L, tot, S = lsoa.n_logs, int(lsoa.n_total), len(train)
         if any(not 0 <= l < L for l in train):
             raise SmxError(-1, f"a log index outside [0, {L})")
-        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
+        log_off = checked_log_off(lsoa)
         lens = log_off[1:] - log_off[:-1]
-        if int(log_off[0]) < 0 or (lens < 0).any() or int(log_off[-1]) > tot:
-            raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
         rec_off = np.concatenate([[0], np.cumsum(lens[train] if S else [], dtype=np.int64)]).astype(np.int64)
         cap = int(rec_off[-1])  # (the accumulator holds at most every op of the train's steps)
         alt = np.zeros(tot, np.int32) if v1_alt is None else np.ascontiguousarray(v1_alt, dtype=np.int32)
@@ -993,22 +1011,14 @@ class ComposeSession:
         smx_screen_train, one copy back, one stream sync.  Invalid input raises SmxError naming
         the train.  The results are copies.  `last` holds the call's legs, "in_bytes" and "out_bytes"."""
         t0 = time.perf_counter()
-        trains = [np.asarray(tr, np.int32).reshape(-1) for tr in trains]
         R, L, tot = len(trains), lsoa.n_logs, int(lsoa.n_total)
         self.last = _last(("in_bytes", "out_bytes"))
         if R == 0:
             return []
-        train_log = np.ascontiguousarray(np.concatenate(trains))
+        train_log, train_off, log_off = train_index(lsoa, trains)
         S = len(train_log)
-        for r, tr in enumerate(trains):
-            if len(tr) and (int(tr.min()) < 0 or int(tr.max()) >= L):
-                raise SmxError(-1, f"train {r}: a log index outside [0, {L})")
-        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
-        if int(log_off[0]) < 0 or (log_off[1:] < log_off[:-1]).any() or int(log_off[-1]) > tot:
-            raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
         ren = _rename_counts(lsoa.kind, log_off)
         step_ren = ren[train_log] if S else np.zeros(0, np.int64)
-        train_off = np.concatenate([[0], np.cumsum([len(tr) for tr in trains], dtype=np.int64)]).astype(np.int64)
         conf_off = np.concatenate([[0], np.cumsum(step_ren, dtype=np.int64)])  # (at most one conflict per rename of B)
         acc_off = np.concatenate([[0], np.cumsum(conf_off[train_off[1:]] - conf_off[train_off[:-1]], dtype=np.int64)])
         n_acc, n_conf = int(acc_off[-1]), int(conf_off[-1])
@@ -1066,18 +1076,7 @@ class ComposeSession:
         self.last = _last(("in_bytes", "out_bytes"))
         if N == 0:
             return []
-        if D > _abi.TREE_MAX_LEVELS:
-            raise SmxError(-1, f"a tree of {D} levels: over SMX_TREE_MAX_LEVELS ({_abi.TREE_MAX_LEVELS})")
-        logs = np.asarray(node_log, np.int32).reshape(N)
-        if int(logs.min()) < 0 or int(logs.max()) >= L:
-            raise SmxError(-1, f"node {int(np.flatnonzero((logs < 0) | (logs >= L))[0])}: a log index outside [0, {L})")
-        log_off = np.ascontiguousarray(lsoa.log_off, dtype=np.int64)
-        if int(log_off[0]) < 0 or (log_off[1:] < log_off[:-1]).any() or int(log_off[-1]) > tot:
-            raise SmxError(-1, "invalid input: the log offsets leave the columns or decrease")
-        par = np.asarray([-1 if p is None else int(p) for p in parents], np.int64)
-        # (level order: the stored parent is the caller's parent's place)
-        lv_par = np.where(par[order] >= 0, back[np.maximum(par[order], 0)], -1).astype(np.int32)
-        lv_log = np.ascontiguousarray(logs[order])
+        lv_par, lv_log, log_off = tree_index(lsoa, parents, node_log, order, level_off, back)
         lv_ren = _rename_counts(lsoa.kind, log_off)[lv_log].astype(np.int64)
         acc_off = np.concatenate([[0], np.cumsum(tree_room(lv_par, lv_ren), dtype=np.int64)])
         conf_off = np.concatenate([[0], np.cumsum(lv_ren, dtype=np.int64)])  # (at most one conflict per rename of B)

@@ -11,13 +11,17 @@
 // tree of logs, and smx_screen_tree (kernels in smx_screen_tree.h), the screen's
 // over such a tree.
 //
-// All three have one shape: a pre-pass sorts the items (merges, pairs) into three size
-// classes, then one kernel per class runs its list on a grid capped by what the device
-// holds at once.  That shape is here once: the residency cache (resident_of) and the
-// per-class launch (launch_classes).  The three compose batches go further: they have one
-// size function, one argument check and one runner (batch_ws_size, batch_check_args, batch_run)
-// over a description of each form (batch_form, batch_prepass).  Nothing here waits, allocates
-// or reads back.
+// All but smx_screen_candidates have one shape: a pre-pass sorts the items (merges, pairs,
+// trains, a level's nodes) into three size classes, then one kernel per class runs its list on a
+// grid capped by what the device holds at once.  That shape is here once: the residency cache
+// (resident_of) and the per-class launch (launch_classes).  The three compose batches go
+// further: they have one size function, one argument check and one runner (batch_ws_size,
+// batch_check_args, batch_run) over a description of each form (batch_form, batch_prepass).  The
+// four entry points over trains and trees share their column, result-array and workspace checks,
+// the screen's extraction over every log and the per-level launch (train_columns_set,
+// train_compose_arrays, train_ws_check, screen_extract_logs, launch_levels); their size and
+// null-pointer checks differ per form in set, order and message, and stay in each entry point.
+// Nothing here waits, allocates or reads back.
 #include <exception>
 
 // (the small kernel's phase stamps belong to the single merge: smx_compose.hip defines the
@@ -361,6 +365,65 @@ extern "C" int smx_compose_pairs(const struct smx_pairs* b, void* workspace, siz
   return batch_run(__func__, b, workspace, workspace_bytes, flags, stream);
 }
 
+// ---- what the four entry points over trains and trees (smx_compose_train, smx_compose_tree,
+// smx_screen_train, smx_screen_tree) share on the host ----
+
+// The six columns every form reads, n_total > 0 of them (the compose forms read v1 too).
+template <typename B>
+static bool train_columns_set(const B* b) {
+  return b->kind && b->ts && b->oid_hi && b->oid_lo && b->sym && b->v0;
+}
+
+// What the two compose forms check of their columns and result arrays alike.
+template <typename B>
+static int train_compose_arrays(const B* b) {
+  if (b->n_total > 0 && !(train_columns_set(b) && b->v1)) return smx_set_error(SMX_E_ARG, "null column");
+  if (b->n_total > 0 && b->empty_str >= 0 && !b->v1_alt) return smx_set_error(SMX_E_ARG, "null v1_alt with empty_str set");
+  if (b->n_out > 0 && (!b->src || !b->addr || !b->file || !b->ctx)) return smx_set_error(SMX_E_ARG, "null result array");
+  return SMX_OK;
+}
+
+// The workspace check, the last one of each; `query` names the entry point's own size query.
+static int train_ws_check(const void* workspace, size_t workspace_bytes, size_t need, const char* query) {
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < need)
+    return smx_set_error(SMX_E_WORKSPACE,
+                         (std::string("workspace too small or not 8-byte aligned (") + query + ")").c_str());
+  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  return SMX_OK;
+}
+
+// min(resident, items) workgroups as capped_grid, and one where there is no item: the per-log
+// launches of a call whose trains name no log.
+static dim3 capped_grid_min1(int resident, i64 items, i64 grid_cap) {
+  return capped_grid(resident, items > 0 ? items : 1, grid_cap);
+}
+
+// The screen's two extraction kernels over every log of a screen of trains or of a tree.
+template <typename B>
+static int screen_extract_logs(const B& b, const int* resident, hipStream_t st, const ScreenWs& w,
+                               const ScreenLargeWs& x) {
+  const ScreenArgs s = screen_step_logs(b);
+  hipLaunchKernelGGL(k_screen_extract, capped_grid_min1(resident[R_EXTRACT], b.n_logs, b.grid_cap), dim3(SCREEN_T1), 0,
+                     st, s, w);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_screen_extract_large, capped_grid_min1(resident[R_EXTRACT_LARGE], b.n_logs, b.grid_cap),
+                     dim3(SCREEN_TL), 0, st, s, w, x);
+  HIP_TRY(hipGetLastError());
+  return SMX_OK;
+}
+
+// The class launch once per level of a tree: level d's counts are lcnt + 4 * d, and the kernels
+// take d after their own arguments.
+template <typename K, typename... A>
+static int launch_levels(K* const (&kern)[3], const int (&cap)[3], const int* resident, i64 n_levels, i64 items,
+                         i64 grid_cap, hipStream_t st, const u32* lcnt, const u32* lists, size_t stride,
+                         const A&... args) {
+  for (i32 d = 0; d < (i32)n_levels; ++d)
+    if (int rc = launch_classes(kern, cap, resident, items, grid_cap, st, lcnt + 4 * d, lists, stride, args..., d))
+      return rc;
+  return SMX_OK;
+}
+
 extern "C" int smx_compose_train_workspace_bytes(int64_t n_logs, int64_t n_trains, int64_t n_steps, int64_t n_out,
                                                  uint32_t flags, size_t* bytes) {
   if (flags) return smx_set_error(SMX_E_ARG, "unknown smx_compose_train flag");
@@ -391,14 +454,10 @@ extern "C" int smx_compose_train(const struct smx_train* b, void* workspace, siz
   if (b->n_logs > 0 && !b->log_off) return smx_set_error(SMX_E_ARG, "null log_off");
   if (b->n_steps > 0 && (!b->train_log || !b->conf_off || !b->step_counts || !b->conflicts))
     return smx_set_error(SMX_E_ARG, "null train_log / conf_off / step_counts / conflicts");
-  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1))
-    return smx_set_error(SMX_E_ARG, "null column");
-  if (b->n_total > 0 && b->empty_str >= 0 && !b->v1_alt) return smx_set_error(SMX_E_ARG, "null v1_alt with empty_str set");
-  if (b->n_out > 0 && (!b->src || !b->addr || !b->file || !b->ctx)) return smx_set_error(SMX_E_ARG, "null result array");
-  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < train_ws_bytes(b->n_logs, b->n_trains, b->n_out))
-    return smx_set_error(SMX_E_WORKSPACE,
-                         "workspace too small or not 8-byte aligned (smx_compose_train_workspace_bytes)");
-  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  if (int rc = train_compose_arrays(b)) return rc;
+  if (int rc = train_ws_check(workspace, workspace_bytes, train_ws_bytes(b->n_logs, b->n_trains, b->n_out),
+                              "smx_compose_train_workspace_bytes"))
+    return rc;
   try {
     const int* resident;
     if (int rc = resident_of(&resident)) return rc;
@@ -448,15 +507,10 @@ extern "C" int smx_compose_tree(const struct smx_tree* b, void* workspace, size_
     return smx_set_error(SMX_E_ARG,
                          "null level_off / node_parent / node_log / res_off / conf_off / conflicts / node_counts / node_acc");
   if (b->n_logs > 0 && !b->log_off) return smx_set_error(SMX_E_ARG, "null log_off");
-  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0 || !b->v1))
-    return smx_set_error(SMX_E_ARG, "null column");
-  if (b->n_total > 0 && b->empty_str >= 0 && !b->v1_alt) return smx_set_error(SMX_E_ARG, "null v1_alt with empty_str set");
-  if (b->n_out > 0 && (!b->src || !b->addr || !b->file || !b->ctx)) return smx_set_error(SMX_E_ARG, "null result array");
-  if (!workspace || ((uintptr_t)workspace & 7) ||
-      workspace_bytes < tree_ws_bytes(b->n_logs, b->n_nodes, b->n_levels, b->n_out))
-    return smx_set_error(SMX_E_WORKSPACE,
-                         "workspace too small or not 8-byte aligned (smx_compose_tree_workspace_bytes)");
-  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  if (int rc = train_compose_arrays(b)) return rc;
+  if (int rc = train_ws_check(workspace, workspace_bytes, tree_ws_bytes(b->n_logs, b->n_nodes, b->n_levels, b->n_out),
+                              "smx_compose_tree_workspace_bytes"))
+    return rc;
   try {
     const int* resident;
     if (int rc = resident_of(&resident)) return rc;
@@ -464,11 +518,8 @@ extern "C" int smx_compose_tree(const struct smx_tree* b, void* workspace, size_
     const TreeWs w = tree_ws(workspace, b->n_logs, b->n_nodes, b->n_levels, b->n_out);
     hipLaunchKernelGGL(k_tree_prepass, dim3(1), dim3(1024), 0, st, *b, w);
     HIP_TRY(hipGetLastError());
-    for (i32 d = 0; d < (i32)b->n_levels; ++d)
-      if (int rc = launch_classes(kTreeKernels, kBatchCaps, resident + R_TREE, b->n_nodes, b->grid_cap, st,
-                                  w.lcnt + 4 * d, w.lists, w.stride, *b, w, d))
-        return rc;
-    return SMX_OK;
+    return launch_levels(kTreeKernels, kBatchCaps, resident + R_TREE, b->n_levels, b->n_nodes, b->grid_cap, st, w.lcnt,
+                         w.lists, w.stride, *b, w);
   } catch (const std::exception& e) {
     return smx_set_error(SMX_E_HIP, e.what());
   }
@@ -555,12 +606,6 @@ extern "C" int smx_screen_train_workspace_bytes(int64_t n_logs, int64_t n_total,
   return SMX_OK;
 }
 
-// min(resident, items) workgroups as capped_grid, and one where there is no item: the per-log
-// launches of a call whose trains name no log.
-static dim3 capped_grid_min1(int resident, i64 items, i64 grid_cap) {
-  return capped_grid(resident, items > 0 ? items : 1, grid_cap);
-}
-
 // The checks; then the pre-pass (k_screen_train_offsets), the screen's two extraction kernels
 // over every log, k_screen_train_classify and the three classes' k_screen_train.
 extern "C" int smx_screen_train(const struct smx_screen_train* b, void* workspace, size_t workspace_bytes,
@@ -579,28 +624,20 @@ extern "C" int smx_screen_train(const struct smx_screen_train* b, void* workspac
   if (b->n_logs > 0 && !b->log_off) return smx_set_error(SMX_E_ARG, "null log_off");
   if (b->n_steps > 0 && (!b->train_log || !b->step_counts))
     return smx_set_error(SMX_E_ARG, "null train_log / step_counts");
-  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0))
-    return smx_set_error(SMX_E_ARG, "null column");
-  if (!workspace || ((uintptr_t)workspace & 7) ||
-      workspace_bytes < screen_train_ws_bytes(b->n_logs, b->n_total, b->n_trains, b->n_acc))
-    return smx_set_error(SMX_E_WORKSPACE,
-                         "workspace too small or not 8-byte aligned (smx_screen_train_workspace_bytes)");
-  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  if (b->n_total > 0 && !train_columns_set(b)) return smx_set_error(SMX_E_ARG, "null column");
+  if (int rc = train_ws_check(workspace, workspace_bytes,
+                              screen_train_ws_bytes(b->n_logs, b->n_total, b->n_trains, b->n_acc),
+                              "smx_screen_train_workspace_bytes"))
+    return rc;
   try {
     const int* resident;
     if (int rc = resident_of(&resident)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const ScreenWs w = screen_ws(workspace, b->n_logs, screen_train_records(b->n_total, b->n_acc), b->n_trains);
     const ScreenTrainWs y = screen_train_ws(workspace, b->n_logs, b->n_total, b->n_trains, b->n_acc);
-    const ScreenArgs s = screen_train_logs(*b);
     hipLaunchKernelGGL(k_screen_train_offsets, dim3(1), dim3(1024), 0, st, *b, w, y);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_screen_extract, capped_grid_min1(resident[R_EXTRACT], b->n_logs, b->grid_cap), dim3(SCREEN_T1),
-                       0, st, s, w);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_screen_extract_large, capped_grid_min1(resident[R_EXTRACT_LARGE], b->n_logs, b->grid_cap),
-                       dim3(SCREEN_TL), 0, st, s, w, y.x);
-    HIP_TRY(hipGetLastError());
+    if (int rc = screen_extract_logs(*b, resident, st, w, y.x)) return rc;
     hipLaunchKernelGGL(k_screen_train_classify, dim3((unsigned)SMX_CEIL_DIV(b->n_trains, (i64)256)), dim3(256), 0, st,
                        *b, w, y);
     HIP_TRY(hipGetLastError());
@@ -642,35 +679,24 @@ extern "C" int smx_screen_tree(const struct smx_screen_tree* b, void* workspace,
   if (!b->level_off || !b->node_parent || !b->node_log || !b->acc_off || !b->node_counts)
     return smx_set_error(SMX_E_ARG, "null level_off / node_parent / node_log / acc_off / node_counts");
   if (b->n_logs > 0 && !b->log_off) return smx_set_error(SMX_E_ARG, "null log_off");
-  if (b->n_total > 0 && (!b->kind || !b->ts || !b->oid_hi || !b->oid_lo || !b->sym || !b->v0))
-    return smx_set_error(SMX_E_ARG, "null column");
-  if (!workspace || ((uintptr_t)workspace & 7) ||
-      workspace_bytes < screen_tree_ws_bytes(b->n_logs, b->n_total, b->n_nodes, b->n_levels, b->n_acc))
-    return smx_set_error(SMX_E_WORKSPACE,
-                         "workspace too small or not 8-byte aligned (smx_screen_tree_workspace_bytes)");
-  (void)hipGetLastError();  // an earlier call's error (any library's) is not this call's
+  if (b->n_total > 0 && !train_columns_set(b)) return smx_set_error(SMX_E_ARG, "null column");
+  if (int rc = train_ws_check(workspace, workspace_bytes,
+                              screen_tree_ws_bytes(b->n_logs, b->n_total, b->n_nodes, b->n_levels, b->n_acc),
+                              "smx_screen_tree_workspace_bytes"))
+    return rc;
   try {
     const int* resident;
     if (int rc = resident_of(&resident)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const ScreenWs w = screen_ws(workspace, b->n_logs, b->n_total + b->n_acc, b->n_nodes);
     const ScreenTreeWs y = screen_tree_ws(workspace, b->n_logs, b->n_total, b->n_nodes, b->n_levels, b->n_acc);
-    const ScreenArgs s = screen_tree_logs(*b);
     hipLaunchKernelGGL(k_screen_tree_offsets, dim3(1), dim3(1024), 0, st, *b, w, y);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_screen_extract, capped_grid_min1(resident[R_EXTRACT], b->n_logs, b->grid_cap), dim3(SCREEN_T1),
-                       0, st, s, w);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_screen_extract_large, capped_grid_min1(resident[R_EXTRACT_LARGE], b->n_logs, b->grid_cap),
-                       dim3(SCREEN_TL), 0, st, s, w, y.x);
-    HIP_TRY(hipGetLastError());
+    if (int rc = screen_extract_logs(*b, resident, st, w, y.x)) return rc;
     hipLaunchKernelGGL(k_screen_tree_prepass, dim3(1), dim3(1024), 0, st, *b, w, y);
     HIP_TRY(hipGetLastError());
-    for (i32 d = 0; d < (i32)b->n_levels; ++d)
-      if (int rc = launch_classes(kScreenTreeKernels, kScreenCaps, resident + R_SCREEN_TREE, b->n_nodes, b->grid_cap,
-                                  st, y.lcnt + 4 * d, w.lists, w.list_stride, *b, w, y, d))
-        return rc;
-    return SMX_OK;
+    return launch_levels(kScreenTreeKernels, kScreenCaps, resident + R_SCREEN_TREE, b->n_levels, b->n_nodes, b->grid_cap,
+                         st, y.lcnt, w.lists, w.list_stride, *b, w, y);
   } catch (const std::exception& e) {
     return smx_set_error(SMX_E_HIP, e.what());
   }

@@ -484,6 +484,7 @@ __device__ __forceinline__ void screen_pair_round(const ScreenArgs& s, const Scr
     while (lo_i < hi_i) {  // A: B keys strictly below; B: A keys at or below (A first on ties)
       const int mid = (lo_i + hi_i) >> 1;
       const u64 mt = kts[mid], mh = khi[mid], ml = klo[mid];
+      // (the tie-break, A first on equal keys, is screen_step_merge's too: smx_screen_train.h)
       const bool below = mt != ts ? mt < ts : mh != hi ? mh < hi : sa ? ml < lo : ml <= lo;
       if (below) lo_i = mid + 1;
       else hi_i = mid;

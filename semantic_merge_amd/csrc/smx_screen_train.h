@@ -25,6 +25,10 @@
 //   k_screen_train<N>        a residency-capped grid; workgroup b runs trains b, b + grid, ... of
 //                            the class list, a train's steps one after another
 // Seven launches, nothing waited for, allocated or read back.  The entry point is in smx_batch.hip.
+//
+// The step is stated here once, as screen_step_walk and screen_step_merge: k_screen_tree
+// (smx_screen_tree.h) runs the same two on a node, and screen_step_logs serves both entry points
+// (DESIGN.md §27).
 #pragma once
 
 #include "smx_screen.h"
@@ -57,8 +61,10 @@ static inline ScreenTrainWs screen_train_ws(void* workspace, int64_t n_logs, int
   return y;
 }
 
-// What the extraction kernels read of a screen: the logs and their columns.
-static inline ScreenArgs screen_train_logs(const ScreenTrainArgs& b) {
+// What the extraction kernels read of a screen over trains or over a tree (B: ScreenTrainArgs,
+// ScreenTreeArgs): the logs and their columns.
+template <typename B>
+static inline ScreenArgs screen_step_logs(const B& b) {
   ScreenArgs s = {};
   s.n_logs = b.n_logs, s.n_total = b.n_total, s.log_off = b.log_off;
   s.kind = b.kind, s.ts = b.ts, s.oid_hi = b.oid_hi, s.oid_lo = b.oid_lo, s.sym = b.sym, s.v0 = b.v0;
@@ -109,13 +115,84 @@ __global__ void __launch_bounds__(256) k_screen_train_classify(ScreenTrainArgs b
   if (cls >= 0) w.lists[(size_t)cls * w.list_stride + start[cls] + rk] = (u32)r;
 }
 
-// Trains by N / 2 threads.  A step whose accumulator and log hold at most N renames together is
-// one round of screen_pair_round; any other runs k_screen_stream's rounds of N / 2 records per
-// side from the two heads.  (A train of class N < SCREEN_N never holds more than N.)
+// ---- the step, for k_screen_train<N> and k_screen_tree<N> (smx_screen_tree.h) alike: N / 2
+// threads, B the call's struct ----
+
+// The walk of the accumulator's records [at, at + acc) against the log's [ob, ob + RB), both
+// non-empty: the step as a pair of the screen, its conflict region conf_off[slot]'s (one that
+// conf_off does not describe holds nothing).  At most N renames together are one round of
+// screen_pair_round; any more run k_screen_stream's rounds of N / 2 records per side from the two
+// heads.  Returns the conflicts, uniform, through heads[2].
+template <int N, typename B>
+__device__ __forceinline__ u32 screen_step_walk(const B& b, const ScreenWs& w, i64 slot, i64 at, i64 acc, i64 ob,
+                                                i64 RB, u32* heads) {
+  constexpr i64 CH = N / 2;
+  u32 nc = 0;  // (wave 0's count, as screen_pair_round leaves it)
+  ScreenArgs s = {};
+  if (b.conflicts) {
+    const i64 c0 = train_uniform(b.conf_off[slot]), c1 = train_uniform(b.conf_off[slot + 1]);
+    if (c0 >= 0 && c1 >= c0) s.conflicts = b.conflicts, s.conf_off = b.conf_off;
+  }
+  const i64 rounds = SMX_CEIL_DIV(acc, CH) + SMX_CEIL_DIV(RB, CH);
+  i64 iA = 0, iB = 0;
+  for (i64 k = 0; k < rounds; ++k) {
+    const bool whole = (acc - iA) + (RB - iB) <= (i64)N;
+    const int nA = (int)(whole || acc - iA < CH ? acc - iA : CH);
+    const int nB = (int)(whole || RB - iB < CH ? RB - iB : CH);
+    screen_pair_round<N, true>(s, w, slot, at + iA, ob + iB, nA, nB, ob, nc, heads);
+    __syncthreads();  // the heads; and the next round's load overwrites what this walk reads
+    iA += (i64)__builtin_amdgcn_readfirstlane((int)heads[0]);
+    iB += (i64)__builtin_amdgcn_readfirstlane((int)heads[1]);
+    if (iA >= acc || iB >= RB) break;  // (uniform) a side is used up for good: the step is done
+  }
+  if (threadIdx.x == 0) heads[2] = nc;  // (wave 0 counted)
+  __syncthreads();
+  return (u32)__builtin_amdgcn_readfirstlane((int)heads[2]);
+}
+
+// The stable merge of the accumulator's records [at, at + acc) and the log's [ob, ob + RB) into
+// [dst, dst + acc + RB): a record's place is its index in its own list and its rank in the other
+// one, by the round's comparison (A: B keys strictly below; B: A keys at or below).  With an
+// empty accumulator it is the copy of the log's sorted records, ridx turned into column indices.
+template <int N>
+__device__ __forceinline__ void screen_step_merge(const ScreenWs& w, i64 at, i64 acc, i64 ob, i64 RB, i64 dst) {
+  const i64 n = acc + RB;
+  for (i64 e = threadIdx.x; e < n; e += N / 2) {
+    const bool sa = e < acc;
+    const i64 own = sa ? e : e - acc;
+    const i64 q = (sa ? at : ob) + own, base = sa ? ob : at;
+    const u64 ts = w.rts[q], hi = w.rhi[q], lo = w.rlo[q];
+    i64 lo_i = 0, hi_i = sa ? RB : acc;
+    while (lo_i < hi_i) {
+      const i64 mid = (lo_i + hi_i) >> 1;
+      const u64 mt = w.rts[base + mid];
+      bool below = mt < ts;
+      if (mt == ts) {
+        const u64 mh = w.rhi[base + mid];
+        below = mh < hi;
+        if (mh == hi) {
+          const u64 ml = w.rlo[base + mid];
+          // (A first on equal keys: the tie-break of smx_screen.h's merge of a pair's two lists too)
+          below = sa ? ml < lo : ml <= lo;
+        }
+      }
+      if (below) lo_i = mid + 1;
+      else hi_i = mid;
+    }
+    const i64 d = dst + own + lo_i;
+    w.rts[d] = ts;
+    w.rhi[d] = hi;
+    w.rlo[d] = lo;
+    w.ridx[d] = sa ? w.ridx[q] : (u32)(ob + (i64)w.ridx[q]);  // the op's column index
+    w.rsym[d] = w.rsym[q];
+    w.rv0[d] = w.rv0[q];
+  }
+}
+
+// Trains by N / 2 threads, a train's steps one after another; the accumulator goes to and fro
+// between the train's two buffers.  (A train of class N < SCREEN_N never holds more than N.)
 template <int N>
 __global__ void __launch_bounds__(N / 2) k_screen_train(ScreenTrainArgs b, ScreenWs w, const u32* cnt, const u32* list) {
-  constexpr int NT = N / 2;
-  constexpr i64 CH = N / 2;
   __shared__ u32 heads[3];  // a round's two heads; a step's conflicts
   const int t = threadIdx.x;
   const u32 c = *cnt;
@@ -132,67 +209,13 @@ __global__ void __launch_bounds__(N / 2) k_screen_train(ScreenTrainArgs b, Scree
       if (RB >= 0) {  // (uniform)
         const i64 ob = train_uniform(b.log_off[l]);
         u32 nc = 0;
-        if (acc > 0 && RB > 0) {
-          // the step as a pair of the screen: its conflict region is the step's, and one that
-          // conf_off does not describe holds nothing
-          ScreenArgs s = {};
-          if (b.conflicts) {
-            const i64 c0 = train_uniform(b.conf_off[g]), c1 = train_uniform(b.conf_off[g + 1]);
-            if (c0 >= 0 && c1 >= c0) s.conflicts = b.conflicts, s.conf_off = b.conf_off;
-          }
-          const i64 rounds = SMX_CEIL_DIV(acc, CH) + SMX_CEIL_DIV(RB, CH);
-          i64 iA = 0, iB = 0;
-          for (i64 k = 0; k < rounds; ++k) {
-            const bool whole = (acc - iA) + (RB - iB) <= (i64)N;
-            const int nA = (int)(whole || acc - iA < CH ? acc - iA : CH);
-            const int nB = (int)(whole || RB - iB < CH ? RB - iB : CH);
-            screen_pair_round<N, true>(s, w, g, at + iA, ob + iB, nA, nB, ob, nc, heads);
-            __syncthreads();  // the heads; and the next round's load overwrites what this walk reads
-            iA += (i64)__builtin_amdgcn_readfirstlane((int)heads[0]);
-            iB += (i64)__builtin_amdgcn_readfirstlane((int)heads[1]);
-            if (iA >= acc || iB >= RB) break;  // (uniform) a side is used up for good: the step is done
-          }
-          if (t == 0) heads[2] = nc;  // (wave 0 counted)
-          __syncthreads();
-          nc = (u32)__builtin_amdgcn_readfirstlane((int)heads[2]);
-        }
+        if (acc > 0 && RB > 0) nc = screen_step_walk<N>(b, w, g, at, acc, ob, RB, heads);
         outcome = (i64)nc;
         if (nc == 0) {
           ++landed;
-          if (RB > 0) {
-            // the stable merge into the other buffer: a record's place is its index in its own
-            // list and its rank in the other one, by the round's comparison (A: B keys strictly
-            // below; B: A keys at or below)
+          if (RB > 0) {  // the merge into the other buffer
             const i64 n = acc + RB;
-            for (i64 e = t; e < n; e += NT) {
-              const bool sa = e < acc;
-              const i64 own = sa ? e : e - acc;
-              const i64 q = (sa ? at : ob) + own, base = sa ? ob : at;
-              const u64 ts = w.rts[q], hi = w.rhi[q], lo = w.rlo[q];
-              i64 lo_i = 0, hi_i = sa ? RB : acc;
-              while (lo_i < hi_i) {
-                const i64 mid = (lo_i + hi_i) >> 1;
-                const u64 mt = w.rts[base + mid];
-                bool below = mt < ts;
-                if (mt == ts) {
-                  const u64 mh = w.rhi[base + mid];
-                  below = mh < hi;
-                  if (mh == hi) {
-                    const u64 ml = w.rlo[base + mid];
-                    below = sa ? ml < lo : ml <= lo;
-                  }
-                }
-                if (below) lo_i = mid + 1;
-                else hi_i = mid;
-              }
-              const i64 d = other + own + lo_i;
-              w.rts[d] = ts;
-              w.rhi[d] = hi;
-              w.rlo[d] = lo;
-              w.ridx[d] = sa ? w.ridx[q] : (u32)(ob + (i64)w.ridx[q]);  // the op's column index
-              w.rsym[d] = w.rsym[q];
-              w.rv0[d] = w.rv0[q];
-            }
+            screen_step_merge<N>(w, at, acc, ob, RB, other);
             const i64 sw = at;
             at = other;
             other = sw;

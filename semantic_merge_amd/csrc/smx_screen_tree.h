@@ -74,15 +74,6 @@ static inline ScreenTreeWs screen_tree_ws(void* workspace, int64_t n_logs, int64
   return y;
 }
 
-// What the extraction kernels read of a screen: the logs and their columns.
-static inline ScreenArgs screen_tree_logs(const ScreenTreeArgs& b) {
-  ScreenArgs s = {};
-  s.n_logs = b.n_logs, s.n_total = b.n_total, s.log_off = b.log_off;
-  s.kind = b.kind, s.ts = b.ts, s.oid_hi = b.oid_hi, s.oid_lo = b.oid_lo, s.sym = b.sym, s.v0 = b.v0;
-  s.grid_cap = b.grid_cap;
-  return s;
-}
-
 __global__ void __launch_bounds__(1024) k_screen_tree_offsets(ScreenTreeArgs b, ScreenWs w, ScreenTreeWs y) {
   __shared__ i64 sc[1024 / WAVE + 1];
   if (threadIdx.x < SCREEN_CLASSES) w.cnt[threadIdx.x] = 0;
@@ -92,11 +83,9 @@ __global__ void __launch_bounds__(1024) k_screen_tree_offsets(ScreenTreeArgs b, 
 }
 
 // After the extraction (linfo: -1 or the log's renames): every structural check, before any
-// record of a node is read through an unchecked index.  The level rules are k_tree_prepass's: a
-// level is valid when its level_off entries are (not negative, not below an earlier entry, not
-// decreasing, not past n_nodes), level 0 starts at node 0 and the last level ends at n_nodes.  A
-// node outside every valid level fails, and so does a node whose parent is not in the level
-// before (that level invalid: no node is), whose parent failed, whose acc_off entries are bad,
+// record of a node is read through an unchecked index.  The level rule and the parent rule are
+// k_tree_prepass's (tree_level, tree_parent_ok in smx_tree.h).  A node outside every valid level
+// fails, and so does a node whose parent breaks the parent rule, whose acc_off entries are bad,
 // or whose own log is valid and has renames while its region is below P(n).
 __global__ void __launch_bounds__(1024) k_screen_tree_prepass(ScreenTreeArgs b, ScreenWs w, ScreenTreeWs y) {
   __shared__ u32 c[SCREEN_CLASSES];
@@ -107,25 +96,11 @@ __global__ void __launch_bounds__(1024) k_screen_tree_prepass(ScreenTreeArgs b, 
   for (i64 d = 0; d < b.n_levels; ++d) {
     if (t < SCREEN_CLASSES) c[t] = 0;
     __syncthreads();
-    i64 lo = 0, hi = 0;
-    if (y.vinfo[d] >= 0) {
-      lo = b.level_off[d];
-      hi = b.level_off[d + 1];
-      if ((d == 0 && lo != 0) || (d == b.n_levels - 1 && hi != b.n_nodes)) lo = hi = 0;
-    }
+    i64 lo, hi;
+    tree_level(b.level_off, y.vinfo, d, b.n_levels, b.n_nodes, lo, hi);
     for (i64 n = lo + t; n < hi; n += 1024) {
-      const i64 p = b.node_parent[n];
-      bool good = y.ainfo[n] >= 0;
-      i64 ps = 0;  // (at most 4096 levels of at most 2^31 - 1 renames each: no overflow)
-      if (d == 0) {
-        good = good && p == SMX_NONE;
-      } else {
-        good = good && p >= plo && p < phi;
-        if (good) {
-          ps = y.pinfo[p];
-          good = ps >= 0;
-        }
-      }
+      i64 ps;  // (at most 4096 levels of at most 2^31 - 1 renames each: no overflow)
+      bool good = y.ainfo[n] >= 0 && tree_parent_ok(d, b.node_parent[n], plo, phi, y.pinfo, ps);
       i64 rb = -1;  // the node's own log: -1 invalid, else its renames
       if (good) {
         const i64 l = b.node_log[n];
@@ -157,16 +132,13 @@ __global__ void __launch_bounds__(1024) k_screen_tree_prepass(ScreenTreeArgs b, 
     }
 }
 
-// One level's nodes of one class by N / 2 threads.  k_screen_train's step, restated: the
-// accumulator in is the region of acc_node[parent], node_counts[2 * parent] records long, and the
-// accumulator out the node's own region.  A node whose accumulator and log hold at most N renames
-// together is one round of screen_pair_round; any other runs k_screen_stream's rounds of N / 2
-// records per side from the two heads.  (A node of class N < SCREEN_N never holds more than N.)
+// One level's nodes of one class by N / 2 threads: k_screen_train's step (screen_step_walk,
+// screen_step_merge), with the accumulator in the region of acc_node[parent],
+// node_counts[2 * parent] records long, and the accumulator out the node's own region.  (A node of
+// class N < SCREEN_N never holds more than N.)
 template <int N>
 __global__ void __launch_bounds__(N / 2) k_screen_tree(ScreenTreeArgs b, ScreenWs w, ScreenTreeWs y, i32 level,
                                                        const u32* cnt, const u32* list) {
-  constexpr int NT = N / 2;
-  constexpr i64 CH = N / 2;
   __shared__ u32 heads[3];  // a round's two heads; the node's conflicts
   const int t = threadIdx.x;
   const u32 c = *cnt;
@@ -191,68 +163,11 @@ __global__ void __launch_bounds__(N / 2) k_screen_tree(ScreenTreeArgs b, ScreenW
     if (RB >= 0) {  // (uniform)
       const i64 ob = train_uniform(b.log_off[l]);
       u32 nc = 0;
-      if (acc > 0 && RB > 0) {
-        // the node as a pair of the screen: its conflict region is the node's, and one that
-        // conf_off does not describe holds nothing
-        ScreenArgs s = {};
-        if (b.conflicts) {
-          const i64 c0 = train_uniform(b.conf_off[n]), c1 = train_uniform(b.conf_off[n + 1]);
-          if (c0 >= 0 && c1 >= c0) s.conflicts = b.conflicts, s.conf_off = b.conf_off;
-        }
-        const i64 rounds = SMX_CEIL_DIV(acc, CH) + SMX_CEIL_DIV(RB, CH);
-        i64 iA = 0, iB = 0;
-        for (i64 k = 0; k < rounds; ++k) {
-          const bool whole = (acc - iA) + (RB - iB) <= (i64)N;
-          const int nA = (int)(whole || acc - iA < CH ? acc - iA : CH);
-          const int nB = (int)(whole || RB - iB < CH ? RB - iB : CH);
-          screen_pair_round<N, true>(s, w, n, at + iA, ob + iB, nA, nB, ob, nc, heads);
-          __syncthreads();  // the heads; and the next round's load overwrites what this walk reads
-          iA += (i64)__builtin_amdgcn_readfirstlane((int)heads[0]);
-          iB += (i64)__builtin_amdgcn_readfirstlane((int)heads[1]);
-          if (iA >= acc || iB >= RB) break;  // (uniform) a side is used up for good: the node is done
-        }
-        if (t == 0) heads[2] = nc;  // (wave 0 counted)
-        __syncthreads();
-        nc = (u32)__builtin_amdgcn_readfirstlane((int)heads[2]);
-      }
+      if (acc > 0 && RB > 0) nc = screen_step_walk<N>(b, w, n, at, acc, ob, RB, heads);
       outcome = (i64)nc;
-      if (nc == 0 && RB > 0) {
-        // the stable merge into the node's own region: a record's place is its index in its own
-        // list and its rank in the other one, by the round's comparison (A: B keys strictly
-        // below; B: A keys at or below).  With an empty accumulator it is the copy of the log's
-        // sorted records, ridx turned into column indices.
-        const i64 out = b.n_total + train_uniform(b.acc_off[n]);
-        const i64 m = acc + RB;
-        for (i64 e = t; e < m; e += NT) {
-          const bool sa = e < acc;
-          const i64 idx = sa ? e : e - acc;
-          const i64 q = (sa ? at : ob) + idx, base = sa ? ob : at;
-          const u64 ts = w.rts[q], hi = w.rhi[q], lo = w.rlo[q];
-          i64 lo_i = 0, hi_i = sa ? RB : acc;
-          while (lo_i < hi_i) {
-            const i64 mid = (lo_i + hi_i) >> 1;
-            const u64 mt = w.rts[base + mid];
-            bool below = mt < ts;
-            if (mt == ts) {
-              const u64 mh = w.rhi[base + mid];
-              below = mh < hi;
-              if (mh == hi) {
-                const u64 ml = w.rlo[base + mid];
-                below = sa ? ml < lo : ml <= lo;
-              }
-            }
-            if (below) lo_i = mid + 1;
-            else hi_i = mid;
-          }
-          const i64 d = out + idx + lo_i;
-          w.rts[d] = ts;
-          w.rhi[d] = hi;
-          w.rlo[d] = lo;
-          w.ridx[d] = sa ? w.ridx[q] : (u32)(ob + (i64)w.ridx[q]);  // the op's column index
-          w.rsym[d] = w.rsym[q];
-          w.rv0[d] = w.rv0[q];
-        }
-        acc = m;
+      if (nc == 0 && RB > 0) {  // the merge into the node's own region
+        screen_step_merge<N>(w, at, acc, ob, RB, b.n_total + train_uniform(b.acc_off[n]));
+        acc += RB;
         own = true;
       }
     }

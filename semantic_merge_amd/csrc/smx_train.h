@@ -32,6 +32,11 @@
 //   k_compose_train<N> a residency-capped grid; workgroup b runs trains b, b + grid, ... of
 //                      the class list one after another
 // Five launches, nothing waited for, allocated or read back.  The entry point is in smx_batch.hip.
+//
+// The step's rules per entry (train_staged, train_landed, train_conflict_record) and its three
+// loops in a workgroup (train_stage_loop, train_record_loop, train_land_loop) are stated here
+// once: k_compose_tree (smx_tree.h) runs the same loops, k_train_stage and k_train_land
+// (smx_train_step.h) the same rules.
 #pragma once
 
 #include "smx_batch.h"
@@ -152,6 +157,117 @@ __device__ __forceinline__ i64 train_uniform(i64 v) {
   return (i64)((u64)hi << 32 | lo);
 }
 
+// ---- the step's rules, per entry: stated here once, for k_compose_train, k_compose_tree
+// (smx_tree.h) and k_train_stage / k_train_land (smx_train_step.h) ----
+
+// The staged v0 / v1 of an entry: the op's own, except a move's -- those are what marshalling
+// the materialised move would give, the accumulated addr `a` / file `f` where there is one.
+// (v1_alt is read only where f is empty_str: it may be null while empty_str is SMX_NONE.)
+__device__ __forceinline__ void train_staged(u8 kind, i32 v0, i32 v1, i32 a, i32 f, i32 empty_str, const i32* v1_alt,
+                                             i64 j, i32& x0, i32& x1) {
+  x0 = v0, x1 = v1;
+  if (kind == SMX_KIND_MOVE) {
+    if (a != SMX_NONE) x0 = a;
+    // (an empty newFile: marshalling falls through to the op's own `file`)
+    if (f != SMX_NONE) x1 = f == empty_str ? v1_alt[j] : f;
+  }
+}
+
+// Per field, the last value a step gave that was not SMX_NONE.
+__device__ __forceinline__ i32 train_fold(i32 ra, i32 a) { return ra != SMX_NONE ? ra : a; }
+
+// Entry q of the accumulator a landing leaves: element e of the step (an entry of the
+// accumulator in below n_acc, else op e - n_acc of the log that starts at column lo) with the
+// step's addr / file / ctx folded in.
+__device__ __forceinline__ void train_landed(i64 e, i64 n_acc, i64 lo, const i32* ssrc, const i32* saddr,
+                                             const i32* sfile, const i32* sctx, i32 ra, i32 rf, i32 rx, i32* nsrc,
+                                             i32* naddr, i32* nfile, i32* nctx, i64 q) {
+  i32 s = (i32)(lo + (e - n_acc)), a = SMX_NONE, f = SMX_NONE, x = SMX_NONE;
+  if (e < n_acc) {
+    s = ssrc[e];
+    a = saddr[e];
+    f = sfile[e];
+    x = sctx[e];
+  }
+  nsrc[q] = s;
+  naddr[q] = train_fold(ra, a);
+  nfile[q] = train_fold(rf, f);
+  nctx[q] = train_fold(rx, x);
+}
+
+// A conflict pair of element indices (ea in the accumulator, eb in the log) as a record: the
+// two ops' column indices, and the addr and file the A op carried.
+__device__ __forceinline__ void train_conflict_record(i32* rec, i64 ea, i64 eb, i64 n_acc, i64 lo, const i32* ssrc,
+                                                      const i32* saddr, const i32* sfile) {
+  rec[0] = ssrc[ea];
+  rec[1] = (i32)(lo + (eb - n_acc));
+  rec[2] = saddr[ea];
+  rec[3] = sfile[ea];
+}
+
+// ---- the step's three loops in a workgroup of NT threads, for k_compose_train and k_compose_tree
+// (B: smx_train / smx_tree, W: TrainWs / TreeWs).  Each makes the thread index opaque: else each
+// array's per-thread address is computed once for the whole train and lives in registers across
+// compose_small ----
+
+// Stages the accumulator in (acc entries, gathered through ssrc with the moves rewritten) and
+// the log [lo, lo + n - acc) behind it at the slice R.
+template <int NT, typename B, typename W>
+__device__ __forceinline__ void train_stage_loop(const B& b, const W& w, i64 R, const i32* ssrc, const i32* saddr,
+                                                 const i32* sfile, int acc, int n, i64 lo) {
+  int tt = threadIdx.x;
+  asm volatile("" : "+v"(tt));
+#pragma unroll 1
+  for (int e = tt; e < n; e += NT) {
+    i64 j = lo + (e - acc);
+    i32 a = SMX_NONE, f = SMX_NONE;
+    if (e < acc) {
+      j = ssrc[e];
+      a = saddr[e];
+      f = sfile[e];
+    }
+    const u8 k = b.kind[j];
+    i32 x0, x1;
+    train_staged(k, b.v0[j], b.v1[j], a, f, b.empty_str, b.v1_alt, j, x0, x1);
+    w.kind[R + e] = k;
+    w.ts[R + e] = b.ts[j];
+    w.hi[R + e] = b.oid_hi[j];
+    w.lo[R + e] = b.oid_lo[j];
+    w.sym[R + e] = b.sym[j];
+    w.v0[R + e] = x0;
+    w.v1[R + e] = x1;
+  }
+}
+
+// The step's nc conflict pairs (element indices) as records in the region of conf_off[slot]: as
+// many as it holds, and one that conf_off does not describe holds none.
+template <int NT, typename B>
+__device__ __forceinline__ void train_record_loop(const B& b, i64 slot, i64 nc, const i32* pairs, const i32* ssrc,
+                                                  const i32* saddr, const i32* sfile, int acc, i64 lo) {
+  const i64 c0 = train_uniform(b.conf_off[slot]), c1 = train_uniform(b.conf_off[slot + 1]);
+  i64 cap = c0 < 0 || c1 < c0 ? 0 : c1 - c0;
+  if (cap > nc) cap = nc;
+  int tt = threadIdx.x;
+  asm volatile("" : "+v"(tt));
+#pragma unroll 1
+  for (i64 q = tt; q < cap; q += NT)
+    train_conflict_record(b.conflicts + 4 * (c0 + q), pairs[2 * q], pairs[2 * q + 1], acc, lo, ssrc, saddr, sfile);
+}
+
+// The k entries of the accumulator out from the step's result (res: order / addr / file / ctx,
+// arrays of arr words).
+template <int NT>
+__device__ __forceinline__ void train_land_loop(const i32* res, size_t arr, int k, const i32* ssrc, const i32* saddr,
+                                                const i32* sfile, const i32* sctx, int acc, i64 lo, i32* nsrc,
+                                                i32* naddr, i32* nfile, i32* nctx) {
+  int tt = threadIdx.x;
+  asm volatile("" : "+v"(tt));
+#pragma unroll 1
+  for (int q = tt; q < k; q += NT)
+    train_landed(res[q], acc, lo, ssrc, saddr, sfile, sctx, res[arr + q], res[2 * arr + q], res[3 * arr + q], nsrc,
+                 naddr, nfile, nctx, q);
+}
+
 template <int N>
 __global__ void __launch_bounds__(N / 2) k_compose_train(smx_train b, TrainWs w, const u32* cnt, const u32* list) {
   constexpr int NT = N / 2;
@@ -185,34 +301,7 @@ __global__ void __launch_bounds__(N / 2) k_compose_train(smx_train b, TrainWs w,
         const int n = acc + (int)nb;
         const i32* const ssrc = w.st + (size_t)cur * 4 * arr + R;
         const i32 *saddr = ssrc + arr, *sfile = ssrc + 2 * arr, *sctx = ssrc + 3 * arr;
-        // (the thread index made opaque per phase: else each array's per-thread address is
-        // computed once for the whole train and lives in registers across compose_small)
-        int tt = t;
-        asm volatile("" : "+v"(tt));
-#pragma unroll 1
-        for (int e = tt; e < n; e += NT) {
-          i64 j = lo + (e - acc);
-          i32 a = SMX_NONE, f = SMX_NONE;
-          if (e < acc) {
-            j = ssrc[e];
-            a = saddr[e];
-            f = sfile[e];
-          }
-          const u8 k = b.kind[j];
-          i32 x0 = b.v0[j], x1 = b.v1[j];
-          if (k == SMX_KIND_MOVE) {  // what marshalling the materialised move would give
-            if (a != SMX_NONE) x0 = a;
-            // (an empty newFile: marshalling falls through to the op's own `file`)
-            if (f != SMX_NONE) x1 = f == b.empty_str ? b.v1_alt[j] : f;
-          }
-          w.kind[R + e] = k;
-          w.ts[R + e] = b.ts[j];
-          w.hi[R + e] = b.oid_hi[j];
-          w.lo[R + e] = b.oid_lo[j];
-          w.sym[R + e] = b.sym[j];
-          w.v0[R + e] = x0;
-          w.v1[R + e] = x1;
-        }
+        train_stage_loop<NT>(b, w, R, ssrc, saddr, sfile, acc, n, lo);
         __syncthreads();
         const smx_ops ops = {(i64)acc, nb,       b.n_sym,   w.kind + R, w.ts + R, w.hi + R,
                              w.lo + R, w.sym + R, w.v0 + R, w.v1 + R,   0};
@@ -227,41 +316,12 @@ __global__ void __launch_bounds__(N / 2) k_compose_train(smx_train b, TrainWs w,
           outcome = -1;  // an op with kind >= 18 or sym >= n_sym in the log
         } else if (nc > 0) {
           outcome = nc;
-          const i64 c0 = train_uniform(b.conf_off[g]), c1 = train_uniform(b.conf_off[g + 1]);
-          i64 cap = c0 < 0 || c1 < c0 ? 0 : c1 - c0;
-          if (cap > nc) cap = nc;
-          tt = t;
-          asm volatile("" : "+v"(tt));
-#pragma unroll 1
-          for (i64 q = tt; q < cap; q += NT) {
-            const i32 ea = res[4 * arr + 2 * q], eb = res[4 * arr + 2 * q + 1];
-            i32* rec = b.conflicts + 4 * (c0 + q);
-            rec[0] = ssrc[ea];
-            rec[1] = (i32)(lo2 + (eb - acc));
-            rec[2] = saddr[ea];
-            rec[3] = sfile[ea];
-          }
+          train_record_loop<NT>(b, g, nc, res + 4 * arr, ssrc, saddr, sfile, acc, lo2);
         } else {
           outcome = 0;
           i32* const nsrc = w.st + (size_t)(cur ^ 1) * 4 * arr + R;
-          tt = t;
-          asm volatile("" : "+v"(tt));
-#pragma unroll 1
-          for (int q = tt; q < (int)k; q += NT) {
-            const i32 e = res[q];
-            i32 s = (i32)(lo2 + (e - acc)), a = SMX_NONE, f = SMX_NONE, x = SMX_NONE;
-            if (e < acc) {
-              s = ssrc[e];
-              a = saddr[e];
-              f = sfile[e];
-              x = sctx[e];
-            }
-            const i32 ra = res[arr + q], rf = res[2 * arr + q], rx = res[3 * arr + q];
-            nsrc[q] = s;
-            nsrc[arr + q] = ra != SMX_NONE ? ra : a;
-            nsrc[2 * arr + q] = rf != SMX_NONE ? rf : f;
-            nsrc[3 * arr + q] = rx != SMX_NONE ? rx : x;
-          }
+          train_land_loop<NT>(res, arr, (int)k, ssrc, saddr, sfile, sctx, acc, lo2, nsrc, nsrc + arr, nsrc + 2 * arr,
+                              nsrc + 3 * arr);
           cur ^= 1;
           acc = (int)k;
           ++landed;

@@ -6,15 +6,16 @@
 // size over the whole chip: a train of any size is therefore a host loop of
 //   k_train_stage   the step's input columns: the accumulator's, gathered through src with the
 //                   moves rewritten, and the log's behind them -- the staging loop of
-//                   k_compose_train, entry by entry
+//                   k_compose_train, entry by entry, by the same rule (train_staged)
 //   smx_compose     on those columns (n_a = n_acc, n_b = log_n, b_gap = 0)
-//   k_train_land    the landing loop of k_compose_train, or its conflict records
+//   k_train_land    the landing loop of k_compose_train, or its conflict records, by the same
+//                   rules (train_landed, train_conflict_record)
 // over columns that stay on the device.  Both kernels are streaming gathers: a thread per entry
 // on a grid-stride grid, coalesced writes, reads through src / order, no LDS, no barrier.  The
 // entry points are in smx_batch.hip.
 #pragma once
 
-#include "smx_common.h"
+#include "smx_train.h"  // the step's per-entry rules: train_staged, train_landed, train_conflict_record
 
 constexpr int TRAIN_STEP_T = 256;
 // (enough workgroups to fill the chip several times over; longer steps stride)
@@ -47,12 +48,8 @@ __global__ void __launch_bounds__(TRAIN_STEP_T) k_train_stage(smx_train_step s) 
     const u8 k = s.kind[j];
     const u32 y = s.sym[j];
     if (k >= SMX_N_KINDS || (i64)y >= s.n_sym) s.status[0] = -1;  // (copied as it is: smx_compose refuses it too)
-    i32 x0 = s.v0[j], x1 = s.v1[j];
-    if (k == SMX_KIND_MOVE) {  // what marshalling the materialised move would give
-      if (a != SMX_NONE) x0 = a;
-      // (an empty newFile: marshalling falls through to the op's own `file`)
-      if (f != SMX_NONE) x1 = f == s.empty_str ? s.v1_alt[j] : f;
-    }
+    i32 x0, x1;
+    train_staged(k, s.v0[j], s.v1[j], a, f, s.empty_str, s.v1_alt, j, x0, x1);
     s.st_kind[e] = k;
     s.st_ts[e] = s.ts[j];
     s.st_oid_hi[e] = s.oid_hi[j];
@@ -84,11 +81,7 @@ __global__ void __launch_bounds__(TRAIN_STEP_T) k_train_land(smx_train_step s) {
     for (i64 q = first; q < cap; q += stride) {
       const i64 ea = s.conflicts[2 * q], eb = s.conflicts[2 * q + 1];
       if (ea < 0 || ea >= s.n_acc || eb < s.n_acc || eb >= n) continue;
-      i32* const rec = s.records + 4 * q;
-      rec[0] = s.acc_src[ea];
-      rec[1] = (i32)(s.log_lo + (eb - s.n_acc));
-      rec[2] = s.acc_addr[ea];
-      rec[3] = s.acc_file[ea];
+      train_conflict_record(s.records + 4 * q, ea, eb, s.n_acc, s.log_lo, s.acc_src, s.acc_addr, s.acc_file);
     }
     return;
   }
@@ -100,17 +93,7 @@ __global__ void __launch_bounds__(TRAIN_STEP_T) k_train_land(smx_train_step s) {
   for (i64 q = first; q < len; q += stride) {
     const i64 e = s.order[q];
     if (e < 0 || e >= n) continue;
-    i32 src = (i32)(s.log_lo + (e - s.n_acc)), a = SMX_NONE, f = SMX_NONE, x = SMX_NONE;
-    if (e < s.n_acc) {
-      src = s.acc_src[e];
-      a = s.acc_addr[e];
-      f = s.acc_file[e];
-      x = s.acc_ctx[e];
-    }
-    const i32 ra = s.addr[q], rf = s.file[q], rx = s.ctx[q];
-    s.out_src[q] = src;
-    s.out_addr[q] = ra != SMX_NONE ? ra : a;
-    s.out_file[q] = rf != SMX_NONE ? rf : f;
-    s.out_ctx[q] = rx != SMX_NONE ? rx : x;
+    train_landed(e, s.n_acc, s.log_lo, s.acc_src, s.acc_addr, s.acc_file, s.acc_ctx, s.addr[q], s.file[q], s.ctx[q],
+                 s.out_src, s.out_addr, s.out_file, s.out_ctx, q);
   }
 }

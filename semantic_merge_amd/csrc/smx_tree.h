@@ -86,12 +86,39 @@ __device__ __forceinline__ bool tree_log_ok(const smx_tree& b, const TreeWs& w, 
   return l >= 0 && l < b.n_logs && w.linfo[l] >= 0;
 }
 
+// ---- the two structural rules of a tree, for k_tree_prepass and k_screen_tree_prepass
+// (smx_screen_tree.h) ----
+
+// The level rule: level d's nodes [lo, hi), none where the level is not valid.  A level is valid
+// when its level_off entries are (vinfo, screen_log_bounds' verdict: not negative, not below an
+// earlier entry, not decreasing, not past n_nodes), level 0 starts at node 0 and the last level
+// ends at n_nodes; valid levels never overlap.
+__device__ __forceinline__ void tree_level(const i64* level_off, const i32* vinfo, i64 d, i64 n_levels, i64 n_nodes,
+                                           i64& lo, i64& hi) {
+  lo = hi = 0;
+  if (vinfo[d] >= 0) {
+    lo = level_off[d];
+    hi = level_off[d + 1];
+    if ((d == 0 && lo != 0) || (d == n_levels - 1 && hi != n_nodes)) lo = hi = 0;
+  }
+}
+
+// The parent rule, for a node of level d with parent p: a level-0 node has none; any other's
+// lies in the level before, [plo, phi) (that level invalid: no node does), and did not fail
+// (info[p] >= 0).  ps: the parent's info, 0 without a parent.
+template <typename T>
+__device__ __forceinline__ bool tree_parent_ok(i64 d, i64 p, i64 plo, i64 phi, const T* info, i64& ps) {
+  ps = 0;
+  if (d == 0) return p == SMX_NONE;
+  if (p < plo || p >= phi) return false;
+  ps = info[p];
+  return ps >= 0;
+}
+
 // Every structural check, before any column of a node is read through an unchecked index.  A
-// level is valid when its level_off entries are (not negative, not below an earlier entry, not
-// decreasing, not past n_nodes), level 0 starts at node 0 and the last level ends at n_nodes;
-// valid levels never overlap.  A node outside every valid level fails, and so does a node whose
-// parent is not in the level before (that level invalid: no node is), whose parent failed,
-// whose res_off entries are bad or whose region is below min(path sum, SMALL_N).
+// node outside every valid level fails (tree_level), and so does a node whose parent breaks the
+// parent rule (tree_parent_ok), whose res_off entries are bad or whose region is below
+// min(path sum, SMALL_N).
 __global__ void __launch_bounds__(1024) k_tree_prepass(smx_tree b, TreeWs w) {
   __shared__ i64 sc[1024 / WAVE + 1];
   __shared__ u32 c[BATCH_CLASSES];
@@ -105,25 +132,11 @@ __global__ void __launch_bounds__(1024) k_tree_prepass(smx_tree b, TreeWs w) {
   for (i64 d = 0; d < b.n_levels; ++d) {
     if (t < BATCH_CLASSES) c[t] = 0;
     __syncthreads();
-    i64 lo = 0, hi = 0;
-    if (w.vinfo[d] >= 0) {
-      lo = b.level_off[d];
-      hi = b.level_off[d + 1];
-      if ((d == 0 && lo != 0) || (d == b.n_levels - 1 && hi != b.n_nodes)) lo = hi = 0;
-    }
+    i64 lo, hi;
+    tree_level(b.level_off, w.vinfo, d, b.n_levels, b.n_nodes, lo, hi);
     for (i64 n = lo + t; n < hi; n += 1024) {
-      const i64 p = b.node_parent[n];
-      bool good = w.rinfo[n] >= 0;
-      i64 ps = 0;
-      if (d == 0) {
-        good = good && p == SMX_NONE;
-      } else {
-        good = good && p >= plo && p < phi;
-        if (good) {
-          ps = w.ninfo[p];
-          good = ps >= 0;
-        }
-      }
+      i64 ps;
+      bool good = w.rinfo[n] >= 0 && tree_parent_ok(d, b.node_parent[n], plo, phi, w.ninfo, ps);
       if (good) {
         const i64 l = b.node_log[n];
         if (tree_log_ok(b, w, l)) ps += b.log_off[l + 1] - b.log_off[l];
@@ -151,9 +164,9 @@ __global__ void __launch_bounds__(1024) k_tree_prepass(smx_tree b, TreeWs w) {
     }
 }
 
-// One level's nodes of one class.  k_compose_train's step, restated (that kernel's register
-// workarounds are tuned to its loop; see its comments for the opaque thread index and offset):
-// the accumulator in is the region of node_acc[parent], node_counts[2 * parent] entries long, and
+// One level's nodes of one class.  k_compose_train's step, by its three loops (train_stage_loop,
+// train_record_loop, train_land_loop in smx_train.h) in a skeleton of this kernel's own: the
+// accumulator in is the region of node_acc[parent], node_counts[2 * parent] entries long, and
 // the accumulator out the node's own region.
 template <int N>
 __global__ void __launch_bounds__(N / 2) k_compose_tree(smx_tree b, TreeWs w, i32 level, const u32* cnt,
@@ -193,32 +206,7 @@ __global__ void __launch_bounds__(N / 2) k_compose_tree(smx_tree b, TreeWs w, i3
       // (acc + nb is at most min(path sum, SMALL_N): the class's N at most, and the region's size)
       const int m = acc + (int)nb;
       const i32 *ssrc = b.src + A, *saddr = b.addr + A, *sfile = b.file + A, *sctx = b.ctx + A;
-      int tt = t;
-      asm volatile("" : "+v"(tt));
-#pragma unroll 1
-      for (int e = tt; e < m; e += NT) {
-        i64 j = lo + (e - acc);
-        i32 a = SMX_NONE, f = SMX_NONE;
-        if (e < acc) {
-          j = ssrc[e];
-          a = saddr[e];
-          f = sfile[e];
-        }
-        const u8 k = b.kind[j];
-        i32 x0 = b.v0[j], x1 = b.v1[j];
-        if (k == SMX_KIND_MOVE) {  // what marshalling the materialised move would give
-          if (a != SMX_NONE) x0 = a;
-          // (an empty newFile: marshalling falls through to the op's own `file`)
-          if (f != SMX_NONE) x1 = f == b.empty_str ? b.v1_alt[j] : f;
-        }
-        w.kind[R + e] = k;
-        w.ts[R + e] = b.ts[j];
-        w.hi[R + e] = b.oid_hi[j];
-        w.lo[R + e] = b.oid_lo[j];
-        w.sym[R + e] = b.sym[j];
-        w.v0[R + e] = x0;
-        w.v1[R + e] = x1;
-      }
+      train_stage_loop<NT>(b, w, R, ssrc, saddr, sfile, acc, m, lo);
       __syncthreads();
       const smx_ops ops = {(i64)acc, nb,       b.n_sym,   w.kind + R, w.ts + R, w.hi + R,
                            w.lo + R, w.sym + R, w.v0 + R, w.v1 + R,   0};
@@ -233,41 +221,12 @@ __global__ void __launch_bounds__(N / 2) k_compose_tree(smx_tree b, TreeWs w, i3
         outcome = -1;  // an op with kind >= 18 or sym >= n_sym in the log
       } else if (nc > 0) {
         outcome = nc;
-        const i64 c0 = train_uniform(b.conf_off[n]), c1 = train_uniform(b.conf_off[n + 1]);
-        i64 cap = c0 < 0 || c1 < c0 ? 0 : c1 - c0;
-        if (cap > nc) cap = nc;
-        tt = t;
-        asm volatile("" : "+v"(tt));
-#pragma unroll 1
-        for (i64 q = tt; q < cap; q += NT) {
-          const i32 ea = res[4 * arr + 2 * q], eb = res[4 * arr + 2 * q + 1];
-          i32* rec = b.conflicts + 4 * (c0 + q);
-          rec[0] = ssrc[ea];
-          rec[1] = (i32)(lo + (eb - acc));
-          rec[2] = saddr[ea];
-          rec[3] = sfile[ea];
-        }
+        train_record_loop<NT>(b, n, nc, res + 4 * arr, ssrc, saddr, sfile, acc, lo);
       } else {
         outcome = 0;
         landed = true;
-        tt = t;
-        asm volatile("" : "+v"(tt));
-#pragma unroll 1
-        for (int q = tt; q < (int)k; q += NT) {
-          const i32 e = res[q];
-          i32 s = (i32)(lo + (e - acc)), a = SMX_NONE, f = SMX_NONE, x = SMX_NONE;
-          if (e < acc) {
-            s = ssrc[e];
-            a = saddr[e];
-            f = sfile[e];
-            x = sctx[e];
-          }
-          const i32 ra = res[arr + q], rf = res[2 * arr + q], rx = res[3 * arr + q];
-          b.src[R + q] = s;
-          b.addr[R + q] = ra != SMX_NONE ? ra : a;
-          b.file[R + q] = rf != SMX_NONE ? rf : f;
-          b.ctx[R + q] = rx != SMX_NONE ? rx : x;
-        }
+        train_land_loop<NT>(res, arr, (int)k, ssrc, saddr, sfile, sctx, acc, lo, b.src + R, b.addr + R, b.file + R,
+                            b.ctx + R);
         acc = (int)k;
       }
     }
